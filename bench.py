@@ -23,6 +23,17 @@ short separate pass after the timed region; `bf16` = BASELINE configs[2] (batch 
 timed steps, roofline against the nominal 2.5 PFLOP/s and step-1 loss vs the CPU oracle) -- per-GPU batch 32 under
 N ranks is configs[3]; `predict` = BASELINE configs[4] (sliding-window scene prediction, pixels/s, GPU and CPU);
 `feed` = the same step fed a FRESH host batch per step through the pinned-host -> device double-buffered loader.
+
+`--dump-outputs DIR` writes what the last timed step of the headline configuration computed (rank 0), as float32
+`DIR/<name>.npy`: `loss`, `loss_terms` (distance / edge / crop), the `distance` / `edge` / `crop` maps, and the model
+after the step -- `parameters` (flat master weights), `gradients` (flat) and `buffers` (BatchNorm running statistics).
+The dumped step is the last of the K timed steps, but it starts from the seeded initial training state (weights, AdamW
+moments and step count, BatchNorm buffers), restored on the launch stream just before it: several float reductions of
+the step (split-K weight gradients, norm and clip sums) add in arrival order, and AdamW amplifies those rounding
+differences step after step, so the state the preceding steps leave differs from run to run. With the restore, the
+dumped step has the same inputs on every run, whatever K and W, and its outputs differ only by that rounding. Without
+--dump-outputs nothing is restored. Arrays that would take the dump past 64 MB are replaced by a fixed sample: sorted
+flat indices drawn by a generator seeded with crc32(name), the same indices for the same array size on every run.
 """
 from __future__ import annotations
 
@@ -88,6 +99,8 @@ def parse():
                     help="internal: one block of the default line in a process of its own (see run_child)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch + rendezvous check only (gloo, no GPU, no kernels): what tests/test_bench_launch.py runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32, at most 64 MB in all)")
     return ap.parse_args()
 
 
@@ -423,6 +436,43 @@ def cpu_first_loss(batch: int, hidden: int, threads: int = 0) -> float:
     return float(loss)
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def capture_outputs(trainer, loss) -> dict:
+    """Host float32 copies of what the step just run left for its caller: the loss it returned, the per-head losses and
+    maps of its forward, and the model it updated (flat weights, flat gradients, BatchNorm running statistics)."""
+    import torch
+
+    arrays = {"loss": loss, "loss_terms": trainer.last_losses}
+    arrays.update(trainer.last_outputs)
+    arrays["parameters"] = trainer.store.flat
+    arrays["gradients"] = trainer.store.flat_grad
+    bufs = [b.reshape(-1).float() for b in trainer.model.buffers() if b.is_floating_point()]
+    if bufs:
+        arrays["buffers"] = torch.cat(bufs)
+    return {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+
+
+def write_outputs(arrays: dict, directory: str) -> None:
+    """DIR/<name>.npy per array; arrays above a common element cap (halved until the dump fits DUMP_MAX_BYTES) are
+    written as a fixed sample: sorted flat indices from a generator seeded with crc32(name)."""
+    import zlib
+
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    cap = max(a.size for a in arrays.values())
+    while sum(min(a.size, cap) for a in arrays.values()) * 4 > DUMP_MAX_BYTES:
+        cap //= 2
+    for name, a in arrays.items():
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+            print(f"bench.py: {name}.npy is a fixed sample of {cap} of its {arrays[name].size} elements", file=sys.stderr)
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def launch_ranks(args) -> int:
     """`python bench.py --gpus N` with N > 1 outside torch.distributed.run: start the ranks as a CHILD process (this
     parent has not touched the GPU and never does), relay rank 0's JSON line, return the child's exit code."""
@@ -475,7 +525,7 @@ def ddp1_block(args) -> dict:
     GPU_MAX_HW_QUEUES <= 5, engine.branch_streams_allowed), weight-gradient slice sums flushed once per ready bucket. fp32 batch 8 and bf16 batch 32 (BASELINE configs[1] / configs[3] per GPU),
     each in a fresh child process. One rank exchanges nothing over xGMI: this prices the stream set and the exposed
     launch / wait time of the collectives, NOT the scaling curve (reference: strategy="ddp",
-    /root/reference/src/cultionet/model.py:101,168-186)."""
+    the reference's src/cultionet/model.py:101,168-186)."""
     out = {"workload": "train step with a live one-rank RCCL group (CN_FORCE_COMM=1): the data-parallel stream set",
            "note": "one rank: no bytes cross xGMI; no scaling curve is implied"}
     for dt in ("f32", "bf16"):
@@ -515,6 +565,19 @@ class TrainLeg:
         self.trainer = HipTrainer(self.lit, gradient_clip_val=1.0, comm=comm,
                                   precision="bf16-mixed" if dtype == "bf16" else "32-true")
 
+    def training_state(self):
+        """Copies of what a training step starts from: flat weights, AdamW moments and step count, module buffers."""
+        tr = self.trainer
+        tensors = [tr.store.flat, tr.exp_avg, tr.exp_avg_sq] + list(tr.model.buffers())
+        return [t.clone() for t in tensors], tr.step_count
+
+    def restore_training_state(self, state) -> None:
+        tr = self.trainer
+        copies, tr.step_count = state
+        for dst, src in zip([tr.store.flat, tr.exp_avg, tr.exp_avg_sq] + list(tr.model.buffers()), copies):
+            dst.copy_(src)
+        tr.store.bump()  # the packed weight copies follow the restored weights
+
     def sync(self):
         import torch
         import torch.distributed as dist
@@ -523,8 +586,10 @@ class TrainLeg:
             dist.barrier()
         torch.cuda.synchronize()
 
-    def run(self, steps: int, warmup: int, extras: bool):
-        """W untimed + K timed steps (barrier + synchronize on both sides, max over ranks). Returns the record."""
+    def run(self, steps: int, warmup: int, extras: bool, capture: bool = False):
+        """W untimed + K timed steps (barrier + synchronize on both sides, max over ranks). Returns the record.
+        capture: the last timed step starts from the initial training state (every rank), and rank 0 keeps host copies
+        of its outputs in ``self.outputs`` (after the clock)."""
         import torch
         import torch.distributed as dist
 
@@ -532,6 +597,7 @@ class TrainLeg:
         from cultionet_amd import engine as E
 
         trainer, batch = self.trainer, self.batch
+        initial = self.training_state() if capture else None  # the seeded state the dumped step starts from
         first_loss = None
         for i in range(warmup):
             l = trainer.training_step(batch)
@@ -562,7 +628,9 @@ class TrainLeg:
         _lib.call("cn_profile_set_filter", top_name.encode() if top_name else None)
         _lib.call("cn_profile_begin")
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for i in range(steps):
+            if initial is not None and i == steps - 1:
+                self.restore_training_state(initial)  # (--dump-outputs: the same inputs for the dumped step on every run)
             loss = trainer.training_step(batch)
         # closing fence: this rank's GPU first, THEN the barrier (so its cost / the wait for slower ranks is visible as
         # `config.end_barrier_ms` instead of hiding inside the timed region), then the clock
@@ -580,6 +648,8 @@ class TrainLeg:
             by_kernel[top_name]["timed_region"] = {"ms_per_step": ms, "tflops": (flops / (ms * 1e-3) / 1e12) if ms else 0.0,
                                                    "launches_per_step": nl}
         loss_val = float(loss.item())
+        if capture and self.rank == 0:  # before the untimed steps below move the weights on
+            self.outputs = capture_outputs(trainer, loss)
         if first_loss is None:
             first_loss = loss_val if steps == 1 else None
         comm_ms = buckets = None
@@ -822,9 +892,12 @@ def main():
     extras = not args.no_extras
     child = args.child == "train"
     leg = TrainLeg(dev, rank, world, comm, use_dist, args.dtype, B, args.hidden)
-    rec = leg.run(args.steps, args.warmup, extras)
+    rec = leg.run(args.steps, args.warmup, extras, capture=args.dump_outputs is not None)
     out = None
     if rank == 0:
+        if args.dump_outputs is not None:
+            write_outputs(leg.outputs, args.dump_outputs)
+            del leg.outputs
         first_loss = rec.pop("_first_loss")
         out = {"metric": "train_chips_per_sec", "value": rec["value"], "unit": "chips/s", "n_gpus": world,
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": rec["ms_per_step"], "higher_is_better": True,

@@ -19,6 +19,8 @@ stream (the predictor's stitch kernel does). Inference only -- a training step i
 """
 from __future__ import annotations
 
+import contextlib
+import gc
 import typing as T
 
 import torch
@@ -28,6 +30,23 @@ from . import engine as E
 
 
 MAX_PLANS = 4  # per model: (input shape, precision) slots kept alive
+
+
+@contextlib.contextmanager
+def _recording_pool(pool):
+    """``torch.cuda.use_mem_pool(pool)`` with Python's cycle collector held off until the scope closes. A dropped plan can
+    be freed by that collector (a step plan and its slice-sum table point at each other), at whatever allocation it
+    happens to run; its MemPool's destructor then empties that pool's cache, which the caching allocator refuses with an
+    internal assert -- a std::terminate from inside a destructor, i.e. an abort -- while any thread routes allocations
+    to a pool, as recording does. Held off, such plans are collected after the scope instead."""
+    enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.use_mem_pool(pool):
+            yield
+    finally:
+        if enabled:
+            gc.enable()
 
 
 class ForwardPlan:
@@ -103,7 +122,7 @@ def forward(model, x: torch.Tensor, bf16: bool, run: T.Callable[[torch.Tensor], 
         return rc
 
     epoch0 = E.workspace_epoch()
-    with torch.cuda.use_mem_pool(plan.pool):
+    with _recording_pool(plan.pool):
         plan.x = torch.empty_like(x)
         plan.x.copy_(x)
         _lib.call = recording
@@ -187,7 +206,7 @@ def record_step(trainer, batch, eager: T.Callable) -> StepPlan:
         ops.append((0, fn, args))
         return rc
 
-    with torch.cuda.use_mem_pool(plan.pool):
+    with _recording_pool(plan.pool):
         # the plan's inputs in the CANONICAL form the loss / forward kernels consume (x fp32, labels int64, distances
         # fp32, all dense): `dst.copy_(src)` of every replayed step then does any cast / re-striding on the device, and no
         # torch conversion kernel (y.long(), .contiguous() -- which a launch plan cannot see) sits between the plan's

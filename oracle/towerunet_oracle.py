@@ -2,9 +2,9 @@
 
 TEST INFRASTRUCTURE ONLY (see oracle/__init__.py). This is the CPU checker and
 the ``cpu_baseline`` ("port") that travels to the GPU box; the reference's own
-Python never does. It is validated against the stub-imported reference in this
-container by tests/test_oracle_vs_reference.py (max |diff| <= 1e-6 on outputs,
-loss and gradients) and against the committed fixtures in tests/golden.
+Python never does. It is validated against the committed fixtures in
+tests/golden, written by the reference itself (oracle/make_golden.py), by
+tests/test_oracle_golden.py (outputs, loss, gradient norms and probes).
 
 Each class cites the reference file:line it restates (paths relative to
 /root/reference/src/cultionet). Module attribute names are chosen so that

@@ -56,3 +56,44 @@ def test_default_bench_line_has_every_block():
         assert d1[dt]["rccl_ranks"] == 1 and d1[dt]["buckets_per_step"] >= 1 and d1[dt]["value"] > 0
         assert d1[dt]["comm_ms_exposed"] is not None
         assert d["config"][f"ddp1_{dt}_chips_per_s"] == d1[dt]["value"]
+
+
+def _dump(out, steps, warmup):
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup",
+                        str(warmup), "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(out)],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, p.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs: the arrays of the last timed step as float32 .npy within 64 MB; the loss is the one the JSON line
+    reports for that step, and the maps are the [batch, 1, 100, 100] probabilities of the headline configuration. The
+    dumped step starts from the seeded initial state, so another run -- other K and W included -- dumps the same arrays
+    to float32 rounding (the weight-gradient sums add in arrival order)."""
+    import numpy as np
+
+    out = tmp_path / "dump"
+    d = _dump(out, 3, 2)
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    files = sorted(os.listdir(out))
+    for name in ("loss", "loss_terms", "distance", "edge", "crop", "parameters", "gradients", "buffers"):
+        assert name + ".npy" in files, files
+    assert sum(os.path.getsize(out / f) for f in files) <= 64 << 20
+    arrays = {f[:-4]: np.load(out / f) for f in files}
+    for name, a in arrays.items():
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all(), name
+    assert arrays["loss"].shape == (1,) and abs(float(arrays["loss"][0]) - d["config"]["loss"]) <= 1e-6
+    assert arrays["loss_terms"].shape == (3,)
+    assert abs(float(arrays["loss_terms"].mean()) - float(arrays["loss"][0])) <= 1e-5
+    for k in ("distance", "edge", "crop"):
+        assert arrays[k].shape == (8, 1, 100, 100) and 0.0 <= arrays[k].min() and arrays[k].max() <= 1.0, k
+    assert np.abs(arrays["gradients"]).max() > 0
+    again = tmp_path / "again"
+    assert _dump(again, 2, 0)["steps"] == 2
+    for name, a in arrays.items():
+        b = np.load(again / (name + ".npy"))
+        assert b.shape == a.shape and np.abs(a - b).max() <= 1e-5 * np.abs(a).max(), name

@@ -41,9 +41,10 @@ def test_groups_with_members_that_would_be_padded_are_ignored():
     assert [id(p) for p in ParamStore._with_contiguous_groups(h, params)] == [id(p) for p in params]
 
 
-def test_spawn_runs_inline_without_a_gpu():
+def test_spawn_runs_inline_without_a_gpu(monkeypatch):
     from cultionet_amd import engine as E
 
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)  # the same on a machine that has one
     x = E.Var(torch.zeros(1, 2, 3, 3))
     seen = []
     br, res = E.spawn(lambda v: seen.append(v) or 7, [x], 0)

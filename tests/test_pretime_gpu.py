@@ -1,6 +1,6 @@
 """The fused PreTimeReduction kernel family (cn_pretime_*; reference models/nunet.py:18-105) through the C ABI against
-the CPU oracle's PreTimeReduction module (plain torch fp32, pinned bit-exact to the imported reference by
-tests/test_oracle_vs_reference.py): training forward (batch statistics, running-statistics update), inference forward,
+the CPU oracle's PreTimeReduction module (plain torch fp32, pinned to the reference's own vectors by
+tests/test_oracle_golden.py): training forward (batch statistics, running-statistics update), inference forward,
 and every parameter gradient of the backward. fp32 NCHW output: 2e-5 * scale (outputs), 1e-4 * scale (gradients), as the
 other fp32 kernels; bf16 NHWC output: 6e-3 * scale."""
 import ctypes
