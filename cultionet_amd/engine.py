@@ -2272,6 +2272,45 @@ TGT_FLOAT, TGT_EQ, TGT_RANGE, TGT_ONEHOT = 0, 1, 2, 3
 MSK_NONE, MSK_LABEL, MSK_I64, MSK_F32 = 0, 1, 2, 3
 
 
+def _loss_pred(pred: Var) -> torch.Tensor:
+    """pred of a Tanimoto loss: fp32 [B,C,H,W] whose inner dims are dense (the kernels take a batch stride only)."""
+    pt = pred.t
+    if not pt.is_cuda or pt.dtype != torch.float32 or pt.dim() != 4:
+        raise RuntimeError(f"Tanimoto losses need an fp32 [B,C,H,W] device tensor, got {pt.dtype} {tuple(pt.shape)}")
+    if not _dense_inner(pt):
+        raise RuntimeError("Tanimoto losses need pred with dense C,H,W (a batch stride is the only freedom)")
+    return pt
+
+
+def _loss_term_check(B: int, C: int, HW: int, kw: T.Dict[str, T.Any]) -> None:
+    """The kernels index target_f as [B][C][HW] and labels / mask as [B][HW] with no bounds of their own: check every
+    buffer a mode reads before anything is launched."""
+    tmode, mmode = int(kw["target_mode"]), int(kw["mask_mode"])
+    if tmode not in (TGT_FLOAT, TGT_EQ, TGT_RANGE, TGT_ONEHOT) or mmode not in (MSK_NONE, MSK_LABEL, MSK_I64, MSK_F32):
+        raise ValueError(f"unknown target_mode {tmode} / mask_mode {mmode}")
+
+    def dense(name, t, dtype, numel):
+        if t is None:
+            raise ValueError(f"{name} is required by target_mode {tmode} / mask_mode {mmode}")
+        if not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+            raise RuntimeError(f"{name} must be a contiguous {dtype} device tensor, got {t.dtype} "
+                               f"(contiguous={t.is_contiguous()}, device={t.device})")
+        if t.numel() != numel:
+            raise ValueError(f"{name} must hold {numel} elements, got {t.numel()} {tuple(t.shape)}")
+
+    labels, target_f, mask = kw.get("labels"), kw.get("target_f"), kw.get("mask")
+    if labels is not None and labels.dtype != torch.int64:
+        raise RuntimeError("labels must be int64")
+    if tmode != TGT_FLOAT or mmode == MSK_LABEL:
+        dense("labels", labels, torch.int64, B * HW)
+    if tmode == TGT_FLOAT:
+        dense("target_f", target_f, torch.float32, B * C * HW)
+    if mmode == MSK_I64:
+        dense("mask", mask, torch.int64, B * HW)
+    elif mmode == MSK_F32:
+        dense("mask", mask, torch.float32, B * HW)
+
+
 def tanimoto_loss(pred: Var, *, target_f: T.Optional[torch.Tensor] = None, labels: T.Optional[torch.Tensor] = None,
                   mask: T.Optional[torch.Tensor] = None, target_mode: int, mask_mode: int, klass: int = 0,
                   loss_kind: int = 0, weight: float = 1.0, smooth: float = 1e-5, depth: int = 5,
@@ -2282,16 +2321,12 @@ def tanimoto_loss(pred: Var, *, target_f: T.Optional[torch.Tensor] = None, label
     tensor), when given, is incremented by ``weight * loss`` on the device.
     """
     tape = current_tape()
-    pt = _check(pred.t)
+    pt = _loss_pred(pred)
     B, C = pt.shape[0], pt.shape[1]
     HW = int(pt[0, 0].numel())
     dev = pt.device
-    if labels is not None and labels.dtype != torch.int64:
-        raise RuntimeError("labels must be int64")
-    if target_f is not None:
-        _check(target_f)
-        if not target_f.is_contiguous():
-            raise RuntimeError("float target must be contiguous")
+    _loss_term_check(B, C, HW, dict(target_f=target_f, labels=labels, mask=mask, target_mode=target_mode,
+                                    mask_mode=mask_mode))
     sums = _alloc(5 * B, torch.float64, dev)
     coef = _alloc(4 * B, torch.float32, dev)
     loss = _alloc(1, torch.float32, dev)
@@ -2324,20 +2359,19 @@ def tanimoto_loss_multi(preds: T.Sequence[Var], terms: T.Sequence[T.Dict[str, T.
 
     tape = current_tape()
     n = len(preds)
+    if not 1 <= n <= 4:
+        raise ValueError(f"tanimoto_loss_multi: 1..4 heads, got {n}")
+    if len(terms) != n or (weights is not None and len(weights) != n):
+        raise ValueError("tanimoto_loss_multi: one term (and one weight) per head")
     weights = [1.0] * n if weights is None else [float(w) for w in weights]
-    pts = [_check(p.t) for p in preds]
+    pts = [_loss_pred(p) for p in preds]
     B = pts[0].shape[0]
     HW = int(pts[0][0, 0].numel())
     dev = pts[0].device
-    for pt in pts:
+    for pt, kw in zip(pts, terms):
         if pt.shape[0] != B or int(pt[0, 0].numel()) != HW:
             raise ValueError("tanimoto_loss_multi: the heads must share batch size and H*W")
-    for kw in terms:
-        lab, tf = kw.get("labels"), kw.get("target_f")
-        if lab is not None and lab.dtype != torch.int64:
-            raise RuntimeError("labels must be int64")
-        if tf is not None and not _check(tf).is_contiguous():
-            raise RuntimeError("float target must be contiguous")
+        _loss_term_check(B, pt.shape[1], HW, kw)
     sums = _alloc(5 * B * n, torch.float64, dev)
     coef = _alloc(4 * B * n, torch.float32, dev)
     loss = _alloc(n, torch.float32, dev)

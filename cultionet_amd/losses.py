@@ -17,22 +17,35 @@ from . import engine as E
 from .autograd_bridge import tanimoto_autograd
 
 
+def _broadcast(t: torch.Tensor, shape: T.Tuple[int, ...], what: str) -> torch.Tensor:
+    try:
+        return t.expand(shape).contiguous()
+    except RuntimeError as e:
+        raise ValueError(f"{what} of shape {tuple(t.shape)} does not broadcast to {shape}") from e
+
+
 def _kernel_args(inputs: torch.Tensor, targets: torch.Tensor, mask: T.Optional[torch.Tensor], one_hot_targets: bool):
-    C = inputs.shape[1]
+    """LossPreprocessing (losses.py:9-59) as kernel arguments. The reference multiplies broadcast-legal masks and
+    targets into the inputs; the kernels index labels / masks as dense [B][HW] and float targets as [B][C][HW], so
+    they are expanded to batch B here. A mask with several channels has no kernel mode."""
+    B, C, H, W = inputs.shape
     kw: T.Dict[str, T.Any] = {}
-    if targets.dtype == torch.int64:
-        if one_hot_targets and C > 1:
-            kw.update(labels=targets.contiguous(), target_mode=E.TGT_ONEHOT)
-        else:  # class index == value for a single channel: t = (y == 1) would drop other classes; use float
-            kw.update(target_f=targets.to(torch.float32).reshape(inputs.shape).contiguous(), target_mode=E.TGT_FLOAT)
-    else:
-        kw.update(target_f=targets.to(torch.float32).reshape(inputs.shape).contiguous(), target_mode=E.TGT_FLOAT)
+    if targets.dtype == torch.int64 and one_hot_targets and C > 1:
+        kw.update(labels=_broadcast(targets, (B, H, W), "one-hot targets"), target_mode=E.TGT_ONEHOT)
+    else:  # class index == value for a single channel: t = (y == 1) would drop other classes; use float
+        t = targets.unsqueeze(1) if targets.dim() == 3 else targets
+        kw.update(target_f=_broadcast(t.to(torch.float32), (B, C, H, W), "targets"), target_mode=E.TGT_FLOAT)
     if mask is None:
         kw.update(mask=None, mask_mode=E.MSK_NONE)
-    elif mask.dtype == torch.int64:
-        kw.update(mask=mask.contiguous(), mask_mode=E.MSK_I64)
+        return kw
+    m = mask.unsqueeze(1) if mask.dim() == 3 else mask
+    if m.dim() > 4 or (m.dim() == 4 and m.shape[1] != 1):
+        raise NotImplementedError(f"a mask of shape {tuple(mask.shape)}: the loss kernels take one mask channel")
+    m = _broadcast(m, (B, 1, H, W), "mask")
+    if m.dtype == torch.int64:
+        kw.update(mask=m, mask_mode=E.MSK_I64)
     else:
-        kw.update(mask=mask.to(torch.float32).contiguous(), mask_mode=E.MSK_F32)
+        kw.update(mask=m.to(torch.float32).contiguous(), mask_mode=E.MSK_F32)
     return kw
 
 
