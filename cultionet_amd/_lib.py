@@ -100,6 +100,7 @@ SIGNATURES = {
     "cn_bn_act_fwd_bf16": [P, L, P, P, P, P, P, L, P, L, P, P, P, L, I, I, F, F, I, P, I, P],
     "cn_bn_act_bwd_bf16": [P, L, P, L, P, P, P, P, P, L, P, P, P, L, I, I, I, I, P],
     "cn_bn_group_workspace_floats_bf16": [I, I],
+    "cn_bn_workspace_head_ints": [],
     "cn_bn_act_group_fwd_bf16": [I, P, L, P, P, P, P, P, L, P, L, P, P, P, L, I, I, F, F, I, I, P, I, P],
     "cn_bn_act_group_bwd_bf16": [I, P, L, P, L, P, P, P, P, P, L, P, P, P, P, L, I, I, I, P],
     "cn_channel_sum_bf16": [P, L, L, I, P, I, P, P],

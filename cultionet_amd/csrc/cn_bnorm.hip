@@ -735,6 +735,9 @@ static inline long bbg_coef_off(int G, int C) {
 }
 static inline long bbg_part_off(int G, int C) { return (bbg_coef_off(G, C) + (long)G * 2 * C + 63) / 64 * 64; }
 static inline long bbg_domain_floats(int C) { return (cn_t2_body_floats(BBN_MAX_BLOCKS, 2 * C) + 63) / 64 * 64; }
+// Ints at the head of that workspace holding every ticket counter (all zero between calls).
+extern "C" int cn_bn_workspace_head_ints(void) { return CN_BNWS_HEAD_INTS; }
+
 extern "C" long cn_bn_group_workspace_floats_bf16(int G, int C) {
   const long own = bbg_part_off(G, C) + (long)G * bbg_domain_floats(C);
   // a convolution that finishes its own statistics (cn_conv2d_fwd_grouped_bnstats_bf16) parks its group rows at the

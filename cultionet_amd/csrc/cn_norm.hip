@@ -29,7 +29,7 @@ __global__ __launch_bounds__(256) void cn_bn_partial_kernel(const float* __restr
       const float4* xp = reinterpret_cast<const float4*>(x + b * xbs + (long)c * L);
       for (int l = beg + threadIdx.x; l < end; l += 256) {
         const float4 v = xp[l];
-        s += (double)((v.x + v.y) + (v.z + v.w));
+        s += ((double)v.x + (double)v.y) + ((double)v.z + (double)v.w);  // fp64: a channel far from zero
         ss += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
       }
     }
@@ -469,7 +469,7 @@ __global__ __launch_bounds__(256) void cn_bn_group_partial_kernel(const CnBnGrou
       const float4* xp = reinterpret_cast<const float4*>(a.x[g] + b * a.xbs + (long)c * a.L);
       for (int l = beg + threadIdx.x; l < end; l += 256) {
         const float4 v = xp[l];
-        s += (double)((v.x + v.y) + (v.z + v.w));
+        s += ((double)v.x + (double)v.y) + ((double)v.z + (double)v.w);  // fp64: a channel far from zero
         ss += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
       }
     }

@@ -1756,6 +1756,13 @@ def bn_act(x: Var, bn, act: int, residual: T.Optional[Var] = None, channels: T.O
     return yv
 
 
+def _bn_group_uniform(bns: T.Sequence) -> bool:
+    """Can one grouped launch serve these layers? It takes a single eps and momentum, and running statistics for
+    every layer or for none."""
+    return 1 <= len(bns) <= 4 and all(bn.momentum == bns[0].momentum and bn.eps == bns[0].eps for bn in bns) \
+        and all((bn.running_mean is None) == (bns[0].running_mean is None) for bn in bns)
+
+
 def bn_act_group(xs: T.Sequence[Var], bns: T.Sequence, act: int, residual: T.Optional[Var] = None,
                  sum_outputs: bool = False, training: bool = True,
                  outs: T.Optional[T.Sequence[torch.Tensor]] = None) -> T.Union[Var, T.List[Var]]:
@@ -1771,13 +1778,26 @@ def bn_act_group(xs: T.Sequence[Var], bns: T.Sequence, act: int, residual: T.Opt
         raise ValueError("bn_act_group: a residual needs sum_outputs=True")
     if is16(xts[0]):  # mixed precision: the G branches in one launch per pass (cn_bn_act_group_*_bf16)
         return _bn_act_group_bf16(xs, bns, act, residual, sum_outputs, training, outs)
+    if not _bn_group_uniform(bns):
+        # the grouped kernels take ONE eps / momentum and running statistics for all layers or none: layers that
+        # differ run one bn_act each; the summed form chains the residual in the order of the fused sum
+        if outs is not None and len(outs) != (1 if sum_outputs else G):
+            raise ValueError("bn_act_group: outs must hold one tensor per output")
+        if not sum_outputs:
+            return [bn_act(x, bn, act, training=training, out=outs[i] if outs is not None else None)
+                    for i, (x, bn) in enumerate(zip(xs, bns))]
+        acc = residual
+        for i, (x, bn) in enumerate(zip(xs, bns)):
+            last = i == G - 1
+            acc = bn_act(x, bn, act, residual=acc, training=training, out=outs[0] if outs is not None and last else None)
+        return acc
     B, C = xts[0].shape[0], xts[0].shape[1]
     L = int(xts[0][0].numel()) // C
     for t in xts:
         if tuple(t.shape) != tuple(xts[0].shape) or bstride(t) != bstride(xts[0]):
             raise ValueError("bn_act_group: inputs must have the same shape and strides")
     dev = xts[0].device
-    use_batch = training or any(bn.running_mean is None for bn in bns)
+    use_batch = training or bns[0].running_mean is None
     _note_bn_update(training)
     tab = lambda ptrs: (ctypes.c_void_p * G)(*ptrs)
     if outs is not None:  # caller-provided outputs (e.g. channel slices of one buffer, all with the same strides)
@@ -1791,7 +1811,7 @@ def bn_act_group(xs: T.Sequence[Var], bns: T.Sequence, act: int, residual: T.Opt
     ws = _alloc(G * _lib.query("cn_bn_workspace_doubles", C), torch.float64, dev)
     rt = residual.t if residual is not None else None
     mom = _bn_momentum(bns[0])
-    has_running = all(bn.running_mean is not None for bn in bns)
+    has_running = bns[0].running_mean is not None
     _lib.call("cn_bn_act_group_fwd_f32", G, tab([t.data_ptr() for t in xts]), bstride(xts[0]),
               tab([bn.weight.data_ptr() for bn in bns]), tab([bn.bias.data_ptr() for bn in bns]),
               tab([bn.running_mean.data_ptr() for bn in bns]) if has_running else None,
@@ -1844,10 +1864,17 @@ def _out_ok(out: T.Optional[torch.Tensor], like: torch.Tensor) -> bool:
             and out.device == like.device and (not is16(like) or (_dense16(out) and out.stride(1) == 1)))
 
 
+LN_BWD_MAX_C = 512  # widest LayerNorm the backward kernels take (cn_ln_bwd_kernel<512> keeps C partial sums in LDS)
+
+
 def layer_norm_c(x: Var, ln, residual: T.Optional[Var] = None, out: T.Optional[torch.Tensor] = None) -> Var:
     """nn.LayerNorm over the channel axis of an NCHW buffer (+ residual)."""
     tape = current_tape()
     xt = _check(x.t)
+    if tape.enabled and xt.shape[1] > LN_BWD_MAX_C:
+        # refused before the forward launch, not at the backward (the bf16 path falls back to this one for wide layers)
+        raise NotImplementedError(f"LayerNorm backward over {xt.shape[1]} channels: cn_layernorm_c_bwd_f32 takes at "
+                                  f"most {LN_BWD_MAX_C} (the forward alone, without a tape, runs at any width)")
     if is16(xt):
         return _layer_norm_c_bf16(x, ln, residual, out)
     B, C = xt.shape[0], xt.shape[1]
@@ -3005,6 +3032,8 @@ def _bn_act_group_bf16(xs: T.Sequence[Var], bns: T.Sequence, act: int, residual:
     use_batch = training or (bns[0].running_mean is None)
     has_sums = all(x.stats is not None for x in xs) and len({x.stats.shape[0] for x in xs}) == 1
     if not _GROUP_BF16 or not ok:
+        if outs is not None and len(outs) != (1 if sum_outputs else G):
+            raise ValueError("bn_act_group: outs must hold one tensor per output")
         if not sum_outputs:
             return [_bn_act_bf16(x, bn, act, None, training, outs[i] if outs is not None else None)
                     for i, (x, bn) in enumerate(zip(xs, bns))]

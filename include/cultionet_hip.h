@@ -440,6 +440,8 @@ int cn_bn_act_bwd_bf16(const void* x, long ldx, const void* dy, long lddy, const
  * Backward: dys[g] = gradient of output g (after a summed forward the same pointer G times: read once per pass);
  * dxs[g] nullable; accumulate_dx: HOST array of G flags; dgammas / dbetas ACCUMULATED. */
 long cn_bn_group_workspace_floats_bf16(int G, int C);
+/* Ints at the head of that workspace that hold its ticket counters (zero between calls). */
+int cn_bn_workspace_head_ints(void);
 int cn_bn_act_group_fwd_bf16(int G, const void* const* xs, long ldx, const float* const* gammas,
                              const float* const* betas, float* const* running_means, float* const* running_vars,
                              const void* res /*nullable*/, long ldr, void* const* ys, long ldy, float* const* means,
