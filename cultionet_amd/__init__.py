@@ -6,7 +6,7 @@ def configure_runtime(hw_queues: int = 5) -> bool:
     """Cap the HIP runtime's hardware-queue pool at ``hw_queues`` per stream priority (``GPU_MAX_HW_QUEUES``) -- OPT-IN,
     never done at import (a drop-in library does not edit its host's environment behind its back).
 
-    Why 5 (round 6, tools/one_aux_try.sh, profiles/r06_hw_queues.txt): this chip runs a process's hardware queues
+    Why 5 (round 6, profiles/r06_hw_queues.txt): this chip runs a process's hardware queues
     concurrently only while there are at most seven; the engine owns one lowest-priority queue (weight gradients) and one
     highest-priority queue (the auxiliary branch stream), which leaves five for everything of normal priority -- the
     compute stream, the bucket stream and the six streams a torch.distributed / RCCL process group brings. With the

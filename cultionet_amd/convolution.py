@@ -12,7 +12,6 @@ reference); every forward runs engine ops on ``Var`` buffers:
 """
 from __future__ import annotations
 
-import os
 import typing as T
 
 import torch
@@ -45,13 +44,7 @@ class ConvTranspose2d(nn.Module):
         self.up_conv = nn.ConvTranspose2d(in_channels, out_channels, kernel_size, stride=stride, padding=padding)
 
     def forward(self, x: E.Var, size, out: T.Optional[torch.Tensor] = None) -> E.Var:
-        y = E.conv_transpose2d(x, self.up_conv, self.stride, self.padding, size=tuple(size), out=out)
-        if y.valid is None and tuple(y.shape[-2:]) == tuple(size) and (out is None or y.t.data_ptr() == out.data_ptr()):
-            return y  # already at ``size`` (the stride >= kernel path resizes in its own pointwise pass), or no resize needed
-        natural = y.valid if y.valid is not None else tuple(y.shape[-2:])
-        if out is not None and tuple(natural) == tuple(size):
-            out = None  # no resize to write through: the caller copies
-        return E.resize_bilinear(y, tuple(size), out=out)
+        return E.conv_transpose2d(x, self.up_conv, self.stride, self.padding, size=tuple(size), out=out)
 
 
 class ConvBlock2d(nn.Module):
@@ -221,9 +214,6 @@ class ResidualConv(nn.Module):
         return self.seq(x, residual=out)
 
 
-_ATT_STREAM = os.environ.get("CN_ATT_STREAM", "1") != "0"  # A/B switch: the attention chain beside the conv branches
-
-
 class ResidualAConv(nn.Module):
     """convolution.py:250-395: out = skip(x) + sum_d ResConvBlock2d_d(x) [+ LN(NA(LN(skip(x))))]."""
 
@@ -268,7 +258,7 @@ class ResidualAConv(nn.Module):
         sum_out = out if self.attention_weights is None else None  # (with attention the branch sum is an intermediate)
         natten = self.attention_weights == AttentionTypes.NATTEN
         att_br = att = None
-        if natten and _ATT_STREAM and not isinstance(self.skip, nn.Conv2d) and E.is16(x.t):
+        if natten and not isinstance(self.skip, nn.Conv2d) and E.is16(x.t):
             # LayerNorm -> neighbourhood attention (qkv, windows, projection) reads nothing but x: on an auxiliary stream
             # beside the MFMA-bound convolution branches (engine.spawn); joined before the closing LayerNorm + add.
             # Mixed precision only: there the chain is bandwidth-bound (same box: bf16 step +1.0 %, reference-default

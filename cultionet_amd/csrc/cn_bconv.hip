@@ -905,7 +905,7 @@ static int cnb_launch(CnBGeom& g, int G, hipStream_t stream, double flops, CnBFi
   int WN = g.NT >= 4 ? 4 : (g.NT >= 2 ? 2 : 1);
   int MPWv = 4;
   cnb_pick_tile(Hg, Wg, g.is, span, 128 * (4 / WN), g.TH, g.TW);
-  if (WN == 4 && getenv("CN_BCONV_NO_HALF") == nullptr) {
+  if (WN == 4) {
     // small planes (25x25 at batch 32: 160 tiles x 1 cout block on 256 CUs): two 64-cout blocks per pixel tile instead
     long blocks = 0;
     for (int c = 0; c < g.ncls; ++c)
@@ -985,11 +985,10 @@ static int cnb_launch(CnBGeom& g, int G, hipStream_t stream, double flops, CnBFi
   g.fin_cnt = nullptr;
   if (fin != nullptr) {
     fin->done = 0;
-    static const bool on = getenv("CN_CONV_BNFIN") == nullptr || atoi(getenv("CN_CONV_BNFIN")) != 0;  // A/B switch
     const long tiles = (long)g.cls[0].tiles_per_img * g.B;
     const long domains = (long)G * g.nblk_n;
     const long grow_doubles = domains * (CN_T2_COUNTERS - 1) * 64 * WN;
-    if (on && g.stats[0] != nullptr && tiles <= CN_BNWS_CONV_MAX_TILES && domains <= CN_BNWS_CONV_DOMAINS &&
+    if (g.stats[0] != nullptr && tiles <= CN_BNWS_CONV_MAX_TILES && domains <= CN_BNWS_CONV_DOMAINS &&
         fin->ws != nullptr && (reinterpret_cast<uintptr_t>(fin->ws) & 7) == 0 &&
         fin->ws_floats >= CN_BNWS_HEAD_INTS + 2 * grow_doubles) {
       g.fin_cnt = reinterpret_cast<int*>(fin->ws) + CN_BNWS_CONV_OFF;

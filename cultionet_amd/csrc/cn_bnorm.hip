@@ -495,23 +495,24 @@ __global__ __launch_bounds__(256) void cn_bbn_group_eval_stats_kernel(const CnBB
 
 struct CnBBnTickets { CnTicket2 t[BBG_MAX]; };
 
-// Per-channel sums over pixels AND their finalize in one launch: GS groups handled by ONE thread (GS = 2: the summed
-// level, dy shared), or group blockIdx.y (GS = 1). Every block stores its row {k}[C] of group g write-through; the
-// two-level last-block reduction (cn_t2_reduce, one ticket domain per group) hands the column totals to the last
-// arriver, which finishes the channels: MODE 0 mean / rstd / running statistics, MODE 1 backward coefficients and
-// dgamma / dbeta. No stand-alone finalize launch.
-template <int MODE, int GS>
+// Per-channel sums over pixels AND their finalize in one launch, group g0 = blockIdx.y. Every block stores its row
+// {k}[C] of group g0 write-through; the two-level last-block reduction (cn_t2_reduce, one ticket domain per group) hands
+// the column totals to the last arriver, which finishes the channels: MODE 0 mean / rstd / running statistics, MODE 1
+// backward coefficients and dgamma / dbeta. No stand-alone finalize launch. (The [GS] register arrays with GS = 1 are
+// the shape of the removed two-branch form; flattening them changes the code the compiler generates.)
+template <int MODE>
 __global__ __launch_bounds__(256) void cn_bbn_group_partial_kernel(const CnBBnGroupArgs a, const CnBBnTickets tks) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* red = reinterpret_cast<float*>(smem);                    // 256 * 16 floats
   double* tot = reinterpret_cast<double*>(smem + 256 * 16 * 4);    // 2C doubles
   __shared__ int s_flag;
+  constexpr int GS = 1;
   const int C = a.C, C8 = C >> 3;
   const int R = 256 / C8;
   const int tid = threadIdx.x;
   const int row = tid / C8, cg = tid - row * C8;
   const bool live = row < R;
-  const int g0 = GS == 1 ? blockIdx.y : 0;
+  const int g0 = blockIdx.y;
   float a1[GS][8], a2[GS][8], m[GS][8], rs[GS][8], ga[GS][8], be[GS][8];
 #pragma unroll
   for (int q = 0; q < GS; ++q)
@@ -527,7 +528,6 @@ __global__ __launch_bounds__(256) void cn_bbn_group_partial_kernel(const CnBBnGr
   const long p0 = blockIdx.x * a.rows_per_block;
   const long p1 = p0 + a.rows_per_block < a.P ? p0 + a.rows_per_block : a.P;
   if (live) {
-    const bool shared_dy = GS > 1;  // the summed level: one dy for every branch
     auto accum = [&](int q, const u32x4& xq, const u32x4& dq) {
       float xv[8];
       cn_unpack8(xq, xv);
@@ -549,7 +549,7 @@ __global__ __launch_bounds__(256) void cn_bbn_group_partial_kernel(const CnBBnGr
     };
     const u32x4 z4 = {0u, 0u, 0u, 0u};
     long p = p0 + row;
-    if (GS == 1) {
+    {
       // two pixels per iteration: both 16-byte loads (four in MODE 1) are in flight before either is consumed
       const bf16_t* __restrict__ xp = a.x[g0];
       const bf16_t* __restrict__ dp = a.dy[g0];
@@ -572,12 +572,7 @@ __global__ __launch_bounds__(256) void cn_bbn_group_partial_kernel(const CnBBnGr
         xr[q] = *reinterpret_cast<const u32x4*>(a.x[g0 + q] + p * a.ldx + cg * 8);
         dr[q] = z4;
       }
-      if (MODE == 1) {
-        dr[0] = *reinterpret_cast<const u32x4*>(a.dy[g0] + p * a.lddy + cg * 8);
-#pragma unroll
-        for (int q = 1; q < GS; ++q)
-          dr[q] = shared_dy ? dr[0] : *reinterpret_cast<const u32x4*>(a.dy[g0 + q] + p * a.lddy + cg * 8);
-      }
+      if (MODE == 1) dr[0] = *reinterpret_cast<const u32x4*>(a.dy[g0] + p * a.lddy + cg * 8);
 #pragma unroll
       for (int q = 0; q < GS; ++q) accum(q, xr[q], dr[q]);
     }
@@ -668,16 +663,16 @@ __global__ __launch_bounds__(256) void cn_bbn_group_apply_fwd_kernel(const CnBBn
   }
 }
 
-// Backward apply: dx_g (+)= gamma*rstd*(dz - coef0 - xhat*coef1). GS = 2: both branches of a summed level in the
-// thread (dy read once); GS = 1: group blockIdx.y.
-template <int GS>
+// Backward apply: dx_g (+)= gamma*rstd*(dz - coef0 - xhat*coef1), group g0 = blockIdx.y (the [GS] arrays: as in
+// cn_bbn_group_partial_kernel).
 __global__ __launch_bounds__(256) void cn_bbn_group_apply_bwd_kernel(const CnBBnGroupArgs a) {
+  constexpr int GS = 1;
   const int C = a.C, C8 = C >> 3;
   const int R = 256 / C8;
   const int tid = threadIdx.x;
   const int row = tid / C8, cg = tid - row * C8;
   if (row >= R) return;
-  const int g0 = GS == 1 ? blockIdx.y : 0;
+  const int g0 = blockIdx.y;
   float sc[GS][8], sh[GS][8], m[GS][8], rs[GS][8], c0[GS][8], c1[GS][8];
 #pragma unroll
   for (int q = 0; q < GS; ++q)
@@ -697,8 +692,7 @@ __global__ __launch_bounds__(256) void cn_bbn_group_apply_bwd_kernel(const CnBBn
 #pragma unroll
     for (int q = 0; q < GS; ++q) {
       xr[q] = *reinterpret_cast<const u32x4*>(a.x[g0 + q] + p * a.ldx + cg * 8);
-      if (q == 0 || GS == 1) dr[q] = *reinterpret_cast<const u32x4*>(a.dy[g0 + q] + p * a.lddy + cg * 8);
-      else dr[q] = dr[0];
+      dr[q] = *reinterpret_cast<const u32x4*>(a.dy[g0 + q] + p * a.lddy + cg * 8);
       if (a.dx[g0 + q] != nullptr && a.accumulate_dx[g0 + q])
         orr[q] = *reinterpret_cast<const u32x4*>(a.dx[g0 + q] + p * a.lddx + cg * 8);
     }
@@ -811,7 +805,7 @@ extern "C" int cn_bn_act_group_fwd_bf16(int G, const void* const* xs, long ldx, 
       long rows;
       bbn_grid(P, C, nblk, rows);
       a.rows_per_block = rows;
-      CN_LAUNCH((cn_bbn_group_partial_kernel<0, 1>), dim3(nblk, G), dim3(256), bbg_partial_shmem(C), stream, a,
+      CN_LAUNCH((cn_bbn_group_partial_kernel<0>), dim3(nblk, G), dim3(256), bbg_partial_shmem(C), stream, a,
                 bbg_tickets(ws, G, C, nblk));
     }
   } else {
@@ -834,8 +828,8 @@ extern "C" int cn_bn_act_group_fwd_bf16(int G, const void* const* xs, long ldx, 
   return cn_check_launch();
 }
 
-// dys[g]: gradient of output g (shared_dy != 0: the summed level, every dys[g] is the same tensor and is read once).
-// dxs[g] nullable; dgamma / dbeta ACCUMULATED.
+// dys[g]: gradient of output g (the summed level passes the same tensor for every g); dxs[g] nullable; dgamma / dbeta
+// ACCUMULATED.
 extern "C" int cn_bn_act_group_bwd_bf16(int G, const void* const* xs, long ldx, const void* const* dys, long lddy,
                                         const float* const* means, const float* const* rstds,
                                         const float* const* gammas, const float* const* betas, void* const* dxs,
@@ -849,17 +843,14 @@ extern "C" int cn_bn_act_group_bwd_bf16(int G, const void* const* xs, long ldx, 
   bbg_common(a, G, xs, ldx, gammas, betas, const_cast<float* const*>(means), const_cast<float* const*>(rstds), ws, P, C,
              act, training);
   a.lddy = lddy; a.lddx = lddx;
-  // dy shared by the two branches of a summed level: the in-thread form (one read of dy for both branches) measured
-  // SLOWER than one grid row per branch (partial 49 vs 31 us, apply 42 vs 24 us at 32 x 100^2 x 128: 143-149 VGPRs, three
+  // one grid row per group even where the groups share dy: an in-thread form reading dy once for both branches of a
+  // summed level measured SLOWER (partial 49 vs 31 us, apply 42 vs 24 us at 32 x 100^2 x 128: 143-149 VGPRs, three
   // waves per SIMD with one pixel in flight each -- latency-bound, and the second read of dy comes out of the Infinity
-  // Cache anyway). Kept behind CN_BBN_SHARED_DY=1 for experiments.
-  static const bool allow_shared = getenv("CN_BBN_SHARED_DY") != nullptr;
-  bool shared = G == 2 && allow_shared;
+  // Cache anyway) and was removed
   bool any_dx = false;
   for (int g = 0; g < G; ++g) {
     a.dy[g] = (const bf16_t*)dys[g]; a.dx[g] = (bf16_t*)dxs[g]; a.accumulate_dx[g] = accumulate_dx[g];
     a.dgamma[g] = dgammas[g]; a.dbeta[g] = dbetas[g];
-    if (dys[g] != dys[0]) shared = false;
     any_dx = any_dx || dxs[g] != nullptr;
   }
   int nblk;
@@ -868,15 +859,13 @@ extern "C" int cn_bn_act_group_bwd_bf16(int G, const void* const* xs, long ldx, 
   a.rows_per_block = rows;
   // statistics pass + its finalize (coefficients, dgamma / dbeta) in ONE launch: the last-arriving block finishes
   const CnBBnTickets tks = bbg_tickets(ws, G, C, nblk);
-  if (shared) CN_LAUNCH((cn_bbn_group_partial_kernel<1, 2>), dim3(nblk), dim3(256), bbg_partial_shmem(C), stream, a, tks);
-  else CN_LAUNCH((cn_bbn_group_partial_kernel<1, 1>), dim3(nblk, G), dim3(256), bbg_partial_shmem(C), stream, a, tks);
+  CN_LAUNCH((cn_bbn_group_partial_kernel<1>), dim3(nblk, G), dim3(256), bbg_partial_shmem(C), stream, a, tks);
   if (any_dx) {
     int ablk;
     long arows;
     bbn_apply_grid(P, C, ablk, arows);
     a.rows_per_block = arows;
-    if (shared) CN_LAUNCH((cn_bbn_group_apply_bwd_kernel<2>), dim3(ablk), dim3(256), 0, stream, a);
-    else CN_LAUNCH((cn_bbn_group_apply_bwd_kernel<1>), dim3(ablk, G), dim3(256), 0, stream, a);
+    CN_LAUNCH(cn_bbn_group_apply_bwd_kernel, dim3(ablk, G), dim3(256), 0, stream, a);
   }
   return cn_check_launch();
 }

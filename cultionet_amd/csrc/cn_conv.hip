@@ -1189,12 +1189,11 @@ int cn_conv_igemm_launch(CnConvGeom& g, hipStream_t stream) {
   if (g.G > 1 && g.shared_y && !allow_split) return CN_ERR_ARG;
   // 16-byte staging needs every image 16-byte aligned and either aligned planes (H*W % 4 == 0) or the odd-plane variant
   // (H*W % 4 == 1: every odd square -- 25x25, 13x13, 99x99, 49x49, 97x97)
-  static const bool odd_vec = getenv("CN_ODD_VEC") == nullptr || atoi(getenv("CN_ODD_VEC")) != 0;  // A/B switch
   const int hw4 = (int)(((long)g.Hin * g.Win) % 4);
   // (measured per layer at batch 8, same box: 25x25 and 49x49 planes 3-9 % faster than the dword kernel, the stride-4
   // scatter 25x25 -> 97x97 1.5x; strided gathers from 99x99 -- two float4 pieces per thread and channel -- 20 % slower:
   // those stay on the dword kernel)
-  g.odd_planes = (hw4 == 1 && odd_vec && !(g.is > 1 && (long)g.Hin * g.Win > 4096)) ? 1 : 0;
+  g.odd_planes = (hw4 == 1 && !(g.is > 1 && (long)g.Hin * g.Win > 4096)) ? 1 : 0;
   bool vec = (hw4 == 0 || g.odd_planes) && (g.xbs % 4 == 0);
   // ... and the same holds for ALIGNED large planes (round 6: with ConvTranspose2d on the 100 x 100 output_padding grid its
   // backward-data gather became eligible for the 16-byte kernel: 83.7 vs 78.3 us alone, and 336 vs 177 us inside the step

@@ -126,7 +126,7 @@ def _dense_inner(t: torch.Tensor) -> bool:
 class Var:
     """A device buffer and (during training) its gradient buffer."""
 
-    __slots__ = ("t", "grad", "req", "parent", "stats", "bnfin", "valid")
+    __slots__ = ("t", "grad", "req", "parent", "stats", "bnfin")
 
     def __init__(self, t: torch.Tensor, req: bool = False):
         self.t = t
@@ -135,7 +135,6 @@ class Var:
         self.parent: T.Optional[T.Tuple["Var", int, int]] = None  # channel slice [c0, c1) of another Var
         self.stats: T.Optional[torch.Tensor] = None  # bf16 conv outputs: per-channel {sum, sumsq} from the epilogue
         self.bnfin = None  # (bn module, mean, rstd): BatchNorm statistics already finished by the producing conv launch
-        self.valid: T.Optional[T.Tuple[int, int]] = None  # (H, W) of the image inside a larger stored grid (conv_transpose2d)
 
     @property
     def shape(self):
@@ -186,8 +185,6 @@ class Tape:
 # 13x13: a fraction of the 256 CUs each) run beside the dx chain instead of in front of it. The main stream joins
 # the side stream once, before the gradient exchange / optimizer. CN_OVERLAP_WGRAD=0 keeps everything on one stream.
 _OVERLAP_WGRAD = os.environ.get("CN_OVERLAP_WGRAD", "1") == "1"
-# diagnostic: weight gradients of more than this many multiply-accumulates stay on the compute stream (0 = no limit)
-_SIDE_MAX_WORK = float(os.environ.get("CN_SIDE_MAX_WORK", "0"))
 _side_streams: T.Dict[T.Any, T.Dict[str, T.Any]] = {}
 
 
@@ -205,27 +202,15 @@ def _make_side_stream(dev) -> "torch.cuda.Stream":
     """The weight-gradient stream. Its kernels (one wave per SIMD, hundreds of microseconds each) must not take CUs
     from the data-gradient chain on the compute stream, which is the critical path: it is created with the LOWEST
     priority the device offers through the C ABI (torch.cuda.Stream can only ask for normal or higher) and wrapped as
-    a torch ExternalStream for events / record_stream. CN_SIDE_STREAM = "low" (default) | "normal" |
-    "mask:<n>" (hipExtStreamCreateWithCUMask over the first n CUs of every XCD-interleaved group)."""
+    a torch ExternalStream for events / record_stream. (A normal-priority stream and a CU-masked one were measured
+    against it and removed: DESIGN.md section 2.)"""
     import ctypes
 
-    mode = os.environ.get("CN_SIDE_STREAM", "low")
-    if mode == "normal":
-        return torch.cuda.Stream(device=dev)
     handle = ctypes.c_void_p()
+    rng = (ctypes.c_int * 2)()
     with torch.cuda.device(dev):
-        if mode.startswith("mask:"):
-            n = int(mode.split(":")[1])
-            ncu = torch.cuda.get_device_properties(dev).multi_processor_count
-            words = (ncu + 31) // 32
-            mask = (ctypes.c_uint * words)()
-            for i in range(min(n, ncu)):
-                mask[i // 32] |= 1 << (i % 32)
-            _lib.call("cn_stream_create", 0, mask, words, ctypes.byref(handle))
-        else:
-            rng = (ctypes.c_int * 2)()
-            _lib.call("cn_stream_priority_range", rng)
-            _lib.call("cn_stream_create", int(rng[0]), None, 0, ctypes.byref(handle))
+        _lib.call("cn_stream_priority_range", rng)
+        _lib.call("cn_stream_create", int(rng[0]), None, 0, ctypes.byref(handle))
     return torch.cuda.ExternalStream(handle.value, device=dev)
 
 
@@ -242,13 +227,12 @@ class side_stream:
     the current stream. ``tensors`` are the buffers those launches read (kept from being recycled by the caching
     allocator until the side stream has passed them)."""
 
-    def __init__(self, *tensors: torch.Tensor, work: float = 0.0):
+    def __init__(self, *tensors: torch.Tensor):
         self.tensors = tensors
         self.ctx = None
-        self.work = work  # multiply-accumulates of the enclosed launches (0: unknown / small)
 
     def __enter__(self):
-        if not _OVERLAP_WGRAD or (_SIDE_MAX_WORK > 0 and self.work > _SIDE_MAX_WORK):
+        if not _OVERLAP_WGRAD:
             return self
         main = _main_stream()
         st = _side_state(main.device)
@@ -300,13 +284,12 @@ def join_side_stream() -> None:
 # forward reaches the heads, and in backward nothing needs their result until tower_b / tower_c run. spawn() puts such
 # a chain on an auxiliary stream the moment its input exists, so that it executes BESIDE the MFMA-bound tower
 # convolutions of the compute stream (the regime in which overlap pays on this chip: a bandwidth- / latency-bound kernel
-# next to a matrix-pipe-bound one); its tape nodes run on the same stream in backward. CN_HEAD_STREAMS=0: off.
-_HEAD_STREAMS = os.environ.get("CN_HEAD_STREAMS", "1") != "0"
+# next to a matrix-pipe-bound one); its tape nodes run on the same stream in backward. ``branch_streams(False)``: off.
 _aux_streams: T.Dict[T.Any, T.List["torch.cuda.Stream"]] = {}
 
 
-# Hardware queues of one process (round 6, tools/one_aux_try.sh + profiles/r06_hw_queues.txt). The HIP runtime keeps a
-# pool of up to GPU_MAX_HW_QUEUES hardware queues PER STREAM PRIORITY, and this chip runs a process's queues concurrently
+# Hardware queues of one process (round 6, profiles/r06_hw_queues.txt). The HIP runtime keeps a pool of up to
+# GPU_MAX_HW_QUEUES hardware queues PER STREAM PRIORITY, and this chip runs a process's queues concurrently
 # only while there are at most SEVEN of them: with an eighth the queues are time-sliced and the whole step runs 1.5-1.9x
 # slower (that is the "auxiliary streams + bucket collectives" slowdown of rounds 4-5: a torch.distributed process group
 # brings six normal-priority streams with it -- 6 + the weight-gradient stream's lowest-priority queue + two
@@ -328,21 +311,15 @@ def branch_streams_allowed() -> bool:
     budget: with a torch.distributed process group alive (six normal-priority streams of its own) the auxiliary stream
     needs GPU_MAX_HW_QUEUES <= 5 (cap + weight-gradient queue + auxiliary queue <= 7). Checked LIVE at every spawn()
     (ADVICE r4), so it follows the group's lifetime and covers the drop-in mode under Lightning's own DDP;
-    CN_KEEP_BRANCH_STREAMS=1 overrides it (to profile the interaction); ``engine.branch_streams(False)`` switches
-    spawn() off for a scope. One-rank RCCL group, same box: bf16 2249 chips/s with the auxiliary stream at 5 queues
-    against 2162 without it at 8 (single process 2279-2285); at 6 queues 1396."""
-    if not _HEAD_STREAMS or getattr(_state, "no_branches", False):
+    ``engine.branch_streams(False)`` switches spawn() off for a scope. One-rank RCCL group, same box: bf16 2249 chips/s
+    with the auxiliary stream at 5 queues against 2162 without it at 8 (single process 2279-2285); at 6 queues 1396."""
+    if getattr(_state, "no_branches", False):
         return False
-    if _KEEP_BRANCHES:
-        return True
     import torch.distributed as dist
 
     if dist.is_available() and dist.is_initialized():
         return _hw_queue_cap() + 2 <= _HW_QUEUE_BUDGET
     return True
-
-
-_KEEP_BRANCHES = os.environ.get("CN_KEEP_BRANCH_STREAMS") == "1"
 
 
 class branch_streams:
@@ -1130,7 +1107,7 @@ class deferring_slice_sums:
         self.on = False
 
     def __enter__(self):
-        if (not _DEFER_SUMS or _SIDE_MAX_WORK > 0 or _ss_state() is not None or not self.store.flat_grad.is_cuda):
+        if not _DEFER_SUMS or _ss_state() is not None or not self.store.flat_grad.is_cuda:
             return self
         # One state PER STORE (tables, arena): a launch plan recorded for one trainer bakes these addresses in, and a
         # second trainer of the process (tests run an eager and a replayed one side by side) must not rewrite them.
@@ -1246,7 +1223,7 @@ def conv2d(x: Var, mod, stride: int = 1, padding: int = 0, dilation: int = 1, ou
             dy = yv.grad
             if dy is None:
                 return
-            with side_stream(xt, dy, work=float(B) * Ho * Wo * Cin * Cout * KH * KW):
+            with side_stream(xt, dy):
                 s = _stream()
                 wsp, wsn = _pad_ws(xt, dy)
                 _lib.call("cn_conv2d_bwd_weight_f32", xt.data_ptr(), bstride(xt), dy.data_ptr(), bstride(dy),
@@ -1306,8 +1283,7 @@ def conv2d_group(xs: T.Sequence[Var], mods: T.Sequence, paddings: T.Sequence[int
             live = [i for i in range(G) if yvs[i].grad is not None]
             grouped_w = (len(live) == G and len(set(paddings)) == 1 and len(set(dilations)) == 1
                          and len({bstride(yvs[i].grad) for i in live}) == 1)
-            with side_stream(*(list(xts) + [yvs[i].grad for i in live]),
-                             work=float(G) * B * Ho * Wo * Cin * Cout * KH * KW):
+            with side_stream(*(list(xts) + [yvs[i].grad for i in live])):
                 s = _stream()
                 if grouped_w:  # one launch for the G weight gradients
                     wsp, wsn = _pad_ws(*([xts[i] for i in range(G)] + [yvs[i].grad for i in range(G)]))
@@ -1367,11 +1343,6 @@ def conv2d_group(xs: T.Sequence[Var], mods: T.Sequence, paddings: T.Sequence[int
     return yvs
 
 
-# CN_CONVT_TAPS=0: a ConvTranspose2d with stride >= kernel size (final_c's 3 x 3, stride 4) runs through the parity-class
-# launches like every other one instead of the dense 1x1 contraction + pointwise scatter / gather (A/B switch).
-_CONVT_TAPS = os.environ.get("CN_CONVT_TAPS", "1") != "0"
-
-
 def _conv_transpose2d_taps(x: Var, mod, stride: int, padding: int, size, out: T.Optional[torch.Tensor]) -> Var:
     """nn.ConvTranspose2d(k, stride s >= k, padding) FOLLOWED BY check_upsample to ``size`` (None: no resize), fp32: no
     two taps of an input pixel meet, so the contraction is a dense 1x1 GEMM on the small grid into
@@ -1426,40 +1397,50 @@ def _conv_transpose2d_taps(x: Var, mod, stride: int, padding: int, size, out: T.
     return zv
 
 
-# CN_CONVT_OUTPAD=0: ConvTranspose2d writes the reference's (2n-1)^2 tensor (rounds 1-5) instead of the 2n x 2n
-# output_padding grid of the resize that follows (A/B switch).
-_CONVT_OUTPAD = os.environ.get("CN_CONVT_OUTPAD", "1") != "0"
-
-
 def conv_transpose2d(x: Var, mod, stride: int, padding: int, size: T.Optional[T.Tuple[int, int]] = None,
                      out: T.Optional[torch.Tensor] = None) -> Var:
-    """nn.ConvTranspose2d forward (k x k, stride s, padding p, with bias).
+    """nn.ConvTranspose2d forward (k x k, stride s, padding p, with bias), then check_upsample (convolution.py:45-68):
+    with ``size`` given the result is the tensor at ``size``, bilinearly resized (into ``out`` when given) unless the
+    natural output already has that size -- then it is returned as computed, and a caller that passed ``out`` copies.
 
-    ``size``: the size check_upsample will resize the result to (convolution.py:45-68). When it exceeds the natural
-    (2n-1)-style output by less than the stride on both axes (every site of TowerUNet), the fp32 result is computed on
-    THAT grid -- the transposed convolution with output_padding = size - natural, whose top-left natural-size block is
-    exactly the reference's tensor -- and returned as a Var whose ``valid`` attribute names the image inside it:
+    When ``size`` exceeds the natural (2n-1)-style output by less than the stride on both axes (every site of
+    TowerUNet), the fp32 transposed convolution is computed on THAT grid -- output_padding = size - natural, whose
+    top-left natural-size block is exactly the reference's tensor -- and the resize reads the image inside it in place:
     planes of 100 x 100 / 50 x 50 are 16-byte aligned where 99 x 99 / 49 x 49 / 97 x 97 are not, so the weight gradient
-    needs no aligned copy of dy (cn_pad_planes), the data gradient stages 16 bytes per lane instead of 4, and
-    resize_bilinear reads / writes the stored grid in place."""
-    tape = current_tape()
+    needs no aligned copy of dy (cn_pad_planes) and the data gradient stages 16 bytes per lane instead of 4. A stride
+    >= kernel size (final_c's 3 x 3, stride 4) takes _conv_transpose2d_taps, which resizes in its own pointwise pass."""
     xt = _check(x.t)
-    if is16(xt):
-        return _conv_transpose2d_bf16(x, mod, stride, padding)
     B, Cin, H, W = xt.shape
     w = mod.weight
     Cout, KH, KW = w.shape[1], w.shape[2], w.shape[3]
     Ho = (H - 1) * stride - 2 * padding + KH
     Wo = (W - 1) * stride - 2 * padding + KW
-    if _CONVT_TAPS and KH == KW and stride >= KH and 0 <= padding < stride and \
+    if is16(xt):
+        y = _conv_transpose2d_bf16(x, mod, stride, padding)
+    elif KH == KW and stride >= KH and 0 <= padding < stride and \
             (size is None or (2 * Ho > int(size[0]) and 2 * Wo > int(size[1]))):
         return _conv_transpose2d_taps(x, mod, stride, padding, size, out)
-    op = 0
-    if _CONVT_OUTPAD and size is not None and stride > 1:
-        dh, dw_ = int(size[0]) - Ho, int(size[1]) - Wo
-        if dh == dw_ and 0 < dh < stride:
-            op = dh
-    Hs, Ws = Ho + op, Wo + op  # the stored grid
+    else:
+        op = 0
+        if size is not None and stride > 1:
+            dh, dw_ = int(size[0]) - Ho, int(size[1]) - Wo
+            if dh == dw_ and 0 < dh < stride:
+                op = dh
+        y = _conv_transpose2d_f32(x, mod, stride, padding, op)
+    if size is None or (Ho, Wo) == (int(size[0]), int(size[1])):
+        return y
+    return _resize_bilinear(y, (Ho, Wo), (int(size[0]), int(size[1])), out)
+
+
+def _conv_transpose2d_f32(x: Var, mod, stride: int, padding: int, op: int) -> Var:
+    """The fp32 transposed convolution with output_padding ``op``: the natural output plus ``op`` rows and columns."""
+    tape = current_tape()
+    xt = x.t
+    B, Cin, H, W = xt.shape
+    w = mod.weight
+    Cout, KH, KW = w.shape[1], w.shape[2], w.shape[3]
+    Hs = (H - 1) * stride - 2 * padding + KH + op  # the stored grid
+    Ws = (W - 1) * stride - 2 * padding + KW + op
     pw = packed_convT(mod, tape.enabled and x.req)
     y = _new((B, Cout, Hs, Ws), xt)
     bias = mod.bias
@@ -1467,8 +1448,6 @@ def conv_transpose2d(x: Var, mod, stride: int, padding: int, size: T.Optional[T.
               bias.data_ptr() if bias is not None else None, y.data_ptr(), bstride(y), B, Cin, H, W, Cout, KH, KW,
               stride, padding, op, 0, _stream())
     yv = Var(y, tape.enabled)
-    if op:
-        yv.valid = (Ho, Wo)
     if tape.enabled:
         store = current_store()
 
@@ -1551,13 +1530,9 @@ def time_conv(x: Var, mod, tin: int) -> Var:
 
 
 _pt_ws: T.Dict[T.Tuple, torch.Tensor] = {}
-# The fused PreTimeReduction family (csrc/cn_pretime.hip). CN_PRETIME_FUSED = "1" (default): training
-# and inference (forward 3 launches / 1 in eval mode instead of ~20, backward 3 instead of ~20; same-box A/B in round 4:
-# bf16 batch 32 at parity with the op-by-op path, fp32 batch 8 +1 %, 32 / 29 launches fewer per step); "infer": the
-# inference forward only; "0": never. CN_PRETIME_BWD = "main" (default) / "side": the stream of the three backward
-# launches -- queued on the weight-gradient stream, behind the encoder's 100 x 100 weight gradients, they cost 1 %.
-_PRETIME_FUSED = os.environ.get("CN_PRETIME_FUSED", "1")
-_PRETIME_BWD = os.environ.get("CN_PRETIME_BWD", "main")
+# The fused PreTimeReduction family (csrc/cn_pretime.hip) serves training and inference (forward 3
+# launches / 1 in eval mode instead of ~20, backward 3 instead of ~20; same-box A/B in round 4 against the op-by-op
+# path: bf16 batch 32 at parity, fp32 batch 8 +1 %, 32 / 29 launches fewer per step).
 
 
 def _zeroed_scratch(n: int, dev: torch.device) -> torch.Tensor:
@@ -1587,14 +1562,12 @@ def _pretime_ws(need: int, dev: torch.device) -> torch.Tensor:
 def pretime_reduction(x: Var, pre, in_channels: int, in_time: int) -> T.Optional[Var]:
     """PreTimeReduction (models/nunet.py:60-105) through the fused kernel family cn_pretime_*: both Conv3d stacks, their
     BatchNorm3d / BatchNorm2d, the branch sum and the LayerNorm, recomputed from x in every pass (3 launches forward in
-    training, 1 in inference, 3 backward -- on the weight-gradient side stream: the stage has parameter gradients only).
+    training, 1 in inference, 3 backward on the compute stream: the stage has parameter gradients only).
     Writes fp32 NCHW, or bf16 NHWC directly when the mixed-precision region is on. Returns None for shapes / settings the
     fused kernels do not cover (the caller keeps the generic op-by-op path)."""
     import ctypes
 
     tape = current_tape()
-    if _PRETIME_FUSED == "0" or (_PRETIME_FUSED != "1" and (tape.enabled or pre.training)):
-        return None
     xt = _check(x.t)
     if is16(xt) or x.req or not xt.is_contiguous():
         return None
@@ -1650,7 +1623,7 @@ def pretime_reduction(x: Var, pre, in_channels: int, in_time: int) -> T.Optional
             glist += [b.seq[0].weight, b.seq[3].weight, b3.weight, b3.bias, b2.weight, b2.bias]
         glist += [ln.weight, ln.bias]
 
-        def bwd():
+        def bwd(stats_t=stats_t):  # (``stats`` points into stats_t: held until the backward has run)
             dy = yv.grad
             if dy is None:
                 return
@@ -1665,13 +1638,11 @@ def pretime_reduction(x: Var, pre, in_channels: int, in_time: int) -> T.Optional
             grads = (ctypes.c_void_p * 14)(*[store.grad_of(p).data_ptr() for p in glist])
             # parameter gradients only, and the LAST node of the backward. On the compute stream: the weight-gradient
             # stream still holds the encoder's 100 x 100 weight gradients at this point, behind which these three
-            # launches would queue (CN_PRETIME_BWD=side: measured 1 % slower end to end)
-            ctx = side_stream(xt, dy, stats_t) if _PRETIME_BWD == "side" else contextlib.nullcontext()
-            with ctx:
-                wsb = _pretime_ws(need, dev)
-                _lib.call("cn_pretime_bwd_f32", xt.data_ptr(), bstride(xt), params, stats, dy.data_ptr(), dstride, kind,
-                          grads, B, C, Tn, HW, Cout, 1 if training else 0, bnc, float(ln.eps), wsb.data_ptr(),
-                          wsb.numel(), _stream())
+            # launches would queue (measured 1 % slower end to end; that variant was removed)
+            wsb = _pretime_ws(need, dev)
+            _lib.call("cn_pretime_bwd_f32", xt.data_ptr(), bstride(xt), params, stats, dy.data_ptr(), dstride, kind,
+                      grads, B, C, Tn, HW, Cout, 1 if training else 0, bnc, float(ln.eps), wsb.data_ptr(), wsb.numel(),
+                      _stream())
             yv.grad = None
 
         tape.add(bwd, tuple(glist))
@@ -1776,11 +1747,12 @@ def bn_act_group(xs: T.Sequence[Var], bns: T.Sequence, act: int, residual: T.Opt
     xts = [_check(x.t) for x in xs]
     if residual is not None and not sum_outputs:
         raise ValueError("bn_act_group: a residual needs sum_outputs=True")
-    if is16(xts[0]):  # mixed precision: the G branches in one launch per pass (cn_bn_act_group_*_bf16)
-        return _bn_act_group_bf16(xs, bns, act, residual, sum_outputs, training, outs)
-    if not _bn_group_uniform(bns):
-        # the grouped kernels take ONE eps / momentum and running statistics for all layers or none: layers that
-        # differ run one bn_act each; the summed form chains the residual in the order of the fused sum
+    bf16 = is16(xts[0])
+    if not _bn_group_uniform(bns) or \
+            (bf16 and not all(tuple(t.shape) == tuple(xts[0].shape) and ld(t) == ld(xts[0]) and _dense16(t) for t in xts)):
+        # the grouped kernels take ONE eps / momentum and running statistics for all layers or none (the bf16 ones also
+        # dense NHWC inputs of one shape and pixel stride): other groups run one bn_act each; the summed form chains
+        # the residual in the order of the fused sum
         if outs is not None and len(outs) != (1 if sum_outputs else G):
             raise ValueError("bn_act_group: outs must hold one tensor per output")
         if not sum_outputs:
@@ -1791,6 +1763,8 @@ def bn_act_group(xs: T.Sequence[Var], bns: T.Sequence, act: int, residual: T.Opt
             last = i == G - 1
             acc = bn_act(x, bn, act, residual=acc, training=training, out=outs[0] if outs is not None and last else None)
         return acc
+    if bf16:  # mixed precision: the G branches in one launch per pass (cn_bn_act_group_*_bf16)
+        return _bn_act_group_bf16(xs, bns, act, residual, sum_outputs, training, outs)
     B, C = xts[0].shape[0], xts[0].shape[1]
     L = int(xts[0][0].numel()) // C
     for t in xts:
@@ -2033,17 +2007,23 @@ def spatial_channel_attention(skip: Var, out: Var, mod) -> Var:
 
 
 def resize_bilinear(x: Var, size: T.Tuple[int, int], out: T.Optional[torch.Tensor] = None) -> Var:
-    """F.interpolate(mode='bilinear', align_corners=True); identity when the size already matches. A Var with a
-    ``valid`` attribute (conv_transpose2d on the output_padding grid) is resized from the image INSIDE its stored grid."""
+    """F.interpolate(mode='bilinear', align_corners=True); identity when the size already matches."""
+    Ho, Wo = int(size[0]), int(size[1])
+    if tuple(x.shape[-2:]) == (Ho, Wo) and out is None:
+        return x
+    return _resize_bilinear(x, tuple(x.shape[-2:]), (Ho, Wo), out)
+
+
+def _resize_bilinear(x: Var, image: T.Tuple[int, int], size: T.Tuple[int, int], out: T.Optional[torch.Tensor]) -> Var:
+    """resize_bilinear of the top-left ``image`` (H, W) of x's stored grid (fp32 conv_transpose2d computes on an
+    output_padding grid larger than its image)."""
     tape = current_tape()
     xt = _check(x.t)
-    B, C, Hp, Wp = xt.shape
-    Hi, Wi = x.valid if x.valid is not None else (Hp, Wp)
-    Ho, Wo = int(size[0]), int(size[1])
-    if (Hi, Wi) == (Ho, Wo) and out is None:
-        return x
     if is16(xt):
-        return _resize_bilinear_bf16(x, (Ho, Wo), out)
+        return _resize_bilinear_bf16(x, size, out)
+    B, C, Hp, Wp = xt.shape
+    Hi, Wi = image
+    Ho, Wo = size
     y = out if out is not None else _new((B, C, Ho, Wo), xt)
     _lib.call("cn_bilinear_fwd_f32", xt.data_ptr(), bstride(xt), y.data_ptr(), bstride(y), B, C, Hi, Wi, Ho, Wo,
               Hp, Wp, _stream())
@@ -2649,9 +2629,6 @@ def _pow2(n: int) -> bool:
     return n >= 1 and (n & (n - 1)) == 0
 
 
-_CONV_BNFIN = os.environ.get("CN_CONV_BNFIN", "1") != "0"
-
-
 def _bnstats_launch(xts, pws, ys, B, Cin, H, W, Cout, KH, KW, stride, paddings, dilations, stats, bns):
     """A training-mode ConvBlock2d convolution (bias-free, G <= 4 branches) through
     cn_conv2d_fwd_grouped_bnstats_bf16: the launch writes the per-tile statistics rows AND, for launches of <= 1008 pixel
@@ -2683,7 +2660,7 @@ def _bnstats_launch(xts, pws, ys, B, Cin, H, W, Cout, KH, KW, stride, paddings, 
 
 
 def _bnfin_ok(bns, mods) -> bool:
-    return (_CONV_BNFIN and _GROUP_BF16 and bns is not None and len(bns) == len(mods)
+    return (bns is not None and len(bns) == len(mods)
             and all(m.bias is None for m in mods) and all(bn.training for bn in bns)
             and all(bn.momentum == bns[0].momentum and bn.eps == bns[0].eps for bn in bns)
             and all((bn.running_mean is None) == (bns[0].running_mean is None) for bn in bns)
@@ -2725,7 +2702,7 @@ def _conv2d_bf16(x: Var, mod, stride: int, padding: int, dilation: int, out: T.O
             dy = yv.grad
             if dy is None:
                 return
-            with side_stream(xt, dy, work=float(B) * Ho * Wo * Cin * Cout * KH * KW):
+            with side_stream(xt, dy):
                 s = _stream()
                 need = _lib.query("cn_bwgrad_workspace_floats", B, Cin, H, W, Cout, KH, KW, stride, padding, dilation, 0)
                 wsp, wsn = _ws16(need, xt.device)
@@ -2745,9 +2722,6 @@ def _conv2d_bf16(x: Var, mod, stride: int, padding: int, dilation: int, out: T.O
     return yv
 
 
-_GROUP_BF16 = os.environ.get("CN_BF16_GROUPED", "1") == "1"  # diagnostic: 0 = branch-by-branch launches (round 3)
-
-
 def _conv2d_group_bf16(xs: T.Sequence[Var], mods: T.Sequence, paddings: T.Sequence[int], dilations: T.Sequence[int],
                        stride: int, bns: T.Optional[T.Sequence] = None) -> T.List[Var]:
     """The G dilation branches of a ResidualAConv level as ONE bf16 implicit-GEMM launch (G classes of one launch:
@@ -2764,7 +2738,7 @@ def _conv2d_group_bf16(xs: T.Sequence[Var], mods: T.Sequence, paddings: T.Sequen
     w0 = mods[0].weight
     same = all(tuple(t.shape) == (B, Cin, H, W) and ld(t) == ld(xts[0]) for t in xts) and \
         all(tuple(m.weight.shape) == tuple(w0.shape) and (m.bias is None) == (mods[0].bias is None) for m in mods)
-    if not _GROUP_BF16 or G < 2 or G > 4 or not same or w0.dim() != 4:
+    if G < 2 or G > 4 or not same or w0.dim() != 4:
         return [_conv2d_bf16(x, m, stride, p, d, None, tape.enabled, bns[i] if bns is not None else None)
                 for i, (x, m, p, d) in enumerate(zip(xs, mods, paddings, dilations))]
     Cout, KH, KW = w0.shape[0], w0.shape[2], w0.shape[3]
@@ -2805,8 +2779,7 @@ def _conv2d_group_bf16(xs: T.Sequence[Var], mods: T.Sequence, paddings: T.Sequen
             live = [i for i in range(G) if yvs[i].grad is not None]
             if not live:
                 return
-            with side_stream(*(list(xts) + [yvs[i].grad for i in live]),
-                             work=float(len(live)) * B * Ho * Wo * Cin * Cout * KH * KW):
+            with side_stream(*(list(xts) + [yvs[i].grad for i in live])):
                 s = _stream()
                 for i in live:
                     dy, m = yvs[i].grad, mods[i]
@@ -2849,7 +2822,7 @@ class _Fold16:
         self.key = None
 
 
-_EVAL_FUSION = os.environ.get("CN_EVAL_FUSION", "1") == "1"
+_EVAL_FUSION = True
 
 
 def eval_fusion(enabled: bool) -> bool:
@@ -2952,7 +2925,7 @@ def _conv_transpose2d_bf16(x: Var, mod, stride: int, padding: int) -> Var:
 
 def _bn_act_bf16(x: Var, bn, act: int, residual: T.Optional[Var], training: bool,
                  out: T.Optional[torch.Tensor]) -> Var:
-    if _GROUP_BF16 and _dense16(x.t) and (out is None or _dense16(out)):
+    if _dense16(x.t) and (out is None or _dense16(out)):
         # G = 1 of the grouped entry point: same arithmetic, the finalize is ONE coalesced, ticketed launch
         return _bn_act_group_bf16([x], [bn], act, residual, True, training, [out] if out is not None else None)
     tape = current_tape()
@@ -3018,6 +2991,7 @@ def _bn_group_ws16(G: int, C: int, dev: torch.device) -> int:
 
 def _bn_act_group_bf16(xs: T.Sequence[Var], bns: T.Sequence, act: int, residual: T.Optional[Var], sum_outputs: bool,
                        training: bool, outs: T.Optional[T.Sequence[torch.Tensor]]) -> T.Union[Var, T.List[Var]]:
+    """bn_act_group in bf16, for layers one grouped launch serves (checked by the callers: bn_act_group, _bn_act_bf16)."""
     import ctypes
 
     tape = current_tape()
@@ -3026,21 +3000,8 @@ def _bn_act_group_bf16(xs: T.Sequence[Var], bns: T.Sequence, act: int, residual:
     B, C, H, W = xts[0].shape
     P = B * H * W
     dev = xts[0].device
-    ok = 1 <= G <= 4 and all(tuple(t.shape) == (B, C, H, W) and ld(t) == ld(xts[0]) and _dense16(t) for t in xts) \
-        and all(bn.momentum == bns[0].momentum and bn.eps == bns[0].eps for bn in bns) \
-        and all((bn.running_mean is None) == (bns[0].running_mean is None) for bn in bns)
     use_batch = training or (bns[0].running_mean is None)
     has_sums = all(x.stats is not None for x in xs) and len({x.stats.shape[0] for x in xs}) == 1
-    if not _GROUP_BF16 or not ok:
-        if outs is not None and len(outs) != (1 if sum_outputs else G):
-            raise ValueError("bn_act_group: outs must hold one tensor per output")
-        if not sum_outputs:
-            return [_bn_act_bf16(x, bn, act, None, training, outs[i] if outs is not None else None)
-                    for i, (x, bn) in enumerate(zip(xs, bns))]
-        acc = residual
-        for x, bn in zip(xs, bns):
-            acc = _bn_act_bf16(x, bn, act, acc, training, None)
-        return acc
     _note_bn_update(training)
     tab = lambda ptrs: (ctypes.c_void_p * G)(*ptrs)
     if outs is not None:

@@ -17,9 +17,7 @@ def _trajectory(precision, hidden, B, H, streams, steps=5, dropout=0.0, seed=123
     from cultionet_amd.data import Data
     from cultionet_amd.lightning import CultionetLitModel, HipTrainer
 
-    prev = E._HEAD_STREAMS
-    E._HEAD_STREAMS = streams
-    try:
+    with E.branch_streams(streams):
         lit = CultionetLitModel(in_channels=3, in_time=12, hidden_channels=hidden, dropout=dropout)
         m = lit.cultionet_model.mask_model
         m.load_state_dict(S.seeded_state_dict(m.state_dict()))
@@ -33,8 +31,6 @@ def _trajectory(precision, hidden, B, H, streams, steps=5, dropout=0.0, seed=123
         torch.cuda.synchronize()
         state = {n: p.detach().float().cpu().clone() for n, p in m.named_parameters()}
         return np.array(losses), state
-    finally:
-        E._HEAD_STREAMS = prev
 
 
 @pytest.mark.parametrize("precision,tol", [("32-true", 5e-6), ("bf16-mixed", 2e-3)])

@@ -168,6 +168,18 @@ def test_conv_transpose2d(case):
     _close(pg["bias"], ref_b, 1e-4, "db")
 
 
+class _RoundBF16(torch.autograd.Function):
+    """Identity that rounds its value and its gradient to bf16."""
+
+    @staticmethod
+    def forward(ctx, t):
+        return t.to(torch.bfloat16).float()
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.to(torch.bfloat16).float()
+
+
 @pytest.mark.parametrize("case", [
     # B, C, H, W, stride, size: the ConvTranspose2d + check_upsample sites of TowerUNet (convolution.py:45-68)
     (2, 16, 25, 25, 2, 50),    # 49 -> 50
@@ -208,6 +220,54 @@ def test_conv_transpose2d_then_resize(case):
     _close(dx, xr.grad, 1e-4, "dx")
     _close(pg["up_conv.weight"], ref_w, 1e-4, "dw")
     _close(pg["up_conv.bias"], ref_b, 1e-4, "db")
+
+
+@pytest.mark.parametrize("case", [
+    # the sites of test_conv_transpose2d_then_resize
+    (2, 16, 25, 25, 2, 50),
+    (2, 24, 50, 50, 2, 100),
+    (1, 16, 25, 25, 4, 100),
+    (2, 16, 13, 13, 2, 25),
+    (2, 8, 14, 14, 2, 30),
+])
+def test_conv_transpose2d_then_resize_bf16(case):
+    """test_conv_transpose2d_then_resize in bf16 (NHWC): the natural output is resized. Held to
+    test_conv_transpose2d_bf16's tolerances against a reference with bf16-rounded inputs and intermediate (the bf16
+    region stores the natural output and its gradient in bf16 between the two ops)."""
+    from cultionet_amd import engine as E
+    from cultionet_amd.convolution import ConvTranspose2d
+
+    B, C, H, W, s, size = case
+    BF = torch.bfloat16
+    torch.manual_seed(11)
+    mod = ConvTranspose2d(C, C, 3, s, 1)
+    x = _rand(B, C, H, W, seed=31).to(BF).float()
+    with torch.no_grad():  # the engine packs the weights to bf16
+        mod.up_conv.weight.copy_(mod.up_conv.weight.to(BF).float())
+    xr = x.clone().requires_grad_(True)
+    yr = _RoundBF16.apply(mod.up_conv(xr))
+    if yr.shape[-1] != size:
+        yr = F.interpolate(yr, size=(size, size), mode="bilinear", align_corners=True)
+    dy = _rand(*yr.shape, seed=32).to(BF).float()
+    yr.backward(dy)
+    ref_w, ref_b = mod.up_conv.weight.grad.clone(), mod.up_conv.bias.grad.clone()
+    # (_engine_run makes its inputs NCHW-contiguous: the bf16 region keeps NHWC buffers)
+    dev = _dev()
+    nhwc = lambda t: t.to(dev, BF).permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+    mod = mod.to(dev)
+    store = E.ParamStore(mod)
+    store.zero_grad()
+    with E.using_store(store), E.recording(True) as tape:
+        xv = E.Var(nhwc(x), True)
+        yv = mod(xv, size=(size, size))
+        yv.grad = nhwc(dy)
+        tape.backward()
+    torch.cuda.synchronize()
+    assert tuple(yv.shape[-2:]) == (size, size)
+    _close_rel(yv.t.float().cpu(), yr, 6e-3, "y")
+    _close_rel(xv.grad.float().cpu(), xr.grad, 6e-3, "dx")
+    _close_rel(store.grad_of(mod.up_conv.weight).cpu(), ref_w, 2e-3, "dw")
+    _close_rel(store.grad_of(mod.up_conv.bias).cpu(), ref_b, 2e-3, "db")
 
 
 @pytest.mark.parametrize("k", [3, 5])

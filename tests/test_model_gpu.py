@@ -124,14 +124,12 @@ def test_native_train_step_matches_reference(golden_dir, name, kw):
 
 @pytest.mark.parametrize("name", ["train_h8_b2_28_masked", "train_h32_b1_100", "train_h32_b8_100"])
 def test_native_train_step_with_fused_pretime_matches_reference(golden_dir, name, monkeypatch):
-    """The same step with the fused PreTimeReduction kernel family (cn_pretime_*) switched on for TRAINING
-    (CN_PRETIME_FUSED=1; by default it serves inference only): loss, maps, masks and every gradient norm -- including
-    the eighteen PreTimeReduction parameters whose gradients the three fused backward passes produce -- against the
-    reference fixtures at the same tolerances."""
+    """The same step through the fused PreTimeReduction kernel family (cn_pretime_*), which serves training as well as
+    inference: loss, maps, masks and every gradient norm -- including the eighteen PreTimeReduction parameters whose
+    gradients the three fused backward passes produce -- against the reference fixtures at the same tolerances."""
     from cultionet_amd import engine as E
     from cultionet_amd.lightning import HipTrainer
 
-    monkeypatch.setattr(E, "_PRETIME_FUSED", "1")
     g = np.load(os.path.join(golden_dir, name + ".npz"))
     lit, ref, batch = _setup(g)
     lit.train()

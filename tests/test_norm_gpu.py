@@ -573,6 +573,30 @@ def test_bn_act_group_layers_that_differ(what, summed, training, dtype):
                 tag=f"mixed {what}", dtype=dtype)
 
 
+def test_bn_act_group_bf16_layers_that_differ_write_outs():
+    """bf16, summed, two layers of different eps (one bn_act per layer): the result lands in the caller's ``outs``
+    buffer, with the values of the same call without ``outs``."""
+    from cultionet_amd import engine as E
+
+    B, C, H, W = 4, 32, 20, 20
+    bns = _mixed_layers(C, "eps")
+    mods = nn.ModuleList(bns).train()
+    ins = [_x((B, C, H, W), 310 + g, edges="bf16").to(BF).permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+           for g in range(2)]
+    dy = _randn((B, C, H, W), 410).to(BF).permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+    buf = torch.full((B, H, W, C), float("nan"), dtype=BF, device=_dev()).permute(0, 3, 1, 2)
+
+    def fn(outs):
+        return lambda *vs: E.bn_act_group(list(vs), bns, E.ACT_SILU, sum_outputs=True, training=True, outs=outs)
+
+    (y_ref,), dx_ref, _ = _run(mods, fn(None), ins, [dy])
+    (y,), dx, _ = _run(mods, fn([buf]), ins, [dy])
+    assert y.data_ptr() == buf.data_ptr()
+    assert torch.equal(buf, y_ref)
+    for g in range(2):
+        assert torch.equal(dx[g], dx_ref[g])
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # bf16 bn_act / bn_act_group, and the statistics epilogue of the convolution
 # ---------------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
-"""Where a data-parallel step (one-rank RCCL group) spends its time with / without the branch streams: HIP events around
-forward+loss, backward (incl. the bucket launches) and the optimizer.  CN_KEEP_BRANCH_STREAMS=1 keeps spawn() active."""
+"""Where a data-parallel step (one-rank RCCL group) spends its time: HIP events around forward+loss, backward (incl. the
+bucket launches) and the optimizer."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER_PORT", "29617")
