@@ -14,15 +14,23 @@ forward + Tanimoto loss + backward + global-norm clip + AdamW, all in the hand-w
 master weights / statistics / accumulation). N > 1 shards chips over ranks (weak scaling, per-GPU batch fixed) with one
 bucketed RCCL all-reduce of the flat gradient overlapped with the backward tape.
 
-Rank 0 prints ONE JSON line. `roofline` is the dominant kernel's algorithmic FLOP/s from HIP events recorded on the
-launch stream inside the timed region (`kernel` = the real rocprof kernel name, `family` = its template family);
-`cpu_baseline` is the CPU oracle (a port of the reference's PyTorch-CPU path) timed on this box's host cores on a
-bounded sample (rank 0, N=1 only); `loss_delta_vs_cpu` compares the step-1 loss of both legs (identical key-seeded
-weights and batch); `roofline.streaming` = GB/s of the HBM-bound BatchNorm / LayerNorm / bilinear entry points from a
-short separate pass after the timed region; `bf16` = BASELINE configs[2] (batch 32, bf16 mixed precision: its own
-timed steps, roofline against the nominal 2.5 PFLOP/s and step-1 loss vs the CPU oracle) -- per-GPU batch 32 under
-N ranks is configs[3]; `predict` = BASELINE configs[4] (sliding-window scene prediction, pixels/s, GPU and CPU);
-`feed` = the same step fed a FRESH host batch per step through the pinned-host -> device double-buffered loader.
+Rank 0 prints ONE JSON line. A plain run does what its headline figure needs: it sets the configuration up, runs the W
+warm-up steps, times the K steps, writes `--dump-outputs` and prints the line. Between warm-up and timed steps it runs
+min(K, 3) untimed steps with every contraction launch bracketed by HIP events: they name the dominant kernel, whose
+launches alone the timed region brackets. `roofline` is that kernel's algorithmic FLOP/s from those events on the launch
+stream inside the timed region (`kernel` = the real rocprof kernel name, `family` = its template family).
+
+`--full` adds everything else the benchmark measures, after the timed region, in steps or processes of its own
+(`--no-extras` keeps only the counted step and `cpu_baseline`, `--no-cpu-baseline` drops the CPU legs):
+`config.kernel_launches_per_step` / `abi_calls_per_step` from one counted step; `roofline.isolated` = the step with the
+weight-gradient side stream off; `cpu_baseline` is the CPU oracle (a port of the reference's PyTorch-CPU path) timed on
+the host's cores on a bounded sample (rank 0, N=1 only); `loss_delta_vs_cpu` compares the step-1 loss of both legs
+(identical key-seeded weights and batch); `roofline.streaming` = GB/s of the HBM-bound BatchNorm / LayerNorm / bilinear
+entry points from a short separate pass; `bf16` = BASELINE configs[2] (batch 32, bf16 mixed precision: its own timed
+steps, roofline against the nominal 2.5 PFLOP/s and step-1 loss vs the CPU oracle) -- per-GPU batch 32 under N ranks is
+configs[3]; `predict` = BASELINE configs[4] (sliding-window scene prediction, pixels/s, GPU and CPU); `feed` = the same
+step fed a FRESH host batch per step through the pinned-host -> device double-buffered loader; `ddp1` = both precisions
+under a one-rank RCCL group; `default_point` = the reference CLI's default operating point.
 
 `--dump-outputs DIR` writes what the last timed step of the headline configuration computed (rank 0), as float32
 `DIR/<name>.npy`: `loss`, `loss_terms` (distance / edge / crop), the `distance` / `edge` / `crop` maps, and the model
@@ -91,12 +99,16 @@ def parse():
     ap.add_argument("--batch", type=int, default=None, help="chips per GPU (default 8 for f32, 32 for bf16)")
     ap.add_argument("--hidden", type=int, default=32)
     ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the streaming-kernel pass and the predict block")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: CPU baseline, other configurations, "
+                         "per-kernel and streaming figures (see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU legs")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: keep only the counted step and the CPU baseline")
     ap.add_argument("--cpu-steps", type=int, default=4)
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = best of the documented sweep (16)")
     ap.add_argument("--child", choices=("train", "predict", "default_point"), default=None,
-                    help="internal: one block of the default line in a process of its own (see run_child)")
+                    help="internal: one block of the --full line in a process of its own (see run_child)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch + rendezvous check only (gloo, no GPU, no kernels): what tests/test_bench_launch.py runs")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -473,6 +485,30 @@ def write_outputs(arrays: dict, directory: str) -> None:
         np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
+def counted_step(trainer, batch):
+    """(C-ABI calls, kernel launches) of one extra untimed step."""
+    import torch
+
+    from cultionet_amd import _lib
+
+    calls = [0]
+    orig_call = _lib.call
+
+    def counting(name, *a):
+        calls[0] += 1
+        return orig_call(name, *a)
+
+    _lib.call = counting
+    _lib.query("cn_launch_count", 1)
+    try:
+        trainer.training_step(batch)
+    finally:
+        _lib.call = orig_call
+    launches = _lib.query("cn_launch_count", 1)
+    torch.cuda.synchronize()
+    return calls[0], launches
+
+
 def launch_ranks(args) -> int:
     """`python bench.py --gpus N` with N > 1 outside torch.distributed.run: start the ranks as a CHILD process (this
     parent has not touched the GPU and never does), relay rank 0's JSON line, return the child's exit code."""
@@ -498,14 +534,15 @@ def launch_ranks(args) -> int:
 
 
 def run_child(kind: str, args, extra: typing.Sequence[str] = (), env_extra: typing.Optional[dict] = None) -> dict:
-    """One block of the default line -- the bf16 configuration, the predict scene -- in a FRESH child process of rank 0
+    """One block of the --full line -- the bf16 configuration, the predict scene -- in a FRESH child process of rank 0
     (N = 1 only). Which HIP streams end up sharing a hardware queue depends on the creation history of a process
     (DESIGN.md section 7): the second configuration of a process measured 1611-1937 chips/s where a process of its own
     gets 1900-1955. A child is started (never exec'ed), after this process has released its GPU memory."""
     import subprocess
 
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", kind, "--gpus", "1", "--steps", str(args.steps),
-           "--warmup", str(args.warmup), "--hidden", str(args.hidden), "--cpu-threads", str(args.cpu_threads)]
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", kind, "--full", "--gpus", "1", "--steps",
+           str(args.steps), "--warmup", str(args.warmup), "--hidden", str(args.hidden), "--cpu-threads",
+           str(args.cpu_threads)]
     cmd += list(extra)
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
@@ -586,10 +623,11 @@ class TrainLeg:
             dist.barrier()
         torch.cuda.synchronize()
 
-    def run(self, steps: int, warmup: int, extras: bool, capture: bool = False):
+    def run(self, steps: int, warmup: int, full: bool = False, extras: bool = False, capture: bool = False):
         """W untimed + K timed steps (barrier + synchronize on both sides, max over ranks). Returns the record.
-        capture: the last timed step starts from the initial training state (every rank), and rank 0 keeps host copies
-        of its outputs in ``self.outputs`` (after the clock)."""
+        full: one counted step after the clock (C-ABI calls and kernel launches per step); extras: the isolated
+        per-kernel pass (N = 1). capture: the last timed step starts from the initial training state (every rank), and
+        rank 0 keeps host copies of its outputs in ``self.outputs`` (after the clock)."""
         import torch
         import torch.distributed as dist
 
@@ -657,22 +695,7 @@ class TrainLeg:
             self.comm.measure = False
             comm_ms = sum(a.elapsed_time(b) for a, b in self.comm.exposed) / max(steps, 1)
             buckets = self.comm.buckets_last_step
-        # C-ABI calls and kernel launches per step, counted on one extra untimed step
-        calls = [0]
-        orig_call = _lib.call
-
-        def counting(name, *a):
-            calls[0] += 1
-            return orig_call(name, *a)
-
-        _lib.call = counting
-        _lib.query("cn_launch_count", 1)
-        try:
-            trainer.training_step(batch)
-        finally:
-            _lib.call = orig_call
-        launches = _lib.query("cn_launch_count", 1)
-        torch.cuda.synchronize()
+        calls, launches = counted_step(trainer, batch) if full else (None, None)
         t = torch.tensor([dt], dtype=torch.float64, device=self.dev)
         if self.use_dist:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -741,7 +764,7 @@ class TrainLeg:
                 "comm_ms_exposed": comm_ms,
                 "end_barrier_ms": end_barrier_ms if self.use_dist else 0.0,
                 "loss": loss_val,
-                "abi_calls_per_step": calls[0],
+                "abi_calls_per_step": calls,
                 "kernel_launches_per_step": launches,
                 # the stream set this step ran on (at most seven hardware queues run concurrently):
                 # normal-priority pool capped at GPU_MAX_HW_QUEUES, + the lowest-priority weight-gradient queue, + ONE
@@ -884,15 +907,16 @@ def main():
     if args.child == "default_point":
         print(json.dumps(default_point_block(dev, min(args.steps, 30), args.warmup)), flush=True)
         return
-    if args.child == "predict":  # the predict block alone (child of a default run)
+    if args.child == "predict":  # the predict block alone (child of a --full run)
         print(json.dumps(predict_block(dev, args.hidden, not args.no_cpu_baseline, args.cpu_threads)), flush=True)
         return
     bf16 = args.dtype == "bf16"
     B = args.batch if args.batch is not None else (32 if bf16 else 8)
-    extras = not args.no_extras
+    extras = args.full and not args.no_extras
+    cpu = args.full and not args.no_cpu_baseline
     child = args.child == "train"
     leg = TrainLeg(dev, rank, world, comm, use_dist, args.dtype, B, args.hidden)
-    rec = leg.run(args.steps, args.warmup, extras, capture=args.dump_outputs is not None)
+    rec = leg.run(args.steps, args.warmup, args.full, extras, capture=args.dump_outputs is not None)
     out = None
     if rank == 0:
         if args.dump_outputs is not None:
@@ -909,7 +933,7 @@ def main():
             out["roofline"]["streaming"] = streaming_pass(leg.trainer, leg.batch)
             if not child:
                 out["feed"] = feed_block(leg, min(args.steps, 20), rec["ms_per_step"])
-        if world == 1 and not args.no_cpu_baseline and not child:
+        if world == 1 and cpu and not child:
             out["cpu_baseline"], cpu_first = cpu_baseline(B, args.hidden, args.cpu_steps, args.cpu_threads)
             if first_loss is not None:
                 out["loss_delta_vs_cpu"] = {"hip_step1_loss": first_loss, "cpu_step1_loss": cpu_first,
@@ -949,7 +973,7 @@ def main():
                 rec16 = {"error": err or "another rank failed to set the bf16 configuration up"}
             else:
                 try:
-                    rec16 = leg16.run(args.steps, args.warmup, False)
+                    rec16 = leg16.run(args.steps, args.warmup, full=True)
                 except Exception as e:
                     err = repr(e)
                 if not agree(err is None):  # the step loop holds collectives: a one-rank failure is fatal for the job
@@ -962,7 +986,7 @@ def main():
             del leg16
             torch.cuda.empty_cache()
         if rank == 0:
-            if world == 1 and not args.no_cpu_baseline and fl16 is not None and "value" in rec16:
+            if world == 1 and cpu and fl16 is not None and "value" in rec16:
                 c16 = cpu_first_loss(32, args.hidden, args.cpu_threads)  # forward + loss only: a few seconds
                 rec16["loss_delta_vs_cpu"] = {"hip_step1_loss": fl16, "cpu_step1_loss": c16,
                                               "abs_delta": abs(fl16 - c16), "tolerance": 5e-4}

@@ -1,6 +1,7 @@
-"""The default `python bench.py` line on a real GPU: ONE JSON line on stdout carrying the contract's fields, the roofline
-and cpu_baseline objects, and the extra blocks (bf16 = BASELINE configs[2], predict = configs[4], feed) without errors.
-Short run (3 timed steps, a 2-step CPU leg); the numbers themselves are the driver's business."""
+"""`python bench.py` on a real GPU: ONE JSON line on stdout. With --full it carries the contract's fields, the roofline
+and cpu_baseline objects, and the extra blocks (bf16 = BASELINE configs[2], predict = configs[4], feed) without errors;
+a plain run carries the headline figure and none of the extra blocks. Short runs (3 timed steps, a 1-step CPU leg); the
+numbers themselves are the driver's business."""
 import json
 import os
 import subprocess
@@ -16,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_default_bench_line_has_every_block():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
-                        "--cpu-steps", "1"], env=env, capture_output=True, text=True, timeout=900)
+                        "--cpu-steps", "1", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -61,12 +62,20 @@ def test_default_bench_line_has_every_block():
 def _dump(out, steps, warmup):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup",
-                        str(warmup), "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(out)],
+                        str(warmup), "--dump-outputs", str(out)],
                        env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, p.stdout[-2000:]
-    return json.loads(lines[0])
+    d = json.loads(lines[0])
+    # a plain run: the headline figure, none of what --full adds
+    assert d["metric"] == "train_chips_per_sec" and d["unit"] == "chips/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["value"] > 0 and abs(d["value"] * d["ms_per_step"] - 8e3) <= 1e-6 * 8e3
+    for k in ("cpu_baseline", "loss_delta_vs_cpu", "feed", "bf16", "predict", "ddp1", "default_point"):
+        assert k not in d, k
+    assert "streaming" not in d["roofline"] and d["roofline"]["isolated"] is None
+    assert d["config"]["kernel_launches_per_step"] is None
+    return d
 
 
 def test_dump_outputs_writes_the_last_timed_step(tmp_path):

@@ -9,14 +9,14 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/evidence
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py > $O/${TAG}_bench_default.json 2> $O/bench_default.err
-python3 $R/bench.py --dtype bf16 > $O/${TAG}_bench_bf16_b32.json 2> $O/bench_bf16.err
+python3 $R/bench.py --full > $O/${TAG}_bench_default.json 2> $O/bench_default.err
+python3 $R/bench.py --full --dtype bf16 > $O/${TAG}_bench_bf16_b32.json 2> $O/bench_bf16.err
 # hidden 64 = the reference CLI's default width (scripts/args.yml:220-226), both precisions, short runs
-python3 $R/bench.py --hidden 64 --steps 10 --warmup 3 --no-cpu-baseline --no-extras > $O/${TAG}_bench_f32_b8_h64.json 2> $O/bench_h64.err
-python3 $R/bench.py --hidden 64 --dtype bf16 --batch 16 --steps 10 --warmup 3 --no-cpu-baseline --no-extras > $O/${TAG}_bench_bf16_b16_h64.json 2>> $O/bench_h64.err
+python3 $R/bench.py --full --hidden 64 --steps 10 --warmup 3 --no-cpu-baseline --no-extras > $O/${TAG}_bench_f32_b8_h64.json 2> $O/bench_h64.err
+python3 $R/bench.py --full --hidden 64 --dtype bf16 --batch 16 --steps 10 --warmup 3 --no-cpu-baseline --no-extras > $O/${TAG}_bench_bf16_b16_h64.json 2>> $O/bench_h64.err
 # one-rank RCCL group (the only RCCL path one GPU can exercise): buckets per step and exposed communication time
-# (fp32 batch 8 and bf16 batch 32 under a one-rank RCCL group are the `ddp1` block of the default line since round 5)
-CN_FORCE_COMM=1 python3 $R/bench.py --hidden 64 --steps 10 --warmup 3 --no-cpu-baseline --no-extras > $O/${TAG}_bench_forcecomm_f32_b8_h64.json 2> $O/bench_fc.err
+# (fp32 batch 8 and bf16 batch 32 under a one-rank RCCL group are the `ddp1` block of the --full line)
+CN_FORCE_COMM=1 python3 $R/bench.py --full --hidden 64 --steps 10 --warmup 3 --no-cpu-baseline --no-extras > $O/${TAG}_bench_forcecomm_f32_b8_h64.json 2> $O/bench_fc.err
 # ordered kernel traces of one step (hardware queue per kernel): fp32 batch 8 and bf16 batch 32
 for P in f32 bf16; do
   A=""; [ $P = bf16 ] && A="--dtype bf16"

@@ -1,5 +1,5 @@
 #!/bin/bash
-# GPU box: the whole -m gpu suite, smoke(), and the default bench line. usage: bash tools/gpu_suite.sh <tag>
+# On an MI355X: the whole -m gpu suite, smoke(), and the --full bench line. usage: bash tools/gpu_suite.sh <tag>
 set -u
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/${1:-r05_full}
@@ -9,7 +9,7 @@ timeout 1800 python3 -m pytest tests -m gpu -q -s --durations=8 > $O/pytest.log 
 echo "pytest rc $?" >> $O/pytest.log
 grep -E "^FAILED|^ERROR|passed|failed|rc |bitwise" $O/pytest.log | tail -12
 python3 -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-timeout 900 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python3 - <<PY
 import json
 d=json.load(open('$O/bench_default.json'))
