@@ -116,6 +116,13 @@ SIGNATURES = {
     "cn_na2d_fwd_bf16": [P, L, P, L, P, I, I, I, I, I, I, I, F, U64, P, P],
     "cn_na2d_bwd_bf16": [P, L, P, L, P, P, P, L, I, I, I, I, I, I, I, F, U64, P, P],
     "cn_dropout_bf16": [P, L, P, L, I, I, I, F, U64, P, I, I, P],
+    "cn_sca_workspace_floats_bf16": [I, I, I],
+    "cn_sca_pool_fwd_bf16": [P, L, I, I, I, P, P, P, P, P, L, P],
+    "cn_sca_pool_bwd_bf16": [P, L, P, P, P, P, P, L, I, I, I, I, P],
+    "cn_sca_apply_fwd_bf16": [P, L, P, P, P, P, L, I, I, I, P],
+    "cn_sca_apply_bwd_bf16": [P, L, P, L, P, P, P, P, L, I, P, P, P, P, L, I, I, I, P],
+    "cn_adaptive_maxpool_fwd_bf16": [P, L, P, L, P, I, I, I, I, I, I, P],
+    "cn_adaptive_maxpool_bwd_bf16": [P, L, P, P, L, I, I, I, I, I, I, I, P],
     "cn_pretime_workspace_floats": [I, I, I, I, I, I],
     "cn_pretime_fwd_f32": [P, L, P, P, P, L, I, I, I, I, I, I, I, P, F, P, L, P],
     "cn_pretime_bwd_f32": [P, L, P, P, P, L, I, P, I, I, I, I, I, I, P, F, P, L, P],
@@ -182,7 +189,8 @@ def call(name: str, *args) -> int:
 
 
 LONG_RESULT = {"cn_launch_count", "cn_bconv_packed_elems", "cn_bwgrad_workspace_floats", "cn_bn_workspace_floats_bf16",
-               "cn_bn_group_workspace_floats_bf16", "cn_pretime_workspace_floats"}
+               "cn_bn_group_workspace_floats_bf16", "cn_pretime_workspace_floats",
+               "cn_sca_workspace_floats_bf16"}
 
 DOUBLE_RESULT = {"cn_profile_top_bytes"}
 

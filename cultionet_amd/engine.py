@@ -1931,7 +1931,7 @@ def spatial_channel_attention(skip: Var, out: Var, mod) -> Var:
     tape = current_tape()
     st, ot = _check(skip.t), _check(out.t)
     if is16(st):
-        raise NotImplementedError("attention_weights='spatial_channel' has no bf16 kernel (fp32 only)")
+        return _spatial_channel_attention_bf16(skip, out, mod)
     B, C, H, W = st.shape
     L = H * W
     Ch = C // 2
@@ -2507,7 +2507,7 @@ def adaptive_max_pool2d(x: Var, size: T.Tuple[int, int]) -> Var:
     tape = current_tape()
     xt = _check(x.t)
     if is16(xt):
-        raise NotImplementedError("pool_by_max has no bf16 kernel (fp32 only)")
+        return _adaptive_max_pool2d_bf16(x, size)
     B, C, Hi, Wi = xt.shape
     Ho, Wo = int(size[0]), int(size[1])
     y = _new((B, C, Ho, Wo), xt)
@@ -3162,6 +3162,114 @@ def _resize_bilinear_bf16(x: Var, size: T.Tuple[int, int], out: T.Optional[torch
                 dx, acc = grad_buffer(x)
                 _lib.call("cn_bilinear_bwd_bf16", dy.data_ptr(), ld(dy), dx.data_ptr(), ld(dx), B, C, Hi, Wi, Ho, Wo, acc,
                           _stream())
+            yv.grad = None
+
+        tape.add(bwd)
+    return yv
+
+
+def _spatial_channel_attention_bf16(skip: Var, out: Var, mod) -> Var:
+    """spatial_channel_attention on bf16 NHWC skip / out: the pools and the gating run on the bf16 kernels; the channel
+    MLPs (fp32 [B][C] in and out) and the 3x3 conv on the fp32 pooled maps [B][2][H][W] stay on their fp32 kernels.
+    The tape has the fp32 structure: the pooling node is recorded first and runs last, after the apply node has handed
+    d ca over and the 3x3 conv's backward has produced d pooled."""
+    tape = current_tape()
+    st, ot = skip.t, out.t
+    B, C, H, W = st.shape
+    L = H * W
+    Ch = C // 2
+    dev = st.device
+    fc1, fc2 = mod.channel_attention.fc1, mod.channel_attention.fc2
+    w1a, w2a, w1m, w2m = fc1[0].weight, fc1[2].weight, fc2[0].weight, fc2[2].weight
+    gamma = mod.gamma
+    f = lambda *shape: _alloc(shape, torch.float32, dev)
+    avg, mx, ca = f(B, C), f(B, C), f(B, C)
+    hpre_a, hpre_m = f(B, Ch), f(B, Ch)
+    idx = _alloc((B, C), torch.int32, dev)
+    pooled = f(B, 2, H, W)
+    nws = _lib.query("cn_sca_workspace_floats_bf16", B, C, L)
+    ws = f(max(nws, 1))
+    s = _stream()
+    _lib.call("cn_sca_pool_fwd_bf16", st.data_ptr(), ld(st), B, C, L, avg.data_ptr(), mx.data_ptr(), idx.data_ptr(),
+              pooled.data_ptr(), ws.data_ptr(), nws, s)
+    _lib.call("cn_sca_mlp_fwd_f32", avg.data_ptr(), mx.data_ptr(), w1a.data_ptr(), w2a.data_ptr(), w1m.data_ptr(),
+              w2m.data_ptr(), hpre_a.data_ptr(), hpre_m.data_ptr(), ca.data_ptr(), B, C, Ch, s)
+    pv = Var(pooled, tape.enabled)
+    shared = {}  # d ca handed from the apply node to the pooling node
+    if tape.enabled:
+        store = current_store()
+
+        def bwd_pool():  # recorded first => runs last: after the apply node and the 3x3 conv's backward
+            dca = shared.pop("dca", None)
+            if dca is None:
+                return
+            s2 = _stream()
+            davg, dmx = f(B, C), f(B, C)
+            _lib.call("cn_sca_mlp_bwd_f32", avg.data_ptr(), mx.data_ptr(), w1a.data_ptr(), w2a.data_ptr(),
+                      w1m.data_ptr(), w2m.data_ptr(), hpre_a.data_ptr(), hpre_m.data_ptr(), ca.data_ptr(),
+                      dca.data_ptr(), store.grad_of(w1a).data_ptr(), store.grad_of(w2a).data_ptr(),
+                      store.grad_of(w1m).data_ptr(), store.grad_of(w2m).data_ptr(), davg.data_ptr(), dmx.data_ptr(),
+                      B, C, Ch, s2)
+            if skip.req:
+                dpool = pv.grad
+                if dpool is None:
+                    dpool = _alloc_like(pooled)
+                    _lib.call("cn_fill_f32", dpool.data_ptr(), dpool.numel(), 0.0, s2)
+                dx, acc = grad_buffer(skip)
+                _lib.call("cn_sca_pool_bwd_bf16", st.data_ptr(), ld(st), davg.data_ptr(), dmx.data_ptr(),
+                          idx.data_ptr(), dpool.data_ptr(), dx.data_ptr(), ld(dx), B, C, L, acc, s2)
+            pv.grad = None
+
+        tape.add(bwd_pool, (w1a, w2a, w1m, w2m))
+    sconv = thin_conv3x3(pv, [mod.spatial_attention.conv], grouped=False)  # fp32 [B,1,H,W], pre-sigmoid
+    y = _new(ot.shape, ot)
+    _lib.call("cn_sca_apply_fwd_bf16", ot.data_ptr(), ld(ot), ca.data_ptr(), sconv.t.data_ptr(), gamma.data_ptr(),
+              y.data_ptr(), ld(y), B, C, L, s)
+    yv = Var(y, tape.enabled)
+    if tape.enabled:
+
+        def bwd_apply():
+            dy = yv.grad
+            if dy is None:
+                return
+            s2 = _stream()
+            dca, dsconv, scratch = f(B, C), f(B, 1, H, W), f(max(nws, 1))
+            if out.req:
+                do, acc = grad_buffer(out)
+                dop, dold = do.data_ptr(), ld(do)
+            else:
+                dop, dold, acc = None, 0, 0
+            _lib.call("cn_sca_apply_bwd_bf16", dy.data_ptr(), ld(dy), ot.data_ptr(), ld(ot), ca.data_ptr(),
+                      sconv.t.data_ptr(), gamma.data_ptr(), dop, dold, acc, dca.data_ptr(), dsconv.data_ptr(),
+                      store.grad_of(gamma).data_ptr(), scratch.data_ptr(), nws, B, C, L, s2)
+            shared["dca"] = dca
+            give_grad(sconv, dsconv)
+            yv.grad = None
+
+        tape.add(bwd_apply, (gamma,))
+    return yv
+
+
+def _adaptive_max_pool2d_bf16(x: Var, size: T.Tuple[int, int]) -> Var:
+    tape = current_tape()
+    xt = x.t
+    B, C, Hi, Wi = xt.shape
+    Ho, Wo = int(size[0]), int(size[1])
+    y = _new((B, C, Ho, Wo), xt)
+    need_bwd = tape.enabled and x.req
+    idx = _alloc((B, Ho, Wo, C), torch.int32, xt.device) if need_bwd else None  # argmax per output (NHWC order)
+    _lib.call("cn_adaptive_maxpool_fwd_bf16", xt.data_ptr(), ld(xt), y.data_ptr(), ld(y),
+              idx.data_ptr() if idx is not None else None, B, C, Hi, Wi, Ho, Wo, _stream())
+    yv = Var(y, need_bwd)
+    if need_bwd:
+
+        def bwd():
+            dy = yv.grad
+            if dy is None:
+                return
+            dx, acc = grad_buffer(x)
+            _lib.call("cn_adaptive_maxpool_bwd_bf16", dy.data_ptr(), ld(dy), idx.data_ptr(), dx.data_ptr(), ld(dx), B,
+                      C, Hi, Wi, Ho, Wo, acc, _stream())
             yv.grad = None
 
         tape.add(bwd)

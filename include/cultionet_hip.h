@@ -496,6 +496,34 @@ int cn_na2d_bwd_bf16(const void* qkv, long ldq, const void* dout, long ldo, cons
 int cn_dropout_bf16(const void* x, long ldx, void* y, long ldy, int B, int C, int HW, float p, unsigned long long seed,
                     const unsigned long long* step, int channelwise, int accumulate, void* stream);
 
+/* SpatialChannelAttention on bf16 NHWC (nn/modules/attention.py:12-126, applied at convolution.py:388-393): the twins of
+ * cn_sca_pool_* / cn_sca_apply_*_f32 around the unchanged fp32 cn_sca_mlp_*_f32 and the fp32 3x3 conv on pooled.
+ *   pool fwd: avg / mx / idx fp32 [B][C] = mean / max / first argmax over the L pixels (nn.AdaptiveAvg/MaxPool2d(1));
+ *             pooled fp32 [B][2][L] = mean / max over the C channels (einops.reduce 'mean' / 'max').
+ *   pool bwd: dx (+)= davg/L + [l == idx] dmx + dpooled[0]/C + dpooled[1] split evenly over the tied channel maxima
+ *             (torch.amax), recounted from x.
+ *   apply:    y = out * (1 + gamma * 0.5 * (ca + sigmoid(sconv))); sconv = the pre-sigmoid conv output [B][1][L].
+ *             bwd: dout (nullable, + accumulate); dca [B][C], dsconv [B][1][L] overwritten; dgamma ACCUMULATED.
+ * C % 8 == 0, C <= 1024. ws: cn_sca_workspace_floats_bf16(B, C, L) floats (per-block partial sums, fixed order). */
+long cn_sca_workspace_floats_bf16(int B, int C, int L);
+int cn_sca_pool_fwd_bf16(const void* x, long ldx, int B, int C, int L, float* avg, float* mx, int* idx, float* pooled,
+                         float* ws, long ws_floats, void* stream);
+int cn_sca_pool_bwd_bf16(const void* x, long ldx, const float* davg, const float* dmx, const int* idx,
+                         const float* dpooled, void* dx, long lddx, int B, int C, int L, int accumulate, void* stream);
+int cn_sca_apply_fwd_bf16(const void* out, long ldo, const float* ca, const float* sconv, const float* gamma, void* y,
+                          long ldy, int B, int C, int L, void* stream);
+int cn_sca_apply_bwd_bf16(const void* dy, long ldd, const void* out, long ldo, const float* ca, const float* sconv,
+                          const float* gamma, void* dout, long lddo, int accumulate_dout, float* dca, float* dsconv,
+                          float* dgamma, float* ws, long ws_floats, int B, int C, int L, void* stream);
+
+/* F.adaptive_max_pool2d on bf16 NHWC (pool_by_max=True: convolution.py:499-503), windows as cn_adaptive_maxpool_*_f32.
+ * idx int32 [B*Ho*Wo][C] (nullable without backward): flat input pixel of the first maximum in window order (a NaN
+ * wins, as ATen). Backward: a gather, deterministic. */
+int cn_adaptive_maxpool_fwd_bf16(const void* x, long ldx, void* y, long ldy, int* idx, int B, int C, int Hi, int Wi,
+                                 int Ho, int Wo, void* stream);
+int cn_adaptive_maxpool_bwd_bf16(const void* dy, long ldd, const int* idx, void* dx, long lddx, int B, int C, int Hi,
+                                 int Wi, int Ho, int Wo, int accumulate, void* stream);
+
 /* ---- PreTimeReduction (models/nunet.py:18-105) fused: both Conv3d stacks (k = 3, 5: Conv3d(C->C,(k,1,1)) -> BatchNorm3d
  * -> SiLU -> Conv3d(C->Cout,(T-k+1,1,1)) -> BatchNorm2d -> SiLU), their sum and the LayerNorm over Cout, recomputed from
  * x [B][C*T][HW] (batch stride xbs) in every pass: training forward = 3 launches (+ 1 weight transpose), backward = 3,
