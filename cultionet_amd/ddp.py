@@ -25,27 +25,42 @@ from . import engine as _engine
 
 
 def plan_buckets(offsets: T.Sequence[int], sizes: T.Sequence[int], ready_node: T.Sequence[int], total: int,
-                 bucket_elems: int) -> T.List[T.Tuple[int, int, int]]:
+                 bucket_elems: int, trainable: T.Optional[T.Sequence[bool]] = None) -> T.List[T.Tuple[int, int, int]]:
     """Cut [0, total) into contiguous buckets walking parameters from last to first.
 
     Returns [(lo, hi, ready)] where ``ready`` is the tape node index after which the whole bucket is final
     (the minimum forward node index over its parameters; backward visits nodes in decreasing order).
+    ``trainable`` (one flag per parameter): frozen parameters have no gradient and are never communicated -- the
+    buckets then cover the runs of adjacent trainable parameters only (each run from its first parameter's offset to
+    the padded end of its last), cut the same way.
     """
     order = sorted(range(len(offsets)), key=lambda i: offsets[i], reverse=True)
+    if trainable is None or all(trainable):
+        runs = [(0, total, order)]
+    else:
+        runs = []  # (lo, hi, parameters from last to first) of every run of adjacent trainable parameters
+        for n, i in enumerate(order):
+            if not trainable[i]:
+                continue
+            if n > 0 and trainable[order[n - 1]]:  # continues the run of the parameter after it
+                runs[-1][2].append(i)
+            else:  # a run ends where the next parameter's slice begins
+                runs.append((0, offsets[order[n - 1]] if n > 0 else total, [i]))
+        runs = [(offsets[ps[-1]], hi, ps) for _, hi, ps in runs]
     buckets: T.List[T.Tuple[int, int, int]] = []
-    hi = total
-    cur_ready = None
-    for n, i in enumerate(order):
-        r = ready_node[i]
-        cur_ready = r if cur_ready is None else min(cur_ready, r)
-        lo = offsets[i]
-        last = n == len(order) - 1
-        if hi - lo >= bucket_elems or last:
-            if last:
-                lo = 0
-            buckets.append((lo, hi, cur_ready))
-            hi = lo
-            cur_ready = None
+    for run_lo, hi, ps in runs:
+        cur_ready = None
+        for n, i in enumerate(ps):
+            r = ready_node[i]
+            cur_ready = r if cur_ready is None else min(cur_ready, r)
+            lo = offsets[i]
+            last = n == len(ps) - 1
+            if hi - lo >= bucket_elems or last:
+                if last:
+                    lo = run_lo
+                buckets.append((lo, hi, cur_ready))
+                hi = lo
+                cur_ready = None
     return buckets
 
 
@@ -82,11 +97,13 @@ class GradientAllReduce:
             broadcast_module_state(store, module, group=self.group, src=0)
 
     def _get_plan(self, tape, store):
-        key = (len(tape.nodes), store.numel)
+        tm = getattr(store, "trainable_mask", None)  # (None: a store without frozen parameters)
+        mask = tm() if tm is not None else None
+        key = (len(tape.nodes), store.numel, mask)
         if self._plan is None or self._plan_key != key:
             sizes = [p.numel() for p in store.params]
             ready = [tape.marks.get(o, 0) for o in store.offsets]
-            self._plan = plan_buckets(store.offsets, sizes, ready, store.numel, self.bucket_elems)
+            self._plan = plan_buckets(store.offsets, sizes, ready, store.numel, self.bucket_elems, mask)
             self._plan_key = key
         return self._plan
 

@@ -141,6 +141,19 @@ class Var:
         return self.t.shape
 
 
+def _tr(p: T.Optional[torch.Tensor]) -> bool:
+    """Does parameter ``p`` get a gradient (exists and ``requires_grad``)? Frozen parameters get none."""
+    return p is not None and p.requires_grad
+
+
+def _req(tape: "Tape", vs: T.Sequence[T.Optional[Var]] = (), params: T.Sequence[T.Optional[torch.Tensor]] = ()) -> bool:
+    """Does an op's output need a gradient: the tape is on and an input or one of the op's own parameters needs one.
+    An op whose output needs none records no tape node."""
+    if not tape.enabled:
+        return False
+    return any(v is not None and v.req for v in vs) or any(p is not None and p.requires_grad for p in params)
+
+
 class Tape:
     def __init__(self, enabled: bool):
         self.enabled = enabled
@@ -157,7 +170,8 @@ class Tape:
                 base = current_store()._base
                 idx = len(self.nodes) - 1
                 for p in params:
-                    if p is not None:  # a gradient is final once backward has passed the FIRST node that used it
+                    # frozen parameters get no gradient: only trainable offsets are marked (the bucket plan relies on it)
+                    if p is not None and p.requires_grad:  # a gradient is final once backward has passed the FIRST node that used it
                         k = (p.data_ptr() - base) // 4
                         self.marks[k] = min(self.marks.get(k, idx), idx)
 
@@ -666,6 +680,9 @@ def give_grad(v: Var, g: torch.Tensor) -> None:
 # flat parameter store
 # ---------------------------------------------------------------------------
 
+_SUB_TABLES_KEPT = 8  # pack tables of partial repacks (ParamStore.repack_all) cached per set of changed parameters
+
+
 class ParamStore:
     """All parameters of a module in one flat fp32 buffer; gradients likewise.
 
@@ -708,6 +725,10 @@ class ParamStore:
         self._pack_table: T.Optional[torch.Tensor] = None
         self._packs16: T.List[T.Tuple] = []    # the same for the bf16 MFMA-fragment copies
         self._pack_table16: T.Optional[torch.Tensor] = None
+        # parameters written since the last repack: None = any of them (a full repack), else a set of indices (the
+        # optimizer step of a model with frozen parameters writes the trainable ones only)
+        self._dirty: T.Optional[T.FrozenSet[int]] = None
+        self._sub_tables: T.Dict[T.Any, T.Tuple[T.Optional[torch.Tensor], int, T.Optional[torch.Tensor], int]] = {}
 
     @staticmethod
     def _with_contiguous_groups(module: torch.nn.Module, params: T.List[torch.nn.Parameter]) -> T.List[torch.nn.Parameter]:
@@ -760,8 +781,18 @@ class ParamStore:
     def zero_grad(self) -> None:
         _lib.call("cn_fill_f32", self.flat_grad.data_ptr(), self.numel, 0.0, _stream())
 
-    def bump(self) -> None:
+    def bump(self, changed: T.Optional[T.Sequence[bool]] = None) -> None:
+        """The parameter values changed. ``changed``: mask (one flag per parameter, store order) of the parameters
+        that did; None = any may have. Packed copies of the others are not refreshed."""
         self.version += 1
+        if changed is None:
+            self._dirty = None
+        elif self._dirty is not None:
+            self._dirty = self._dirty | frozenset(i for i, c in enumerate(changed) if c)
+
+    def trainable_mask(self) -> T.Tuple[bool, ...]:
+        """``requires_grad`` of every parameter in store order: the trainable set (frozen parameters get no gradient)."""
+        return tuple(p.requires_grad for p in self.params)
 
     def _signature(self) -> int:
         """Sum of the parameters' torch version counters: moves whenever anything outside the engine writes a
@@ -787,8 +818,58 @@ class ParamStore:
         self._packs16.append((pw, attr, dst, w.data_ptr(), T_, K, N, sk, sn, st))
         self._pack_table16 = None
 
+    def _sub_table(self, packs: T.List[T.Tuple], dirty: T.FrozenSet[int], fmt: str) -> T.Tuple[T.Optional[torch.Tensor], int]:
+        """(device table, count) of the pack records whose source weight overlaps a parameter in ``dirty``."""
+        import bisect
+        import struct
+
+        buf, cnt = bytearray(), 0
+        for (_pw, _attr, dst, wptr, T_, K, N, sk, sn, st) in packs:
+            lo = (wptr - self._base) // 4
+            hi = lo + T_ * K * N  # (the source is a dense weight tensor, or adjacent ones: a declared group)
+            i = max(bisect.bisect_right(self.offsets, lo) - 1, 0)
+            hit = False
+            while i < len(self.offsets) and self.offsets[i] < hi:
+                if i in dirty:
+                    hit = True
+                    break
+                i += 1
+            if not hit:
+                continue
+            if fmt == "f32":
+                buf += struct.pack("<QQiiiiiiqqq", wptr, dst.data_ptr(), T_, K, N, _lib.query("cn_conv_kpad", K),
+                                   _lib.query("cn_conv_npad", N), 0, sk, sn, st)
+            else:
+                buf += struct.pack("<QQiiiiiiqqqQ", wptr, dst.data_ptr(), T_, K, N, (K + 15) // 16, (N + 31) // 32, 0,
+                                   sk, sn, st, 0)
+            cnt += 1
+        if not cnt:
+            return None, 0
+        return torch.frombuffer(buf, dtype=torch.uint8).clone().to(self.flat.device), cnt
+
     def repack_all(self) -> None:
-        """Refresh every registered packed weight copy with ONE launch per precision (after the parameters changed)."""
+        """Refresh the registered packed weight copies with ONE launch per precision (after the parameters changed):
+        every copy, or -- when only known parameters changed (bump with a mask) -- the copies of those."""
+        dirty = self._dirty
+        self._dirty = frozenset()
+        if dirty is not None:
+            key = (dirty, len(self._packs), len(self._packs16))
+            sub = self._sub_tables.pop(key, None)
+            if sub is None:
+                sub = self._sub_table(self._packs, dirty, "f32") + self._sub_table(self._packs16, dirty, "bf16")
+            self._sub_tables[key] = sub  # most recently used last; a few trainable sets are kept (gradual unfreezing)
+            while len(self._sub_tables) > _SUB_TABLES_KEPT:
+                self._sub_tables.pop(next(iter(self._sub_tables)))
+            t32, n32, t16, n16 = sub
+            for sink in getattr(_state, "alloc_sinks", None) or ():  # a plan being recorded bakes the table pointers in:
+                sink.extend(t for t in (t32, t16) if t is not None)  # it keeps the tables alive past their eviction
+            if n16:
+                _lib.call("cn_pack_weights_batched_bf16", t16.data_ptr(), n16, _stream())
+            if n32:
+                _lib.call("cn_pack_weights_batched_f32", t32.data_ptr(), n32, _stream())
+            for (pw, *_rest) in self._packs16 + self._packs:
+                pw.version = self.version
+            return
         if self._packs16:
             if self._pack_table16 is None:
                 import struct
@@ -816,6 +897,40 @@ class ParamStore:
         _lib.call("cn_pack_weights_batched_f32", self._pack_table.data_ptr(), len(self._packs), _stream())
         for (pw, _attr, _dst, *_rest) in self._packs:
             pw.version = self.version
+
+
+SEG_CHUNK = 4096  # elements per chunk of the segmented optimizer kernels (CN_SEG_CHUNK in csrc/cn_optim.hip)
+
+
+def trainable_segments(offsets: T.Sequence[int], sizes: T.Sequence[int], trainable: T.Sequence[bool],
+                       steps: T.Sequence[int]) -> T.List[T.Tuple[int, int, int]]:
+    """The runs of trainable parameters in the flat buffer as [(offset, length, step)]: adjacent trainable parameters
+    with equal AdamW step counts merge (across the 16-byte padding between their slices, which is zero in every
+    buffer); a frozen parameter or a different step count starts a new run."""
+    segs: T.List[T.List[int]] = []
+    end = None  # padded end of the previous parameter, when it is trainable
+    for i in sorted(range(len(offsets)), key=lambda k: offsets[k]):
+        o, n = int(offsets[i]), int(sizes[i])
+        if not trainable[i] or n <= 0:
+            end = None
+            continue
+        if end is not None and end == o and segs[-1][2] == int(steps[i]):
+            segs[-1][1] = o + n - segs[-1][0]
+        else:
+            segs.append([o, n, int(steps[i])])
+        end = o + (n + 3) // 4 * 4
+    return [tuple(x) for x in segs]
+
+
+def segment_table(segs: T.Sequence[T.Tuple[int, int, int]]) -> T.Tuple[bytes, int]:
+    """The 24-byte CnSeg records of ``segs`` for cn_*_seg_f32 and the total chunk count."""
+    import struct
+
+    buf, chunk = bytearray(), 0
+    for o, n, st in segs:
+        buf += struct.pack("<qqii", o, n, st, chunk)
+        chunk += (n + SEG_CHUNK - 1) // SEG_CHUNK
+    return bytes(buf), chunk
 
 
 # Launch plans (cultionet_amd/replay.py) bake the raw pointers of the process-wide scratch buffers below into their
@@ -1215,23 +1330,26 @@ def conv2d(x: Var, mod, stride: int = 1, padding: int = 0, dilation: int = 1, ou
     _lib.call("cn_conv2d_fwd_f32", xt.data_ptr(), bstride(xt), pw.fwd.data_ptr(),
               bias.data_ptr() if bias is not None else None, y.data_ptr(), bstride(y), B, Cin, H, W, Cout, KH, KW,
               stride, padding, dilation, 0, _stream())
-    yv = Var(y, tape.enabled)
-    if tape.enabled:
+    yv = Var(y, _req(tape, (x,), (w, bias)))
+    if yv.req:
         store = current_store()
+        gw, gb = _tr(w), _tr(bias)
 
         def bwd():
             dy = yv.grad
             if dy is None:
                 return
-            with side_stream(xt, dy):
-                s = _stream()
-                wsp, wsn = _pad_ws(xt, dy)
-                _lib.call("cn_conv2d_bwd_weight_f32", xt.data_ptr(), bstride(xt), dy.data_ptr(), bstride(dy),
-                          store.grad_of(w).data_ptr(), B, Cin, H, W, Cout, KH, KW, stride, padding, dilation, wsp, wsn,
-                          s)
-                if bias is not None:
-                    _lib.call("cn_channel_sum_f32", dy.data_ptr(), bstride(dy), B, Cout, Ho * Wo,
-                              store.grad_of(bias).data_ptr(), 1, s)
+            if gw or gb:
+                with side_stream(xt, dy):
+                    s = _stream()
+                    if gw:
+                        wsp, wsn = _pad_ws(xt, dy)
+                        _lib.call("cn_conv2d_bwd_weight_f32", xt.data_ptr(), bstride(xt), dy.data_ptr(), bstride(dy),
+                                  store.grad_of(w).data_ptr(), B, Cin, H, W, Cout, KH, KW, stride, padding, dilation,
+                                  wsp, wsn, s)
+                    if gb:
+                        _lib.call("cn_channel_sum_f32", dy.data_ptr(), bstride(dy), B, Cout, Ho * Wo,
+                                  store.grad_of(bias).data_ptr(), 1, s)
             if x.req:
                 dx, acc = grad_buffer(x)
                 _lib.call("cn_conv2d_bwd_data_f32", dy.data_ptr(), bstride(dy), pw.bwd.data_ptr(), dx.data_ptr(),
@@ -1275,23 +1393,27 @@ def conv2d_group(xs: T.Sequence[Var], mods: T.Sequence, paddings: T.Sequence[int
               tab([p.fwd.data_ptr() for p in pws]), tab([b.data_ptr() for b in biases]) if has_bias else None,
               tab([y.data_ptr() for y in ys]), bstride(ys[0]), B, Cin, H, W, Cout, KH, KW, stride, pads_c, dils_c, 0,
               _stream())
-    yvs = [Var(y, tape.enabled) for y in ys]
-    if tape.enabled:
+    req = _req(tape, xs, [m.weight for m in mods] + biases)
+    yvs = [Var(y, req) for y in ys]
+    if req:
         store = current_store()
+        # one flag for the group (the grouped weight-gradient launch writes every member; a frozen member's slice is
+        # written and never read)
+        gw = any(_tr(m.weight) for m in mods) or any(_tr(b) for b in biases)
 
         def bwd():
             live = [i for i in range(G) if yvs[i].grad is not None]
             grouped_w = (len(live) == G and len(set(paddings)) == 1 and len(set(dilations)) == 1
                          and len({bstride(yvs[i].grad) for i in live}) == 1)
-            with side_stream(*(list(xts) + [yvs[i].grad for i in live])):
+            with side_stream(*(list(xts) + [yvs[i].grad for i in live])) if gw else contextlib.nullcontext():
                 s = _stream()
-                if grouped_w:  # one launch for the G weight gradients
+                if grouped_w and gw:  # one launch for the G weight gradients
                     wsp, wsn = _pad_ws(*([xts[i] for i in range(G)] + [yvs[i].grad for i in range(G)]))
                     _lib.call("cn_conv2d_bwd_weight_grouped_f32", G, tab([t.data_ptr() for t in xts]), bstride(xts[0]),
                               tab([yvs[i].grad.data_ptr() for i in range(G)]), bstride(yvs[0].grad),
                               tab([store.grad_of(m.weight).data_ptr() for m in mods]), B, Cin, H, W, Cout, KH, KW,
                               stride, paddings[0], dilations[0], wsp, wsn, s)
-                for i in live:
+                for i in (live if gw else ()):
                     dy, m, xt = yvs[i].grad, mods[i], xts[i]
                     if grouped_w:
                         if has_bias:
@@ -1368,25 +1490,30 @@ def _conv_transpose2d_taps(x: Var, mod, stride: int, padding: int, size, out: T.
     _lib.call("cn_convt_taps_fwd_f32", P.data_ptr(), bstride(P), bias.data_ptr() if bias is not None else None,
               z.data_ptr(), bstride(z), B, Cout, H, W, K, stride, padding, Ho, Wo, _stream())
     del P  # (not needed by the backward pass)
-    zv = Var(z, tape.enabled)
-    if tape.enabled:
+    zv = Var(z, _req(tape, (x,), (w, bias)))
+    if zv.req:
         store = current_store()
+        gw, gb = _tr(w), _tr(bias)
 
         def bwd():
             dz = zv.grad
             if dz is None:
                 return
-            dP = _new((B, Cout * KK, H, W), xt)
-            _lib.call("cn_convt_taps_bwd_f32", dz.data_ptr(), bstride(dz), dP.data_ptr(), bstride(dP), B, Cout, H, W, K,
-                      stride, padding, Ho, Wo, _stream())
-            with side_stream(xt, dP, dz):
-                s = _stream()
-                wsp, wsn = _pad_ws(xt, dP)
-                _lib.call("cn_conv_transpose2d_bwd_weight_f32", xt.data_ptr(), bstride(xt), dP.data_ptr(), bstride(dP),
-                          store.grad_of(w).data_ptr(), B, Cin, H, W, Cout * KK, 1, 1, 1, 0, 0, wsp, wsn, s)
-                if bias is not None:  # the resize weights of every output pixel sum to one: sum of dz
-                    _lib.call("cn_channel_sum_f32", dz.data_ptr(), bstride(dz), B, Cout, Ho * Wo,
-                              store.grad_of(bias).data_ptr(), 1, s)
+            if gw or x.req:  # (a bias gradient alone needs only dz)
+                dP = _new((B, Cout * KK, H, W), xt)
+                _lib.call("cn_convt_taps_bwd_f32", dz.data_ptr(), bstride(dz), dP.data_ptr(), bstride(dP), B, Cout, H,
+                          W, K, stride, padding, Ho, Wo, _stream())
+            if gw or gb:
+                with side_stream(xt, dP, dz) if gw else side_stream(xt, dz):
+                    s = _stream()
+                    if gw:
+                        wsp, wsn = _pad_ws(xt, dP)
+                        _lib.call("cn_conv_transpose2d_bwd_weight_f32", xt.data_ptr(), bstride(xt), dP.data_ptr(),
+                                  bstride(dP), store.grad_of(w).data_ptr(), B, Cin, H, W, Cout * KK, 1, 1, 1, 0, 0, wsp,
+                                  wsn, s)
+                    if gb:  # the resize weights of every output pixel sum to one: sum of dz
+                        _lib.call("cn_channel_sum_f32", dz.data_ptr(), bstride(dz), B, Cout, Ho * Wo,
+                                  store.grad_of(bias).data_ptr(), 1, s)
             if x.req:
                 dx, acc = grad_buffer(x)
                 _lib.call("cn_conv_transpose2d_bwd_data_f32", dP.data_ptr(), bstride(dP), pw.bwd.data_ptr(),
@@ -1447,22 +1574,26 @@ def _conv_transpose2d_f32(x: Var, mod, stride: int, padding: int, op: int) -> Va
     _lib.call("cn_conv_transpose2d_fwd_f32", xt.data_ptr(), bstride(xt), pw.fwd.data_ptr(),
               bias.data_ptr() if bias is not None else None, y.data_ptr(), bstride(y), B, Cin, H, W, Cout, KH, KW,
               stride, padding, op, 0, _stream())
-    yv = Var(y, tape.enabled)
-    if tape.enabled:
+    yv = Var(y, _req(tape, (x,), (w, bias)))
+    if yv.req:
         store = current_store()
+        gw, gb = _tr(w), _tr(bias)
 
         def bwd():
             dy = yv.grad
             if dy is None:
                 return
-            with side_stream(xt, dy):
-                s = _stream()
-                wsp, wsn = _pad_ws(xt, dy)
-                _lib.call("cn_conv_transpose2d_bwd_weight_f32", xt.data_ptr(), bstride(xt), dy.data_ptr(), bstride(dy),
-                          store.grad_of(w).data_ptr(), B, Cin, H, W, Cout, KH, KW, stride, padding, op, wsp, wsn, s)
-                if bias is not None:  # (the padding of dy is zero: the resize adjoint writes it)
-                    _lib.call("cn_channel_sum_f32", dy.data_ptr(), bstride(dy), B, Cout, Hs * Ws,
-                              store.grad_of(bias).data_ptr(), 1, s)
+            if gw or gb:
+                with side_stream(xt, dy):
+                    s = _stream()
+                    if gw:
+                        wsp, wsn = _pad_ws(xt, dy)
+                        _lib.call("cn_conv_transpose2d_bwd_weight_f32", xt.data_ptr(), bstride(xt), dy.data_ptr(),
+                                  bstride(dy), store.grad_of(w).data_ptr(), B, Cin, H, W, Cout, KH, KW, stride, padding,
+                                  op, wsp, wsn, s)
+                    if gb:  # (the padding of dy is zero: the resize adjoint writes it)
+                        _lib.call("cn_channel_sum_f32", dy.data_ptr(), bstride(dy), B, Cout, Hs * Ws,
+                                  store.grad_of(bias).data_ptr(), 1, s)
             if x.req:
                 dx, acc = grad_buffer(x)
                 _lib.call("cn_conv_transpose2d_bwd_data_f32", dy.data_ptr(), bstride(dy), pw.bwd.data_ptr(),
@@ -1500,24 +1631,26 @@ def time_conv(x: Var, mod, tin: int) -> Var:
     y = _new((B, Cout * tout, H, W), xt)
     _lib.call("cn_conv2d_fwd_f32", xt.data_ptr(), bstride(xt), pw.fwd.data_ptr(), None, y.data_ptr(), bstride(y), B,
               CT, H, W, Cout * tout, 1, 1, 1, 0, 1, 0, _stream())
-    yv = Var(y, tape.enabled)
-    if tape.enabled:
+    yv = Var(y, _req(tape, (x,), (w,)))
+    if yv.req:
         store = current_store()
+        gw = _tr(w)
 
         def bwd():
             dy = yv.grad
             if dy is None:
                 return
-            with side_stream(xt, dy):
-                s = _stream()
-                dwexp = _alloc(Cout * tout * CT, torch.float32, xt.device)
-                _lib.call("cn_fill_f32", dwexp.data_ptr(), dwexp.numel(), 0.0, s)
-                _lib.call("cn_conv2d_bwd_weight_f32", xt.data_ptr(), bstride(xt), dy.data_ptr(), bstride(dy),
-                          dwexp.data_ptr(), B, CT, H, W, Cout * tout, 1, 1, 1, 0, 1, None, 0, s)
-                _lib.call("cn_fold_timeconv_grad_f32", dwexp.data_ptr(), store.grad_of(w).data_ptr(), Cout, Cin, tin, k,
-                          s)
-                if _OVERLAP_WGRAD:
-                    dwexp.record_stream(_side_state(xt.device)["stream"])
+            if gw:
+                with side_stream(xt, dy):
+                    s = _stream()
+                    dwexp = _alloc(Cout * tout * CT, torch.float32, xt.device)
+                    _lib.call("cn_fill_f32", dwexp.data_ptr(), dwexp.numel(), 0.0, s)
+                    _lib.call("cn_conv2d_bwd_weight_f32", xt.data_ptr(), bstride(xt), dy.data_ptr(), bstride(dy),
+                              dwexp.data_ptr(), B, CT, H, W, Cout * tout, 1, 1, 1, 0, 1, None, 0, s)
+                    _lib.call("cn_fold_timeconv_grad_f32", dwexp.data_ptr(), store.grad_of(w).data_ptr(), Cout, Cin,
+                              tin, k, s)
+                    if _OVERLAP_WGRAD:
+                        dwexp.record_stream(_side_state(xt.device)["stream"])
             s = _stream()
             if x.req:
                 dx, acc = grad_buffer(x)
@@ -1585,7 +1718,12 @@ def pretime_reduction(x: Var, pre, in_channels: int, in_time: int) -> T.Optional
             bn2[0].momentum != bn2[1].momentum or any(b.running_mean is None for b in bn3 + bn2) or \
             any(b.training != training for b in bn3 + bn2):
         return None
-    with_bwd = 1 if tape.enabled else 0
+    glist = []
+    for b, b3, b2 in zip(br, bn3, bn2):
+        glist += [b.seq[0].weight, b.seq[3].weight, b3.weight, b3.bias, b2.weight, b2.bias]
+    glist += [ln.weight, ln.bias]
+    req = _req(tape, (), glist)  # (the stage has parameter gradients only; a frozen one records nothing)
+    with_bwd = 1 if req else 0
     need = int(_lib.query("cn_pretime_workspace_floats", B, C, Tn, HW, Cout, with_bwd))
     if need < 0:
         return None
@@ -1615,13 +1753,9 @@ def pretime_reduction(x: Var, pre, in_channels: int, in_time: int) -> T.Optional
     ws = _pretime_ws(need, dev)
     _lib.call("cn_pretime_fwd_f32", xt.data_ptr(), bstride(xt), params, stats, y.data_ptr(), ystride, kind, B, C, Tn, HW,
               Cout, 1 if training else 0, bnc, float(ln.eps), ws.data_ptr(), ws.numel(), _stream())
-    yv = Var(y, tape.enabled)
-    if tape.enabled:
+    yv = Var(y, req)
+    if req:
         store = current_store()
-        glist = []
-        for b, b3, b2 in zip(br, bn3, bn2):
-            glist += [b.seq[0].weight, b.seq[3].weight, b3.weight, b3.bias, b2.weight, b2.bias]
-        glist += [ln.weight, ln.bias]
 
         def bwd(stats_t=stats_t):  # (``stats`` points into stats_t: held until the backward has run)
             dy = yv.grad
@@ -1698,11 +1832,11 @@ def bn_act(x: Var, bn, act: int, residual: T.Optional[Var] = None, channels: T.O
               rt.data_ptr() if rt is not None else None, bstride(rt) if rt is not None else 0, y.data_ptr(),
               bstride(y), mean.data_ptr(), rstd.data_ptr(), ws.data_ptr(), B, C, L, 1 if use_batch else 0, float(mom),
               float(bn.eps), act, _stream())
-    req = tape.enabled
-    yv = Var(y, req)
-    if tape.enabled:
+    gamma, beta = bn.weight, bn.bias
+    # frozen gamma / beta with a live input: the fused kernel still writes their slices (never read)
+    yv = Var(y, _req(tape, (x, residual), (gamma, beta)))
+    if yv.req:
         store = current_store()
-        gamma, beta = bn.weight, bn.bias
 
         def bwd():
             dy = yv.grad
@@ -1794,8 +1928,9 @@ def bn_act_group(xs: T.Sequence[Var], bns: T.Sequence, act: int, residual: T.Opt
               (ctypes.c_void_p * len(ys))(*[y.data_ptr() for y in ys]) if not sum_outputs else tab([ys[0].data_ptr()] * G),
               bstride(ys[0]), tab([m.data_ptr() for m in means]), tab([r.data_ptr() for r in rstds]), ws.data_ptr(),
               B, C, L, 1 if use_batch else 0, float(mom), float(bns[0].eps), act, 1 if sum_outputs else 0, _stream())
-    yvs = [Var(y, tape.enabled) for y in ys]
-    if tape.enabled:
+    req = _req(tape, list(xs) + [residual], [bn.weight for bn in bns] + [bn.bias for bn in bns])
+    yvs = [Var(y, req) for y in ys]
+    if req:
         store = current_store()
 
         def bwd():
@@ -1860,8 +1995,8 @@ def layer_norm_c(x: Var, ln, residual: T.Optional[Var] = None, out: T.Optional[t
     _lib.call("cn_layernorm_c_fwd_f32", xt.data_ptr(), bstride(xt), ln.weight.data_ptr(), ln.bias.data_ptr(),
               rt.data_ptr() if rt is not None else None, bstride(rt) if rt is not None else 0, y.data_ptr(),
               bstride(y), mu.data_ptr(), rstd.data_ptr(), B, C, L, float(ln.eps), _stream())
-    yv = Var(y, tape.enabled)
-    if tape.enabled:
+    yv = Var(y, _req(tape, (x, residual), (ln.weight, ln.bias)))
+    if yv.req:
         store = current_store()
 
         def bwd():
@@ -1898,8 +2033,8 @@ def na2d(qkv: Var, heads: int, kernel_size: int, dilation: int, attn_drop: float
     step_fwd = _rng["step"]
     _lib.call("cn_na2d_fwd_f32", qt.data_ptr(), bstride(qt), out.data_ptr(), bstride(out), attn.data_ptr(), B, C,
               heads, H, W, kernel_size, dilation, float(attn_drop), seed, stepw, _stream())
-    ov = Var(out, tape.enabled)
-    if tape.enabled:
+    ov = Var(out, _req(tape, (qkv,)))
+    if ov.req:
 
         def bwd():
             do = ov.grad
@@ -1950,9 +2085,13 @@ def spatial_channel_attention(skip: Var, out: Var, mod) -> Var:
               pooled.data_ptr(), cidx.data_ptr(), s)
     _lib.call("cn_sca_mlp_fwd_f32", avg.data_ptr(), mx.data_ptr(), w1a.data_ptr(), w2a.data_ptr(), w1m.data_ptr(),
               w2m.data_ptr(), hpre_a.data_ptr(), hpre_m.data_ptr(), ca.data_ptr(), B, C, Ch, s)
-    pv = Var(pooled, tape.enabled)
+    # one flag for the whole block: its fused kernels write every parameter gradient of the block together (frozen
+    # slices included, never read) whenever a gradient has to pass through it
+    req = _req(tape, (skip, out), (w1a, w2a, w1m, w2m, gamma, mod.spatial_attention.conv.weight,
+                                   mod.spatial_attention.conv.bias))
+    pv = Var(pooled, req)
     shared = {}  # d ca handed from the apply node to the pooling node
-    if tape.enabled:
+    if req:
         store = current_store()
 
         def bwd_pool():  # recorded first => runs last: after the apply node and the 3x3 conv's backward
@@ -1981,8 +2120,8 @@ def spatial_channel_attention(skip: Var, out: Var, mod) -> Var:
     y = _new(ot.shape, ot)
     _lib.call("cn_sca_apply_fwd_f32", ot.data_ptr(), bstride(ot), ca.data_ptr(), sconv.t.data_ptr(), gamma.data_ptr(),
               y.data_ptr(), bstride(y), B, C, L, s)
-    yv = Var(y, tape.enabled)
-    if tape.enabled:
+    yv = Var(y, req)
+    if req:
 
         def bwd_apply():
             dy = yv.grad
@@ -2065,8 +2204,8 @@ def join_channels(parts: T.Sequence[Var], buf: torch.Tensor) -> Var:
                 (not is16(buf) and buf.shape[0] > 1 and bstride(p.t) != bstride(buf)):
             raise RuntimeError("join_channels: parts must be the channel slices of buf, in order")
         c0 += c
-    yv = Var(buf, tape.enabled)
-    if tape.enabled:
+    yv = Var(buf, _req(tape, parts))
+    if yv.req:
 
         def bwd():
             dy = yv.grad
@@ -2111,20 +2250,22 @@ def thin_conv3x3(x: Var, mods: T.Sequence, grouped: bool, dilation: int = 1,
     wpk = _new((Cin * 84,), xt) if (n, CP, g) == (3, 3, 0) and Cin >= 16 else None  # per-call packed weights
     _lib.call("cn_thin_conv3x3_fwd_f32", xt.data_ptr(), bstride(xt), wtab, btab, y.data_ptr(), bstride(y), B, Cin, H, W,
               n, CP, g, dilation, wpk.data_ptr() if wpk is not None else None, _stream())
-    yv = Var(y, tape.enabled)
-    if tape.enabled:
+    yv = Var(y, _req(tape, (x,), ws + bs))
+    if yv.req:
         store = current_store()
+        gw, gb = any(_tr(w) for w in ws), any(_tr(b) for b in bs)  # (one launch writes every weight set)
 
         def bwd():
             dy = yv.grad
             if dy is None:
                 return
-            with side_stream(xt, dy):
+            with side_stream(xt, dy) if (gw or gb) else contextlib.nullcontext():
                 s = _stream()
-                dwtab = _ptr_table([store.grad_of(w).data_ptr() for w in ws])
-                _lib.call("cn_thin_conv3x3_bwd_weight_f32", xt.data_ptr(), bstride(xt), dy.data_ptr(), bstride(dy),
-                          dwtab, B, Cin, H, W, n, CP, g, dilation, s)
-                if has_bias:
+                if gw:
+                    dwtab = _ptr_table([store.grad_of(w).data_ptr() for w in ws])
+                    _lib.call("cn_thin_conv3x3_bwd_weight_f32", xt.data_ptr(), bstride(xt), dy.data_ptr(), bstride(dy),
+                              dwtab, B, Cin, H, W, n, CP, g, dilation, s)
+                if has_bias and gb:
                     for i, b in enumerate(bs):
                         dyi = dy[:, i * CP:(i + 1) * CP]
                         _lib.call("cn_channel_sum_f32", dyi.data_ptr(), bstride(dy), B, CP, H * W,
@@ -2166,8 +2307,8 @@ def cat_channels(parts: T.Sequence[Var], buf: T.Optional[torch.Tensor] = None) -
             _lib.call("cn_copy_f32", p.t.data_ptr(), bstride(p.t), dst.data_ptr(), bstride(y), B, c * H * W, 0,
                       _stream())
         off += c
-    yv = Var(y, tape.enabled)
-    if tape.enabled:
+    yv = Var(y, _req(tape, parts))
+    if yv.req:
 
         def bwd():
             dy = yv.grad
@@ -2196,8 +2337,8 @@ def add(a: Var, b: Var) -> Var:
     else:
         _lib.call("cn_add_f32", at.data_ptr(), bstride(at), bt.data_ptr(), bstride(bt), y.data_ptr(), bstride(y), B, n,
                   _stream())
-    yv = Var(y, tape.enabled)
-    if tape.enabled:
+    yv = Var(y, _req(tape, (a, b)))
+    if yv.req:
 
         def bwd():
             dy = yv.grad
@@ -2241,8 +2382,9 @@ def final_combine(ha: Var, hb: Var, hc: Var, params: T.Sequence[torch.nn.Paramet
     dist, edge, crop = (_new((B, 1, H, W), a) for _ in range(3))
     _lib.call("cn_final_combine_fwd_f32", a.data_ptr(), b.data_ptr(), c.data_ptr(), ptab, dist.data_ptr(),
               edge.data_ptr(), crop.data_ptr(), B, HW, float(smooth), _stream())
-    outs = tuple(Var(t, tape.enabled) for t in (dist, edge, crop))
-    if tape.enabled:
+    req = _req(tape, (ha, hb, hc), params)
+    outs = tuple(Var(t, req) for t in (dist, edge, crop))
+    if req:
         store = current_store()
 
         def bwd():
@@ -2692,24 +2834,27 @@ def _conv2d_bf16(x: Var, mod, stride: int, padding: int, dilation: int, out: T.O
         _lib.call("cn_conv2d_fwd_bf16", xt.data_ptr(), ld(xt), pw.fwd16.data_ptr(),
                   bias.data_ptr() if bias is not None else None, y.data_ptr(), ld(y), 0, B, Cin, H, W, Cout, KH, KW,
                   stride, padding, dilation, 0, 0, stats.data_ptr() if stats is not None else None, _stream())
-    yv = Var(y, tape.enabled)
+    yv = Var(y, _req(tape, (x,), (w, bias)))
     yv.stats = stats
     yv.bnfin = bnfin or None
-    if tape.enabled:
+    if yv.req:
         store = current_store()
+        gw, gb = _tr(w), _tr(bias)
 
         def bwd():
             dy = yv.grad
             if dy is None:
                 return
-            with side_stream(xt, dy):
+            with side_stream(xt, dy) if (gw or gb) else contextlib.nullcontext():
                 s = _stream()
-                need = _lib.query("cn_bwgrad_workspace_floats", B, Cin, H, W, Cout, KH, KW, stride, padding, dilation, 0)
-                wsp, wsn = _ws16(need, xt.device)
-                _lib.call("cn_conv2d_bwd_weight_bf16", xt.data_ptr(), ld(xt), dy.data_ptr(), ld(dy),
-                          store.grad_of(w).data_ptr(), B, Cin, H, W, Cout, KH, KW, stride, padding, dilation, wsp, wsn,
-                          s)
-                if bias is not None:
+                if gw:
+                    need = _lib.query("cn_bwgrad_workspace_floats", B, Cin, H, W, Cout, KH, KW, stride, padding,
+                                      dilation, 0)
+                    wsp, wsn = _ws16(need, xt.device)
+                    _lib.call("cn_conv2d_bwd_weight_bf16", xt.data_ptr(), ld(xt), dy.data_ptr(), ld(dy),
+                              store.grad_of(w).data_ptr(), B, Cin, H, W, Cout, KH, KW, stride, padding, dilation, wsp,
+                              wsn, s)
+                if gb:
                     _lib.call("cn_channel_sum_bf16", dy.data_ptr(), ld(dy), B * Ho * Wo, Cout,
                               store.grad_of(bias).data_ptr(), 1, _bn_ws16(Cout, xt.device, "side"), s)
             if x.req:
@@ -2767,29 +2912,37 @@ def _conv2d_group_bf16(xs: T.Sequence[Var], mods: T.Sequence, paddings: T.Sequen
                   tab([p.fwd16.data_ptr() for p in pws]), tab([b.data_ptr() for b in biases]) if has_bias else None,
                   tab([y.data_ptr() for y in ys]), ld(ys[0]), B, Cin, H, W, Cout, KH, KW, stride, pads_c, dils_c, 0,
                   tab([t.data_ptr() for t in stats]) if stats is not None else None, _stream())
-    yvs = [Var(y, tape.enabled) for y in ys]
+    req = _req(tape, xs, [m.weight for m in mods] + biases)
+    yvs = [Var(y, req) for y in ys]
     for i, v in enumerate(yvs):
         v.stats = stats[i] if stats is not None else None
         v.bnfin = bnfin[i] if bnfin else None
-    if tape.enabled:
+    if req:
         store = current_store()
         shared_in = any(xs[i] is xs[j] for i in range(G) for j in range(i))
+        gws = [_tr(m.weight) for m in mods]
+        gbs = [_tr(b) for b in biases]
 
         def bwd():
             live = [i for i in range(G) if yvs[i].grad is not None]
             if not live:
                 return
-            with side_stream(*(list(xts) + [yvs[i].grad for i in live])):
+            wlive = [i for i in live if gws[i] or gbs[i]]
+            with side_stream(*(list(xts) + [yvs[i].grad for i in live])) if wlive else contextlib.nullcontext():
                 s = _stream()
-                for i in live:
+                for i in wlive:
                     dy, m = yvs[i].grad, mods[i]
+                    if not gws[i]:
+                        _lib.call("cn_channel_sum_bf16", dy.data_ptr(), ld(dy), B * Ho * Wo, Cout,
+                                  store.grad_of(m.bias).data_ptr(), 1, _bn_ws16(Cout, xts[i].device, "side"), s)
+                        continue
                     need = _lib.query("cn_bwgrad_workspace_floats", B, Cin, H, W, Cout, KH, KW, stride, paddings[i],
                                       dilations[i], 0)
                     wsp, wsn = _ws16(need, xts[i].device)
                     _lib.call("cn_conv2d_bwd_weight_bf16", xts[i].data_ptr(), ld(xts[i]), dy.data_ptr(), ld(dy),
                               store.grad_of(m.weight).data_ptr(), B, Cin, H, W, Cout, KH, KW, stride, paddings[i],
                               dilations[i], wsp, wsn, s)
-                    if has_bias:
+                    if has_bias and gbs[i]:
                         _lib.call("cn_channel_sum_bf16", dy.data_ptr(), ld(dy), B * Ho * Wo, Cout,
                                   store.grad_of(m.bias).data_ptr(), 1, _bn_ws16(Cout, xts[i].device, "side"), s)
             todo = [i for i in live if xs[i].req]
@@ -2896,21 +3049,23 @@ def _conv_transpose2d_bf16(x: Var, mod, stride: int, padding: int) -> Var:
     _lib.call("cn_conv_transpose2d_fwd_bf16", xt.data_ptr(), ld(xt), pw.fwd16.data_ptr(),
               bias.data_ptr() if bias is not None else None, y.data_ptr(), ld(y), B, Cin, H, W, Cout, KH, KW, stride,
               padding, 0, _stream())
-    yv = Var(y, tape.enabled)
-    if tape.enabled:
+    yv = Var(y, _req(tape, (x,), (w, bias)))
+    if yv.req:
         store = current_store()
+        gw, gb = _tr(w), _tr(bias)
 
         def bwd():
             dy = yv.grad
             if dy is None:
                 return
-            with side_stream(xt, dy):
+            with side_stream(xt, dy) if (gw or gb) else contextlib.nullcontext():
                 s = _stream()
-                need = _lib.query("cn_bwgrad_workspace_floats", B, Cin, H, W, Cout, KH, KW, stride, padding, 1, 1)
-                wsp, wsn = _ws16(need, xt.device)
-                _lib.call("cn_conv_transpose2d_bwd_weight_bf16", xt.data_ptr(), ld(xt), dy.data_ptr(), ld(dy),
-                          store.grad_of(w).data_ptr(), B, Cin, H, W, Cout, KH, KW, stride, padding, wsp, wsn, s)
-                if bias is not None:
+                if gw:
+                    need = _lib.query("cn_bwgrad_workspace_floats", B, Cin, H, W, Cout, KH, KW, stride, padding, 1, 1)
+                    wsp, wsn = _ws16(need, xt.device)
+                    _lib.call("cn_conv_transpose2d_bwd_weight_bf16", xt.data_ptr(), ld(xt), dy.data_ptr(), ld(dy),
+                              store.grad_of(w).data_ptr(), B, Cin, H, W, Cout, KH, KW, stride, padding, wsp, wsn, s)
+                if gb:
                     _lib.call("cn_channel_sum_bf16", dy.data_ptr(), ld(dy), B * Ho * Wo, Cout,
                               store.grad_of(bias).data_ptr(), 1, _bn_ws16(Cout, xt.device, "side"), s)
             if x.req:
@@ -2947,10 +3102,11 @@ def _bn_act_bf16(x: Var, bn, act: int, residual: T.Optional[Var], training: bool
               mean.data_ptr(), rstd.data_ptr(), _bn_ws16(C, dev), P, C, 1 if use_batch else 0, _bn_momentum(bn),
               float(bn.eps), act, sums.data_ptr() if sums is not None else None,
               sums.shape[0] if sums is not None else 0, _stream())
-    yv = Var(y, tape.enabled)
-    if tape.enabled:
+    gamma, beta = bn.weight, bn.bias
+    # frozen gamma / beta with a live input: the fused kernel still writes their slices (never read)
+    yv = Var(y, _req(tape, (x, residual), (gamma, beta)))
+    if yv.req:
         store = current_store()
-        gamma, beta = bn.weight, bn.bias
 
         def bwd():
             dy = yv.grad
@@ -3032,8 +3188,9 @@ def _bn_act_group_bf16(xs: T.Sequence[Var], bns: T.Sequence, act: int, residual:
               1 if use_batch else 0, _bn_momentum(bns[0]), float(bns[0].eps), act, 1 if sum_outputs else 0,
               tab([t.data_ptr() for t in sums]) if sums is not None else None,
               -1 if prefin else (sums[0].shape[0] if sums is not None else 0), _stream())
-    yvs = [Var(y, tape.enabled) for y in ys]
-    if tape.enabled:
+    req = _req(tape, list(xs) + [residual], [bn.weight for bn in bns] + [bn.bias for bn in bns])
+    yvs = [Var(y, req) for y in ys]
+    if req:
         store = current_store()
 
         def bwd():
@@ -3082,8 +3239,8 @@ def _layer_norm_c_bf16(x: Var, ln, residual: T.Optional[Var], out: T.Optional[to
     _lib.call("cn_layernorm_c_fwd_bf16", xt.data_ptr(), ld(xt), ln.weight.data_ptr(), ln.bias.data_ptr(),
               rt.data_ptr() if rt is not None else None, ld(rt) if rt is not None else 0, y.data_ptr(), ld(y), P, C,
               float(ln.eps), _stream())
-    yv = Var(y, tape.enabled)
-    if tape.enabled:
+    yv = Var(y, _req(tape, (x, residual), (ln.weight, ln.bias)))
+    if yv.req:
         store = current_store()
 
         def bwd():
@@ -3117,8 +3274,8 @@ def _na2d_bf16(qkv: Var, heads: int, kernel_size: int, dilation: int, attn_drop:
     attn = _alloc((B, heads, kernel_size * kernel_size, H, W), torch.float32, qt.device)
     _lib.call("cn_na2d_fwd_bf16", qt.data_ptr(), ld(qt), out.data_ptr(), ld(out), attn.data_ptr(), B, C, heads, H, W,
               kernel_size, dilation, float(attn_drop), seed, stepw, _stream())
-    ov = Var(out, tape.enabled)
-    if tape.enabled:
+    ov = Var(out, _req(tape, (qkv,)))
+    if ov.req:
 
         def bwd():
             do = ov.grad
@@ -3194,9 +3351,13 @@ def _spatial_channel_attention_bf16(skip: Var, out: Var, mod) -> Var:
               pooled.data_ptr(), ws.data_ptr(), nws, s)
     _lib.call("cn_sca_mlp_fwd_f32", avg.data_ptr(), mx.data_ptr(), w1a.data_ptr(), w2a.data_ptr(), w1m.data_ptr(),
               w2m.data_ptr(), hpre_a.data_ptr(), hpre_m.data_ptr(), ca.data_ptr(), B, C, Ch, s)
-    pv = Var(pooled, tape.enabled)
+    # one flag for the whole block: its fused kernels write every parameter gradient of the block together (frozen
+    # slices included, never read) whenever a gradient has to pass through it
+    req = _req(tape, (skip, out), (w1a, w2a, w1m, w2m, gamma, mod.spatial_attention.conv.weight,
+                                   mod.spatial_attention.conv.bias))
+    pv = Var(pooled, req)
     shared = {}  # d ca handed from the apply node to the pooling node
-    if tape.enabled:
+    if req:
         store = current_store()
 
         def bwd_pool():  # recorded first => runs last: after the apply node and the 3x3 conv's backward
@@ -3225,8 +3386,8 @@ def _spatial_channel_attention_bf16(skip: Var, out: Var, mod) -> Var:
     y = _new(ot.shape, ot)
     _lib.call("cn_sca_apply_fwd_bf16", ot.data_ptr(), ld(ot), ca.data_ptr(), sconv.t.data_ptr(), gamma.data_ptr(),
               y.data_ptr(), ld(y), B, C, L, s)
-    yv = Var(y, tape.enabled)
-    if tape.enabled:
+    yv = Var(y, req)
+    if req:
 
         def bwd_apply():
             dy = yv.grad
@@ -3349,8 +3510,9 @@ def _thin_conv3x3_bf16(x: Var, mods: T.Sequence, grouped: bool, dilation: int, o
         tw.version = store.version
     _lib.call("cn_conv2d_fwd_bf16", xt.data_ptr(), ld(xt), tw.fwd16.data_ptr(), None, y.data_ptr(), 0, CPt * HW, B, Cin,
               H, W, CPt, 3, 3, 1, dilation, dilation, 0, 1, None, _stream())
-    yv = Var(y, tape.enabled)
-    if tape.enabled:
+    yv = Var(y, _req(tape, (x,), [m.weight for m in mods]))
+    if yv.req:
+        gw = any(_tr(m.weight) for m in mods)  # (one launch writes every weight set)
 
         def bwd():
             dy = yv.grad
@@ -3360,22 +3522,23 @@ def _thin_conv3x3_bf16(x: Var, mods: T.Sequence, grouped: bool, dilation: int, o
             cp8 = (CPt + 7) // 8 * 8
             d16 = _alloc((B, H, W, cp8), torch.bfloat16, xt.device)
             _lib.call("cn_convert_f32nchw_to_bf16nhwc", dy.data_ptr(), bstride(dy), d16.data_ptr(), cp8, B, CPt, cp8, HW, s)
-            with side_stream(xt, d16):
-                ss = _stream()
-                need = _lib.query("cn_bwgrad_workspace_floats", B, Cin, H, W, CPt, 3, 3, 1, dilation, dilation, 0)
-                wsp, wsn = _ws16(need, xt.device)
-                if tw.view:  # accumulates straight into the flat gradient (zeroed once per step)
-                    _lib.call("cn_conv2d_bwd_weight_bf16", xt.data_ptr(), ld(xt), d16.data_ptr(), cp8,
-                              store.grad_of(tw.wcat).data_ptr(), B, Cin, H, W, CPt, 3, 3, 1, dilation, dilation, wsp,
-                              wsn, ss)
-                else:
-                    _lib.call("cn_fill_f32", tw.dwcat.data_ptr(), tw.dwcat.numel(), 0.0, ss)
-                    _lib.call("cn_conv2d_bwd_weight_bf16", xt.data_ptr(), ld(xt), d16.data_ptr(), cp8,
-                              tw.dwcat.data_ptr(), B, Cin, H, W, CPt, 3, 3, 1, dilation, dilation, wsp, wsn, ss)
-                    per = CP * Cin * 9
-                    for i, m in enumerate(mods):
-                        _lib.call("cn_copy_f32", tw.dwcat[i * CP].data_ptr(), per, store.grad_of(m.weight).data_ptr(),
-                                  per, 1, per, 1, ss)
+            if gw:
+                with side_stream(xt, d16):
+                    ss = _stream()
+                    need = _lib.query("cn_bwgrad_workspace_floats", B, Cin, H, W, CPt, 3, 3, 1, dilation, dilation, 0)
+                    wsp, wsn = _ws16(need, xt.device)
+                    if tw.view:  # accumulates straight into the flat gradient (zeroed once per step)
+                        _lib.call("cn_conv2d_bwd_weight_bf16", xt.data_ptr(), ld(xt), d16.data_ptr(), cp8,
+                                  store.grad_of(tw.wcat).data_ptr(), B, Cin, H, W, CPt, 3, 3, 1, dilation, dilation, wsp,
+                                  wsn, ss)
+                    else:
+                        _lib.call("cn_fill_f32", tw.dwcat.data_ptr(), tw.dwcat.numel(), 0.0, ss)
+                        _lib.call("cn_conv2d_bwd_weight_bf16", xt.data_ptr(), ld(xt), d16.data_ptr(), cp8,
+                                  tw.dwcat.data_ptr(), B, Cin, H, W, CPt, 3, 3, 1, dilation, dilation, wsp, wsn, ss)
+                        per = CP * Cin * 9
+                        for i, m in enumerate(mods):
+                            _lib.call("cn_copy_f32", tw.dwcat[i * CP].data_ptr(), per, store.grad_of(m.weight).data_ptr(),
+                                      per, 1, per, 1, ss)
             if x.req:
                 dx, acc = grad_buffer(x)
                 _lib.call("cn_conv2d_bwd_data_bf16", d16.data_ptr(), cp8, tw.bwd16.data_ptr(), dx.data_ptr(), ld(dx), B,

@@ -360,8 +360,11 @@ class CultionetLitTransferModel(LightningModuleMixin):
 
     ``finetune``: "all" trains everything; "fc" freezes the network and unfreezes the ``mask_model.final_*`` heads;
     anything else (the default None) freezes the network and REPLACES final_a / final_b / final_c / final_combine by
-    freshly initialised, trainable heads. Frozen parameters keep ``requires_grad=False`` (torch optimizers skip them);
-    the HIP tape still writes their gradient slices, which nothing reads.
+    freshly initialised, trainable heads. Frozen parameters keep ``requires_grad=False``: torch optimizers skip them,
+    and the HIP tape records no backward for the frozen tower in front of the heads (only the heads' backward runs).
+    (A frozen layer a gradient must pass through still launches its data gradient; a fused kernel there writes the
+    layer's frozen gradient slices too, which nothing reads.)
+    HipTrainer trains the model natively (segmented clip + AdamW over the trainable parameters).
     """
 
     def __init__(
@@ -526,6 +529,10 @@ class HipTrainer:
     see cultionet_amd.schedules); otherwise ``lr_fn(step) -> lr`` (or ``-> (lr, beta1)``), constant by default.
     With ``world_size > 1`` the flat gradient is all-reduced over RCCL in buckets overlapped with the backward
     tape (see cultionet_amd.ddp).
+
+    Frozen parameters (``requires_grad=False``: CultionetLitTransferModel, or any frozen set of submodules) get no
+    update and no gradient is read for them (fused backward kernels may still write their slices), as torch.optim.AdamW skips parameters without ``.grad``; clipping sees the trainable
+    gradients only, and every parameter keeps its own AdamW step count. The trainable set is read at every step.
     """
 
     def __init__(self, lit: CultionetLitModel, gradient_clip_val: T.Optional[float] = 1.0,
@@ -573,21 +580,60 @@ class HipTrainer:
             self.bf16 = False
         if lit.optimizer != "AdamW":
             raise NotImplementedError("the fused HIP optimizer implements AdamW (the reference default)")
-        if any(not p.requires_grad for p in self.store.params):
-            raise NotImplementedError("frozen parameters (CultionetLitTransferModel): the fused optimizer updates the "
-                                      "whole flat buffer; train transfer models through the drop-in (torch optimizer) mode")
+        # frozen parameters (requires_grad=False; CultionetLitTransferModel, partial training): the backward computes no
+        # gradient for them and the optimizer step skips them, as torch.optim.AdamW does for parameters without .grad.
+        # Every parameter keeps its own AdamW step count: ``_psteps`` (per parameter, store order) once a step has run
+        # with frozen parameters; until then all share ``step_count`` and the step is the unsegmented one.
+        self._psteps: T.Optional[T.List[int]] = None
+        self._mask = self._trainable_mask()
+        self._segs = None  # (mask, steps at build, [(offset, length, step)], device table, chunks, (lo, hi))
         if comm is not None:
             # torch DDP (the reference's strategy="ddp", model.py:101,184) broadcasts rank 0's parameters and buffers
             # at construction; dropout masks must differ per rank (each rank draws its own torch RNG stream upstream)
             comm.sync_initial_state(self.store, self.model)
             E.manual_seed(E._rng["seed"] + 0x9E37 * comm.rank)
 
+    def _trainable_mask(self) -> T.Tuple[bool, ...]:
+        mask = self.store.trainable_mask()
+        if not any(mask):
+            # (upstream fails here too: loss.backward() on a graph without any parameter that requires a gradient)
+            raise ValueError("every parameter of the model is frozen (requires_grad=False): nothing to train")
+        return mask
+
+    @property
+    def param_steps(self) -> T.List[int]:
+        """AdamW step count of every parameter (store order)."""
+        return list(self._psteps) if self._psteps is not None else [self.step_count] * len(self.store.params)
+
+    def _segments(self):
+        """Segment table of the current trainable set (rebuilt when that set changes)."""
+        steps = self.param_steps
+        sg = self._segs
+        if sg is None or sg[0] != self._mask:
+            store = self.store
+            segs = E.trainable_segments(store.offsets, [p.numel() for p in store.params], self._mask, steps)
+            raw, chunks = E.segment_table(segs)
+            table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(store.flat.device)
+            span = (segs[0][0], segs[-1][0] + segs[-1][1])
+            # the step counts of a table's parameters advance together while the set is unchanged: the kernel adds
+            # the steps taken since the build (step_add)
+            anchor = next(i for i, t in enumerate(self._mask) if t)
+            sg = self._segs = (self._mask, steps[anchor], segs, table, chunks, span)
+        return sg
+
     def forward_backward(self, batch: Data) -> torch.Tensor:
-        """Forward + loss + backward; leaves d(loss)/d(params) in store.flat_grad. Returns the loss (1-elem tensor)."""
+        """Forward + loss + backward; leaves d(loss)/d(params) in store.flat_grad (the trainable slices when parameters
+        are frozen). Returns the loss (1-elem tensor)."""
+        self._mask = self._trainable_mask()
         if self.replay and self.comm is None and self.model.training:
             from . import replay as R
 
             key = R.step_key(self, batch)
+            if self._plan is not None and self._plan.key == key and not all(self._mask) and \
+                    self.store._signature() != self.store._sig:
+                # parameters were written outside the engine: the plan refreshes the trainable packs only
+                self.store.refresh()
+                self._plan = None
             if self._plan is not None and self._plan.key == key:
                 R.replay_step(self._plan, batch)
                 self.last_outputs = self._plan.outputs
@@ -613,7 +659,11 @@ class HipTrainer:
             terms = lit._loss_terms(batch)
             self.last_losses = E.tanimoto_loss_multi([outs[key] for key, _ in terms], [kw for _, kw in terms],
                                                      loss_kind=kind, weights=[1.0 / 3.0] * len(terms), total=self.total)
-            store.zero_grad()
+            if all(self._mask):
+                store.zero_grad()
+            else:  # the span of the trainable runs (frozen slices get no gradient and are never read)
+                lo, hi = self._segments()[5]
+                _lib.call("cn_fill_f32", store.flat_grad[lo:].data_ptr(), hi - lo, 0.0, E._stream())
             if self.comm is not None:
                 self.comm.backward(tape, store)
             else:
@@ -627,6 +677,15 @@ class HipTrainer:
         self.step_count += 1
         s = E._stream()
         scale = 1.0 / self.comm.world_size if self.comm is not None else 1.0
+        mask = self._mask
+        if self._psteps is not None or not all(mask):
+            if self._psteps is None:
+                self._psteps = [self.step_count - 1] * len(mask)
+            for i, t in enumerate(mask):
+                if t:
+                    self._psteps[i] += 1
+            self._segmented_step(scale, s)
+            return
         sumsq = None
         if self.clip is not None:
             _lib.call("cn_grad_sumsq_f32", store.flat_grad.data_ptr(), store.numel, self.sumsq.data_ptr(), s)
@@ -638,6 +697,27 @@ class HipTrainer:
                   float(lit.eps), float(lit.weight_decay), self.step_count, scale, sumsq,
                   float(self.clip) if self.clip is not None else 0.0, s)
         store.bump()
+
+    def _segmented_step(self, scale: float, s: int) -> None:
+        """clip_grad_norm_ + AdamW over the trainable runs only, each with its own step count (cn_*_seg_f32)."""
+        from . import _lib
+
+        lit, store = self.lit, self.store
+        mask, step0, segs, table, chunks, _span = self._segments()
+        anchor = next(i for i, t in enumerate(mask) if t)
+        step_add = self._psteps[anchor] - step0
+        sumsq = None
+        if self.clip is not None:
+            _lib.call("cn_grad_sumsq_seg_f32", store.flat_grad.data_ptr(), store.numel, table.data_ptr(), len(segs),
+                      chunks, self.sumsq.data_ptr(), s)
+            sumsq = self.sumsq.data_ptr()
+        sched = self.lr_fn(self.step_count)
+        lr, beta1 = sched if isinstance(sched, tuple) else (sched, 0.9)
+        _lib.call("cn_adamw_step_seg_f32", store.flat.data_ptr(), store.flat_grad.data_ptr(), self.exp_avg.data_ptr(),
+                  self.exp_avg_sq.data_ptr(), store.numel, table.data_ptr(), len(segs), chunks, step_add, float(lr),
+                  float(beta1), 0.98, float(lit.eps), float(lit.weight_decay), scale, sumsq,
+                  float(self.clip) if self.clip is not None else 0.0, s)
+        store.bump(mask)  # only the trainable weights changed: only their packed copies are refreshed
 
     def training_step(self, batch: Data) -> torch.Tensor:
         loss = self.forward_backward(batch)

@@ -180,10 +180,15 @@ class StepPlan:
 
 
 def step_key(trainer, batch) -> tuple:
+    """Validity of a recorded step. Holds the trainable set (``requires_grad`` of every parameter): which backward
+    launches exist depends on it, so a plan recorded under one freezing pattern never replays under another."""
     x, y, bd = batch.x, batch.y, batch.bdist
+    mask = getattr(trainer, "_mask", None)
+    if mask is None:
+        mask = trainer.store.trainable_mask()
     return (tuple(x.shape), x.dtype, tuple(y.shape), y.dtype, tuple(bd.shape), bd.dtype, trainer.bf16, trainer.store.uid,
             str(trainer.lit.loss_name), torch.cuda.current_stream(x.device).cuda_stream, E._OVERLAP_WGRAD,
-            E.workspace_epoch(), E.branch_streams_allowed())
+            E.workspace_epoch(), E.branch_streams_allowed(), mask)
 
 
 def record_step(trainer, batch, eager: T.Callable) -> StepPlan:
@@ -206,6 +211,13 @@ def record_step(trainer, batch, eager: T.Callable) -> StepPlan:
         ops.append((0, fn, args))
         return rc
 
+    mask = getattr(trainer, "_mask", None)
+    partial = mask is not None and not all(mask)
+    if partial and trainer.store._dirty is None:
+        # parameters were written outside the engine since the last repack: refresh every packed copy NOW, eagerly, so
+        # that the plan records the repack of the trainable weights only (the optimizer step writes nothing else)
+        with E.using_store(trainer.store):
+            trainer.store.repack_all()
     with _recording_pool(plan.pool):
         # the plan's inputs in the CANONICAL form the loss / forward kernels consume (x fp32, labels int64, distances
         # fp32, all dense): `dst.copy_(src)` of every replayed step then does any cast / re-striding on the device, and no
@@ -218,7 +230,9 @@ def record_step(trainer, batch, eager: T.Callable) -> StepPlan:
         for dst, src in zip(plan.inputs, (batch.x, batch.y, batch.bdist)):
             dst.copy_(src)
         pb = Data(x=plan.inputs[0], y=plan.inputs[1], bdist=plan.inputs[2])
-        trainer.store.bump()  # the batched weight re-pack must be PART of the plan even if nothing changed since the last pack
+        # the batched weight re-pack must be PART of the plan even if nothing changed since the last pack (of the trainable
+        # weights only when parameters are frozen: the optimizer step writes nothing else)
+        trainer.store.bump(mask if partial else None)
         _lib.call = recording
         E._recorder = ops
         try:

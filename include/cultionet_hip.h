@@ -32,6 +32,7 @@ extern "C" {
 #define CN_ERR_LAUNCH (-2)
 #define CN_ERR_LDS (-3)
 
+/* cn_version(): 100 initial ABI; 101 adds cn_grad_sumsq_seg_f32 / cn_adamw_step_seg_f32 (frozen parameters). */
 int cn_version(void);
 
 /* ---- packed weights for the implicit-GEMM kernels -------------------------------------------
@@ -312,6 +313,15 @@ int cn_grad_sumsq_f32(const float* g, long n, double* out, void* stream);
 int cn_adamw_step_f32(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                       float eps, float weight_decay, int step, float grad_scale, const double* sumsq, float max_norm,
                       void* stream);
+/* Segmented step (v101: frozen parameters). segs: device table of nseg 24-byte records
+ *   { long off; long len; int step; int chunk0; }  sorted by off, non-overlapping, inside [0, n):
+ * runs of trainable parameters sharing an AdamW step count; chunk0 = sum of ceil(len / 4096) over the records before it,
+ * nchunks = that sum over all records. Elements outside the segments are neither read nor written. Each segment gets
+ * its own bias corrections 1 - beta^(step + step_add); the clip coefficient uses the segmented sum of squares (sumsq nullable). */
+int cn_grad_sumsq_seg_f32(const float* g, long n, const void* segs, int nseg, int nchunks, double* out, void* stream);
+int cn_adamw_step_seg_f32(float* p, const float* g, float* m, float* v, long n, const void* segs, int nseg, int nchunks,
+                          int step_add, float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                          const double* sumsq, float max_norm, void* stream);
 
 /* ---- input / output edges ------------------------------------------------
  * prepare: EdgeDataset.get scale + clip (data/datasets.py:443-446) + NormValues z-score
