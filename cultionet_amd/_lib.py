@@ -76,6 +76,8 @@ SIGNATURES = {
     "cn_adamw_step_f32": [P, P, P, P, L, F, F, F, F, F, I, F, P, F, P],
     "cn_grad_sumsq_seg_f32": [P, L, P, I, I, P, P],
     "cn_adamw_step_seg_f32": [P, P, P, P, L, P, I, I, I, F, F, F, F, F, F, P, F, P],
+    "cn_optim_step_f32": [I, I, P, P, P, P, L, F, F, F, F, F, I, F, P, F, P],
+    "cn_optim_step_seg_f32": [I, I, P, P, P, P, L, P, I, I, I, F, F, F, F, F, F, P, F, P],
     "cn_pack_timeconv_f32": [P, P, I, I, I, I, I, P],
     "cn_fold_timeconv_grad_f32": [P, P, I, I, I, I, P],
     "cn_prepare_chips_f32": [P, I, P, P, P, I, I, L, F, F, F, P],

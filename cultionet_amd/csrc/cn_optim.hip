@@ -6,6 +6,9 @@
 // All parameters live in ONE contiguous fp32 buffer (and so do grads, exp_avg, exp_avg_sq), so the
 // whole step is two launches: a sum-of-squares reduction and the update. The clip coefficient is
 // computed on the device from the reduced norm -- no host synchronisation.
+// The reference's other choices -- Adam, RAdam, SGD (lightning.py:611-655) and value clipping -- follow the AdamW pair
+// below: cn_optim_step_f32 / cn_optim_step_seg_f32 (Adam with norm clipping is the AdamW kernel with weight_decay 0;
+// value clipping happens inside the update and needs no reduction launch).
 #include "cn_common.h"
 
 __global__ __launch_bounds__(256) void cn_sumsq_kernel(const float* __restrict__ g, long n, double* __restrict__ out) {
@@ -181,4 +184,199 @@ extern "C" int cn_adamw_step_seg_f32(float* p, const float* g, float* m, float* 
   return cn_check_launch();
 }
 
-extern "C" int cn_version() { return 101; }
+// ---- every optimizer and clip mode of the reference's command line ------------------------------------------------------
+// --optimizer Adam | AdamW | RAdam | SGD and gradient_clip_algorithm norm | value (lightning.py:611-655, model.py:84,173)
+// over the same flat buffers and the same CnSeg table as the AdamW pair above. torch 2.10 single-tensor semantics,
+// maximize=False, no amsgrad / nesterov / dampening:
+//   CN_OPT_ADAMW  the rule above (Adam is weight_decay = 0: p * 1 is exact)
+//   CN_OPT_SGD    g += wd*p ; buf = mu*buf + g ; p -= lr*buf      (mu arrives as beta1: OneCycleLR cycles it; torch's
+//                 first-step buf = g equals mu*0 + g, so a zero-initialised buffer needs no branch; v is never touched)
+//   CN_OPT_RADAM  p *= 1 - lr*wd ; m, v as AdamW ; rho_t = rho_inf - 2 t b2^t / (1 - b2^t)
+//                 rho_t > 5:  p -= (lr/bc1) * m * rect * sqrt(bc2) / (sqrt(v) + eps)     else  p -= (lr/bc1) * m
+// The gradient an element sees is g * grad_scale, then times the norm-clip coefficient (CN_CLIP_NORM, sumsq as above) or
+// clamped to [-clip, clip] (CN_CLIP_VALUE: clip_grad_value_, no reduction launch at all). Everything that depends on
+// the step count alone is computed once per launch (per chunk when segmented) in double.
+// HBM streaming: 16-byte accesses over the 16-byte-aligned body of a run, scalar head / tail (a run of the segment
+// table may start anywhere; ParamStore slices start on 16 bytes).
+enum { CN_OPT_ADAMW = 0, CN_OPT_SGD = 1, CN_OPT_RADAM = 2 };
+enum { CN_CLIP_NONE = 0, CN_CLIP_NORM = 1, CN_CLIP_VALUE = 2 };
+
+struct CnOptCoef {
+  float decay;  // 1 - lr*wd (decoupled)            | SGD: wd
+  float step;   // lr / bc1                         | SGD: lr
+  float adapt;  // AdamW sqrt(bc2); RAdam rect*sqrt(bc2), or 0 while the variance is not rectified yet
+  float b1, b2, eps;
+};
+
+__host__ __device__ inline CnOptCoef cn_opt_coef(int kind, float lr, float b1, float b2, float eps, float wd, double t) {
+  CnOptCoef c;
+  c.b1 = b1, c.b2 = b2, c.eps = eps;
+  if (kind == CN_OPT_SGD) {
+    c.decay = wd, c.step = lr, c.adapt = 0.f;
+    return c;
+  }
+  const double b2t = pow((double)b2, t);
+  const double bc2 = 1.0 - b2t;
+  c.decay = 1.f - lr * wd;
+  c.step = lr / (float)(1.0 - pow((double)b1, t));
+  c.adapt = (float)sqrt(bc2);
+  if (kind == CN_OPT_RADAM) {
+    const double rho_inf = 2.0 / (1.0 - (double)b2) - 1.0;
+    const double rho_t = rho_inf - 2.0 * t * b2t / bc2;
+    c.adapt = rho_t > 5.0 ? (float)(sqrt((rho_t - 4.0) * (rho_t - 2.0) * rho_inf /
+                                         ((rho_inf - 4.0) * (rho_inf - 2.0) * rho_t)) * sqrt(bc2))
+                          : 0.f;
+  }
+  return c;
+}
+
+template <int KIND, int CLIP>
+__device__ __forceinline__ void cn_opt_elem(float& p, float g, float& m, float& v, const CnOptCoef& c, float gs,
+                                            float clip) {
+  g *= gs;
+  if (CLIP == CN_CLIP_VALUE) g = fminf(fmaxf(g, -clip), clip);
+  if (KIND == CN_OPT_SGD) {
+    g += c.decay * p;
+    m = c.b1 * m + g;
+    p -= c.step * m;
+    return;
+  }
+  p *= c.decay;
+  m = c.b1 * m + (1.f - c.b1) * g;
+  v = c.b2 * v + (1.f - c.b2) * g * g;
+  if (KIND == CN_OPT_ADAMW) {
+    p -= c.step * m / (sqrtf(v) / c.adapt + c.eps);
+  } else if (c.adapt != 0.f) {
+    p -= c.step * m * c.adapt / (sqrtf(v) + c.eps);
+  } else {
+    p -= c.step * m;
+  }
+}
+
+template <int KIND, int CLIP>
+__device__ __forceinline__ void cn_opt_one(float* p, const float* g, float* m, float* v, long i, const CnOptCoef& c,
+                                           float gs, float clip) {
+  float pi = p[i], mi = m[i], vi = KIND == CN_OPT_SGD ? 0.f : v[i];
+  cn_opt_elem<KIND, CLIP>(pi, g[i], mi, vi, c, gs, clip);
+  p[i] = pi;
+  m[i] = mi;
+  if (KIND != CN_OPT_SGD) v[i] = vi;
+}
+
+template <int KIND, int CLIP>
+__device__ __forceinline__ void cn_opt_four(float* p, const float* g, float* m, float* v, long i, const CnOptCoef& c,
+                                            float gs, float clip) {
+  float4 p4 = *reinterpret_cast<float4*>(p + i), m4 = *reinterpret_cast<float4*>(m + i);
+  const float4 g4 = *reinterpret_cast<const float4*>(g + i);
+  float4 v4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (KIND != CN_OPT_SGD) v4 = *reinterpret_cast<float4*>(v + i);
+  cn_opt_elem<KIND, CLIP>(p4.x, g4.x, m4.x, v4.x, c, gs, clip);
+  cn_opt_elem<KIND, CLIP>(p4.y, g4.y, m4.y, v4.y, c, gs, clip);
+  cn_opt_elem<KIND, CLIP>(p4.z, g4.z, m4.z, v4.z, c, gs, clip);
+  cn_opt_elem<KIND, CLIP>(p4.w, g4.w, m4.w, v4.w, c, gs, clip);
+  *reinterpret_cast<float4*>(p + i) = p4;
+  *reinterpret_cast<float4*>(m + i) = m4;
+  if (KIND != CN_OPT_SGD) *reinterpret_cast<float4*>(v + i) = v4;
+}
+
+// elements [lo, hi) by one block; `vec` when the four base pointers are 16-byte aligned
+template <int KIND, int CLIP>
+__device__ __forceinline__ void cn_opt_run(float* p, const float* g, float* m, float* v, long lo, long hi, long first,
+                                           long stride, bool vec, const CnOptCoef& c, float gs, float clip) {
+  long alo = hi, ahi = hi;  // [alo, ahi): the aligned body
+  if (vec) {
+    alo = (lo + 3) & ~3L;
+    if (alo > hi) alo = hi;
+    ahi = alo + ((hi - alo) & ~3L);
+  }
+  for (long i = lo + first; i < alo; i += stride) cn_opt_one<KIND, CLIP>(p, g, m, v, i, c, gs, clip);
+  for (long i = alo + 4 * first; i < ahi; i += 4 * stride) cn_opt_four<KIND, CLIP>(p, g, m, v, i, c, gs, clip);
+  for (long i = ahi + first; i < hi; i += stride) cn_opt_one<KIND, CLIP>(p, g, m, v, i, c, gs, clip);
+}
+
+__device__ __forceinline__ float cn_clip_scale(int clip_mode, float grad_scale, const double* sumsq, float clip) {
+  if (clip_mode != CN_CLIP_NORM) return grad_scale;
+  const float norm = (float)sqrt(*sumsq) * grad_scale;
+  return grad_scale * fminf(clip / (norm + 1e-6f), 1.0f);
+}
+
+template <int KIND, int CLIP>
+__global__ __launch_bounds__(256) void cn_optim_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                      float* __restrict__ m, float* __restrict__ v, long n, CnOptCoef c,
+                                                      float grad_scale, const double* sumsq, float clip, int vec) {
+  const float gs = cn_clip_scale(CLIP, grad_scale, sumsq, clip);
+  cn_opt_run<KIND, CLIP>(p, g, m, v, 0, n, blockIdx.x * 256L + threadIdx.x, (long)gridDim.x * 256, vec != 0, c, gs,
+                         clip);
+}
+
+template <int KIND, int CLIP>
+__global__ __launch_bounds__(256) void cn_optim_seg_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                          float* __restrict__ m, float* __restrict__ v, long n,
+                                                          const CnSeg* __restrict__ segs, int nseg, int nchunks,
+                                                          int step_add, float lr, float b1, float b2, float eps, float wd,
+                                                          float grad_scale, const double* sumsq, float clip, int vec) {
+  const float gs = cn_clip_scale(CLIP, grad_scale, sumsq, clip);
+  for (int ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
+    const CnSeg sg = segs[cn_seg_find(segs, nseg, ch)];
+    const long lo = sg.off + (long)(ch - sg.chunk0) * CN_SEG_CHUNK;
+    long hi = sg.off + sg.len;
+    if (hi > lo + CN_SEG_CHUNK) hi = lo + CN_SEG_CHUNK;
+    if (hi > n) hi = n;
+    const CnOptCoef c = cn_opt_coef(KIND, lr, b1, b2, eps, wd, (double)sg.step + step_add);
+    cn_opt_run<KIND, CLIP>(p, g, m, v, lo, hi, threadIdx.x, 256, vec != 0, c, gs, clip);
+  }
+}
+
+static bool cn_opt_args_ok(int kind, int clip_mode, const void* v, const double* sumsq) {
+  if (kind < CN_OPT_ADAMW || kind > CN_OPT_RADAM || clip_mode < CN_CLIP_NONE || clip_mode > CN_CLIP_VALUE) return false;
+  if (kind != CN_OPT_SGD && v == nullptr) return false;
+  return clip_mode != CN_CLIP_NORM || sumsq != nullptr;
+}
+
+static int cn_opt_vec(const void* p, const void* g, const void* m, const void* v) {
+  return (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
+}
+
+#define CN_OPT_DISPATCH(KERNEL, kind, clip_mode, ...)                                                     \
+  do {                                                                                                    \
+    switch ((kind) * 3 + (clip_mode)) {                                                                   \
+      case 0: CN_LAUNCH((KERNEL<CN_OPT_ADAMW, CN_CLIP_NONE>), __VA_ARGS__); break;                        \
+      case 1: CN_LAUNCH((KERNEL<CN_OPT_ADAMW, CN_CLIP_NORM>), __VA_ARGS__); break;                        \
+      case 2: CN_LAUNCH((KERNEL<CN_OPT_ADAMW, CN_CLIP_VALUE>), __VA_ARGS__); break;                       \
+      case 3: CN_LAUNCH((KERNEL<CN_OPT_SGD, CN_CLIP_NONE>), __VA_ARGS__); break;                          \
+      case 4: CN_LAUNCH((KERNEL<CN_OPT_SGD, CN_CLIP_NORM>), __VA_ARGS__); break;                          \
+      case 5: CN_LAUNCH((KERNEL<CN_OPT_SGD, CN_CLIP_VALUE>), __VA_ARGS__); break;                         \
+      case 6: CN_LAUNCH((KERNEL<CN_OPT_RADAM, CN_CLIP_NONE>), __VA_ARGS__); break;                        \
+      case 7: CN_LAUNCH((KERNEL<CN_OPT_RADAM, CN_CLIP_NORM>), __VA_ARGS__); break;                        \
+      default: CN_LAUNCH((KERNEL<CN_OPT_RADAM, CN_CLIP_VALUE>), __VA_ARGS__); break;                      \
+    }                                                                                                     \
+  } while (0)
+
+// kind: CN_OPT_*; clip_mode: CN_CLIP_* (`clip` is max_norm or clip_value; sumsq is read under CN_CLIP_NORM only).
+// v is not touched (may be null) for CN_OPT_SGD, whose momentum arrives as beta1.
+extern "C" int cn_optim_step_f32(int kind, int clip_mode, float* p, const float* g, float* m, float* v, long n, float lr,
+                                 float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                                 const double* sumsq, float clip, void* stream) {
+  if (n < 0 || !cn_opt_args_ok(kind, clip_mode, v, sumsq)) return CN_ERR_ARG;
+  if (n == 0) return CN_OK;
+  const CnOptCoef c = cn_opt_coef(kind, lr, beta1, beta2, eps, weight_decay, (double)step);
+  long bx = (n + 1023) / 1024;
+  if (bx > 2048) bx = 2048;
+  CN_OPT_DISPATCH(cn_optim_kernel, kind, clip_mode, dim3((unsigned)bx), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                  n, c, grad_scale, sumsq, clip, cn_opt_vec(p, g, m, v));
+  return cn_check_launch();
+}
+
+extern "C" int cn_optim_step_seg_f32(int kind, int clip_mode, float* p, const float* g, float* m, float* v, long n,
+                                     const void* segs, int nseg, int nchunks, int step_add, float lr, float beta1,
+                                     float beta2, float eps, float weight_decay, float grad_scale, const double* sumsq,
+                                     float clip, void* stream) {
+  if (nseg < 0 || nchunks < 0 || n < 0 || !cn_opt_args_ok(kind, clip_mode, v, sumsq)) return CN_ERR_ARG;
+  if (nseg == 0 || nchunks == 0) return CN_OK;
+  CN_OPT_DISPATCH(cn_optim_seg_kernel, kind, clip_mode, dim3((unsigned)cn_seg_grid(nchunks, 2048)), dim3(256), 0,
+                  (hipStream_t)stream, p, g, m, v, n, (const CnSeg*)segs, nseg, nchunks, step_add, lr, beta1, beta2, eps,
+                  weight_decay, grad_scale, sumsq, clip, cn_opt_vec(p, g, m, v));
+  return cn_check_launch();
+}
+
+extern "C" int cn_version() { return 102; }

@@ -155,6 +155,15 @@ class GradientAllReduce:
             ev1.record(torch.cuda.current_stream())
             self.exposed.append((ev0, ev1))
 
+    def reduce(self, store) -> None:
+        """All-reduce (SUM) ``store.flat_grad`` outside a backward pass, in one collective: a trailing group of
+        accumulated micro-batches whose last backward ran without communication."""
+        flat = store.flat_grad
+        if flat.is_cuda and self.comm_stream is None:
+            self.comm_stream = torch.cuda.Stream(device=flat.device)
+        self._launch(flat, flat.is_cuda).wait()
+        self.buckets_last_step = 1
+
     def _launch(self, chunk: torch.Tensor, on_gpu: bool, side_ev=None):
         if not on_gpu:
             return dist.all_reduce(chunk, op=dist.ReduceOp.SUM, group=self.group, async_op=True)

@@ -310,8 +310,8 @@ class LightningModuleMixin(_Base):
         self.cls_loss = entry.get("classification")
 
     # The reference's optimizer / scheduler choices as data (lightning.py:611-683): name -> (torch class, which of the
-    # module's hyper-parameters it takes, fixed keyword arguments). AdamW's betas (0.9, 0.98) and eps are what
-    # cultionet_amd.lightning.HipTrainer's fused kernel implements natively.
+    # module's hyper-parameters it takes, fixed keyword arguments). HipTrainer reads this table too: its fused kernels
+    # implement all four natively.
     _OPTIMIZERS = {
         "Adam": ("Adam", ("lr", "eps"), {}),
         "AdamW": ("AdamW", ("lr", "weight_decay", "eps"), {"betas": (0.9, 0.98)}),
@@ -340,8 +340,8 @@ class LightningModuleMixin(_Base):
 
     def configure_optimizers(self):
         """Lightning hook, same choices and error behaviour as the reference (lightning.py:611-683): a torch optimizer over
-        the model's parameters + one scheduler monitored on ``val_score``. (The native path -- HipTrainer -- does not use
-        this: its clip + AdamW + OneCycleLR run in cn_optim.hip.)"""
+        the model's parameters + one scheduler monitored on ``val_score``. (The native path -- HipTrainer -- builds no torch
+        object: it reads the same recipe table and runs clip + optimizer in cn_optim.hip, the schedule on the host.)"""
         recipe = self._OPTIMIZERS.get(str(self.optimizer))
         if recipe is None:
             raise NameError("Choose either 'AdamW' or 'SGD'.")
@@ -520,50 +520,90 @@ class CultionetLitModel(LightningModuleMixin):
         return False
 
 
-class HipTrainer:
-    """Native training step: every FLOP and byte of forward + loss + backward + clip + AdamW in HIP kernels.
+class _PlanSlot:
+    """Replay state of one phase of a step (HipTrainer): the recorded plan, the key the eager warm-up steps were counted
+    under, and that count."""
 
-    Semantics of lightning.Trainer(gradient_clip_val=1.0) + AdamW(lr, wd, eps, betas=(0.9, 0.98)) as configured
-    by the reference (model.py:84,168-186; lightning.py:622-629). Learning-rate schedule: ``total_steps`` given
-    => the reference's default OneCycleLR stepped per optimizer step (lightning.py:657-664; it also cycles beta1,
-    see cultionet_amd.schedules); otherwise ``lr_fn(step) -> lr`` (or ``-> (lr, beta1)``), constant by default.
-    With ``world_size > 1`` the flat gradient is all-reduced over RCCL in buckets overlapped with the backward
-    tape (see cultionet_amd.ddp).
+    __slots__ = ("plan", "key", "eager_steps")
+
+    def __init__(self):
+        self.plan, self.key, self.eager_steps = None, None, 0
+
+
+class HipTrainer:
+    """Native training step: every FLOP and byte of forward + loss + backward + clip + optimizer in HIP kernels.
+
+    Semantics of lightning.Trainer(gradient_clip_val=1.0, gradient_clip_algorithm=..., accumulate_grad_batches=...) +
+    the optimizer ``lit.optimizer`` names, from the same recipe table as ``configure_optimizers`` (Adam, AdamW, RAdam,
+    SGD with the reference's fixed arguments: model.py:84,168-186; lightning.py:611-655). The default -- AdamW, norm
+    clipping, no accumulation -- is two launches (cn_grad_sumsq_f32 + cn_adamw_step_f32); Adam takes the same pair;
+    SGD, RAdam and value clipping run in cn_optim_step_f32, value clipping without the reduction launch.
+
+    Learning-rate schedule: ``lr_fn(step) -> lr`` (or ``-> (lr, beta1)``) when given; else ``total_steps`` => the
+    reference's default OneCycleLR stepped per optimizer step (lightning.py:657-664; it also cycles the first-moment
+    coefficient -- beta1, or SGD's momentum -- see cultionet_amd.schedules); else ``steps_per_epoch`` (optimizer steps
+    per epoch) => the per-epoch scheduler ``lit.lr_scheduler`` names (CosineAnnealingLR, ExponentialLR, StepLR); else
+    constant. With ``world_size > 1`` the flat gradient is all-reduced over RCCL in buckets overlapped with the
+    backward tape (see cultionet_amd.ddp).
+
+    ``accumulate_grad_batches=k``: every ``training_step`` is one micro-batch and returns its own loss; gradients add up
+    in the flat buffer (zeroed before the first micro-batch of a group only) and clip + optimizer run after the k-th,
+    on the sum divided by k. Step counts and the schedule advance per optimizer step. ``flush_accumulated()`` steps a
+    trailing incomplete group (still dividing by k, as Lightning does on the last batch of an epoch). Under a
+    communicator only the last micro-batch of a group all-reduces (Lightning's ``no_sync``): pass ``last=True`` to
+    ``training_step`` for the last batch of an epoch.
 
     Frozen parameters (``requires_grad=False``: CultionetLitTransferModel, or any frozen set of submodules) get no
-    update and no gradient is read for them (fused backward kernels may still write their slices), as torch.optim.AdamW skips parameters without ``.grad``; clipping sees the trainable
-    gradients only, and every parameter keeps its own AdamW step count. The trainable set is read at every step.
+    update and no gradient is read for them (fused backward kernels may still write their slices), as torch optimizers skip parameters without ``.grad``; clipping sees the trainable
+    gradients only, and every parameter keeps its own step count (bias corrections, RAdam's rectification). The
+    trainable set is read at every step; it must not change inside a group of accumulated micro-batches.
     """
+
+    _KINDS = {"Adam": 0, "AdamW": 0, "SGD": 1, "RAdam": 2}  # CN_OPT_* of csrc/cn_optim.hip
+    _CLIP_NONE, _CLIP_NORM, _CLIP_VALUE = 0, 1, 2          # CN_CLIP_*
 
     def __init__(self, lit: CultionetLitModel, gradient_clip_val: T.Optional[float] = 1.0,
                  lr_fn: T.Optional[T.Callable[[int], T.Union[float, T.Tuple[float, float]]]] = None, comm=None,
-                 total_steps: T.Optional[int] = None, precision: str = "32-true", replay: bool = False):
+                 total_steps: T.Optional[int] = None, precision: str = "32-true", replay: bool = False,
+                 gradient_clip_algorithm: str = "norm", accumulate_grad_batches: int = 1,
+                 steps_per_epoch: T.Optional[int] = None):
         self.lit = lit
         # replay=True: forward + loss + backward run from a recorded launch plan after the first steps
         # (cultionet_amd/replay.py): the Python of a step drops from ~8-10 ms to ~1.5 ms, which is what bounds the step at
         # the reference's default batch of 4 in mixed precision. Dropout replays too (the per-step part of the mask
         # seeds is a device word the plan's first launch bumps); a communicator keeps the step eager.
+        # One plan per phase: a micro-step that zeroes the gradient and repacks the weights (the first of a group; every
+        # step without accumulation) and one that does neither (the later micro-batches of a group).
         self.replay = bool(replay)
-        self._plan = None
-        self._plan_key = None
-        self._eager_steps = 0
+        self._slots = {False: _PlanSlot(), True: _PlanSlot()}  # key: does the micro-step accumulate?
+        recipe = lit._OPTIMIZERS.get(str(lit.optimizer))
+        if recipe is None:
+            raise NameError("Choose either 'AdamW' or 'SGD'.")
+        cls_name, takes, fixed = recipe
+        self.opt_kind = self._KINDS[cls_name]
+        betas = fixed.get("betas", (0.9, 0.999))  # (torch's default for Adam)
+        self._beta1 = float(fixed.get("momentum", betas[0]))
+        self._beta2 = float(betas[1])
+        self._wd = float(lit.weight_decay) if "weight_decay" in takes else 0.0
+        self._eps = float(lit.eps) if "eps" in takes else 0.0
+        if gradient_clip_algorithm not in ("norm", "value"):
+            raise ValueError(f"gradient_clip_algorithm {gradient_clip_algorithm!r}: choose 'norm' or 'value'")
+        self.clip_algorithm = gradient_clip_algorithm
+        if int(accumulate_grad_batches) != accumulate_grad_batches or accumulate_grad_batches < 1:
+            raise ValueError(f"accumulate_grad_batches must be a positive integer, got {accumulate_grad_batches!r}")
+        self.accumulate = int(accumulate_grad_batches)
+        self._micro = 0  # micro-batches in flat_grad since the last optimizer step
+        self._reduced = True  # under a communicator: has flat_grad been all-reduced since the last micro-batch?
         self.model = lit.cultionet_model.mask_model
         self.store = self.model.param_store()
         dev = self.store.flat.device
-        self.exp_avg = torch.zeros_like(self.store.flat)
-        self.exp_avg_sq = torch.zeros_like(self.store.flat)
+        self.exp_avg = torch.zeros_like(self.store.flat)  # (SGD: the momentum buffer, its only state)
+        self.exp_avg_sq = torch.zeros_like(self.store.flat) if cls_name != "SGD" else None
         self.sumsq = torch.zeros(1, dtype=torch.float64, device=dev)
         self.total = torch.zeros(1, dtype=torch.float32, device=dev)
         self.clip = gradient_clip_val
         if lr_fn is None:
-            from .schedules import ConstantLR, OneCycleLR
-
-            if total_steps is not None:
-                if str(lit.lr_scheduler) != str(LearningRateSchedulers.ONE_CYCLE_LR):
-                    raise NotImplementedError("the native step schedules OneCycleLR (the reference default); pass lr_fn")
-                lr_fn = OneCycleLR(lit.learning_rate, total_steps)
-            else:
-                lr_fn = ConstantLR(lit.learning_rate)
+            lr_fn = self._schedule(lit, total_steps, steps_per_epoch)
         self.lr_fn = lr_fn
         self.step_count = 0
         self.comm = comm
@@ -578,11 +618,9 @@ class HipTrainer:
             warnings.warn("cultionet_amd: the mixed-precision path needs channel counts that are multiples of 8 "
                           "(hidden_channels % 8 == 0); this trainer runs in fp32", stacklevel=2)
             self.bf16 = False
-        if lit.optimizer != "AdamW":
-            raise NotImplementedError("the fused HIP optimizer implements AdamW (the reference default)")
         # frozen parameters (requires_grad=False; CultionetLitTransferModel, partial training): the backward computes no
-        # gradient for them and the optimizer step skips them, as torch.optim.AdamW does for parameters without .grad.
-        # Every parameter keeps its own AdamW step count: ``_psteps`` (per parameter, store order) once a step has run
+        # gradient for them and the optimizer step skips them, as torch optimizers do for parameters without .grad.
+        # Every parameter keeps its own step count: ``_psteps`` (per parameter, store order) once a step has run
         # with frozen parameters; until then all share ``step_count`` and the step is the unsegmented one.
         self._psteps: T.Optional[T.List[int]] = None
         self._mask = self._trainable_mask()
@@ -593,6 +631,49 @@ class HipTrainer:
             comm.sync_initial_state(self.store, self.model)
             E.manual_seed(E._rng["seed"] + 0x9E37 * comm.rank)
 
+    def _schedule(self, lit, total_steps: T.Optional[int], steps_per_epoch: T.Optional[int]):
+        """``lr_fn`` for ``lit.lr_scheduler`` (the choices of LightningModuleMixin._make_scheduler)."""
+        from . import schedules as S
+
+        name = str(lit.lr_scheduler)
+        if total_steps is None and steps_per_epoch is None:
+            return S.ConstantLR(lit.learning_rate, self._beta1)
+        if name == str(LearningRateSchedulers.ONE_CYCLE_LR):
+            if total_steps is None:
+                raise ValueError("OneCycleLR is stepped per optimizer step: pass total_steps (steps_per_epoch alone "
+                                 "does not say how long the cycle is)")
+            return S.OneCycleLR(lit.learning_rate, total_steps)
+        per_epoch = {
+            str(LearningRateSchedulers.COSINE_ANNEALING_LR): lambda: S.CosineAnnealingLR(lit.learning_rate),
+            str(LearningRateSchedulers.EXPONENTIAL_LR): lambda: S.ExponentialLR(lit.learning_rate),
+            str(LearningRateSchedulers.STEP_LR): lambda: S.StepLR(lit.learning_rate, lit.steplr_step_size),
+        }
+        if name not in per_epoch:
+            raise NameError("The learning rate scheduler is not implemented in Cultionet.")
+        if steps_per_epoch is None:
+            raise ValueError(f"{name} is stepped per epoch: pass steps_per_epoch (optimizer steps per epoch); "
+                             "total_steps alone does not say where an epoch ends")
+        return S.PerEpoch(per_epoch[name](), steps_per_epoch, self._beta1)
+
+    # the replay state of the zeroing phase under its historical names (the only phase without accumulation)
+    @property
+    def _plan(self):
+        return self._slots[False].plan
+
+    @_plan.setter
+    def _plan(self, plan):
+        self._slots[False].plan = plan
+
+    @property
+    def _plan_acc(self):
+        """The recorded plan of an accumulating micro-step (no gradient zero-fill, no weight repack)."""
+        return self._slots[True].plan
+
+    @property
+    def _accumulating(self) -> bool:
+        """Does the next micro-batch add to gradients already in flat_grad?"""
+        return self.accumulate > 1 and self._micro > 0
+
     def _trainable_mask(self) -> T.Tuple[bool, ...]:
         mask = self.store.trainable_mask()
         if not any(mask):
@@ -602,7 +683,7 @@ class HipTrainer:
 
     @property
     def param_steps(self) -> T.List[int]:
-        """AdamW step count of every parameter (store order)."""
+        """Optimizer step count of every parameter (store order)."""
         return list(self._psteps) if self._psteps is not None else [self.step_count] * len(self.store.params)
 
     def _segments(self):
@@ -621,30 +702,48 @@ class HipTrainer:
             sg = self._segs = (self._mask, steps[anchor], segs, table, chunks, span)
         return sg
 
-    def forward_backward(self, batch: Data) -> torch.Tensor:
-        """Forward + loss + backward; leaves d(loss)/d(params) in store.flat_grad (the trainable slices when parameters
-        are frozen). Returns the loss (1-elem tensor)."""
-        self._mask = self._trainable_mask()
+    def forward_backward(self, batch: Data, last: bool = False) -> torch.Tensor:
+        """Forward + loss + backward; adds d(loss)/d(params) of this micro-batch to store.flat_grad (the trainable slices
+        when parameters are frozen), zeroed first unless the micro-batch continues a group. Returns the loss (1-elem
+        tensor). ``last``: the group ends here (matters under a communicator, which all-reduces on a group's last
+        micro-batch only)."""
+        mask = self._trainable_mask()
+        acc = self._accumulating
+        if acc and mask != self._mask:
+            raise RuntimeError("requires_grad changed inside a group of accumulated micro-batches: the gradients "
+                               "already summed belong to another trainable set (change it after an optimizer step)")
+        self._mask = mask
+        if not acc:
+            self._micro = 0
+        self._sync = self.comm is not None and (last or self._micro + 1 >= self.accumulate)
+        try:
+            return self._forward_backward(batch, acc)
+        finally:
+            self._micro += 1
+            self._reduced = self._sync
+
+    def _forward_backward(self, batch: Data, acc: bool) -> torch.Tensor:
         if self.replay and self.comm is None and self.model.training:
             from . import replay as R
 
+            slot = self._slots[acc]
             key = R.step_key(self, batch)
-            if self._plan is not None and self._plan.key == key and not all(self._mask) and \
+            if slot.plan is not None and slot.plan.key == key and not all(self._mask) and \
                     self.store._signature() != self.store._sig:
                 # parameters were written outside the engine: the plan refreshes the trainable packs only
                 self.store.refresh()
-                self._plan = None
-            if self._plan is not None and self._plan.key == key:
-                R.replay_step(self._plan, batch)
-                self.last_outputs = self._plan.outputs
+                slot.plan = None
+            if slot.plan is not None and slot.plan.key == key:
+                R.replay_step(slot.plan, batch)
+                self.last_outputs = slot.plan.outputs
                 return self.total
-            if self._plan_key != key:  # new shapes / stream: two eager steps first (workspaces grow, packs are built)
-                self._plan_key, self._eager_steps, self._plan = key, 0, None
-            if self._eager_steps >= 2:  # everything lazily created exists by now: record this step
+            if slot.key != key:  # new shapes / stream: two eager steps first (workspaces grow, packs are built)
+                slot.key, slot.eager_steps, slot.plan = key, 0, None
+            if slot.eager_steps >= 2:  # everything lazily created exists by now: record this step
                 plan = R.record_step(self, batch, self._forward_backward_eager)
-                self._plan = plan if plan.key is not None else None  # (None: a scratch buffer moved while recording)
+                slot.plan = plan if plan.key is not None else None  # (None: a scratch buffer moved while recording)
                 return self.total
-        self._eager_steps += 1
+            slot.eager_steps += 1
         return self._forward_backward_eager(batch)
 
     def _forward_backward_eager(self, batch: Data) -> torch.Tensor:
@@ -659,24 +758,46 @@ class HipTrainer:
             terms = lit._loss_terms(batch)
             self.last_losses = E.tanimoto_loss_multi([outs[key] for key, _ in terms], [kw for _, kw in terms],
                                                      loss_kind=kind, weights=[1.0 / 3.0] * len(terms), total=self.total)
-            if all(self._mask):
+            if self._accumulating:  # every producer of a parameter gradient adds into flat_grad
+                pass
+            elif all(self._mask):
                 store.zero_grad()
             else:  # the span of the trainable runs (frozen slices get no gradient and are never read)
                 lo, hi = self._segments()[5]
                 _lib.call("cn_fill_f32", store.flat_grad[lo:].data_ptr(), hi - lo, 0.0, E._stream())
-            if self.comm is not None:
+            if self.comm is not None and self._sync:
                 self.comm.backward(tape, store)
-            else:
+            else:  # (under a communicator: Lightning's no_sync for all but a group's last micro-batch)
                 tape.backward()
         return self.total
 
-    def optimizer_step(self) -> None:
+    def _clip_args(self, sumsq_entry: str, *seg_args) -> T.Tuple[int, T.Optional[int], float]:
+        """(clip mode, sumsq pointer, clip value) of this step; launches the sum of squares that norm clipping needs."""
         from . import _lib
 
-        lit, store = self.lit, self.store
+        if self.clip is None:
+            return self._CLIP_NONE, None, 0.0
+        if self.clip_algorithm == "value":
+            return self._CLIP_VALUE, None, float(self.clip)
+        store = self.store
+        _lib.call(sumsq_entry, store.flat_grad.data_ptr(), store.numel, *seg_args, self.sumsq.data_ptr(), E._stream())
+        return self._CLIP_NORM, self.sumsq.data_ptr(), float(self.clip)
+
+    def optimizer_step(self) -> None:
+        """Clip + optimizer over what flat_grad holds: the sum of the micro-batches since the last step, divided by
+        ``accumulate_grad_batches`` (and by the world size)."""
+        from . import _lib
+
+        store = self.store
+        if self.accumulate > 1 and self._micro == 0:
+            raise RuntimeError("optimizer_step without a micro-batch since the last step: nothing accumulated")
+        if self.comm is not None and not self._reduced:
+            self.comm.reduce(store)  # a trailing group flushed without a ``last=True`` micro-batch
+            self._reduced = True
+        self._micro = 0
         self.step_count += 1
         s = E._stream()
-        scale = 1.0 / self.comm.world_size if self.comm is not None else 1.0
+        scale = 1.0 / ((self.comm.world_size if self.comm is not None else 1) * self.accumulate)
         mask = self._mask
         if self._psteps is not None or not all(mask):
             if self._psteps is None:
@@ -686,40 +807,54 @@ class HipTrainer:
                     self._psteps[i] += 1
             self._segmented_step(scale, s)
             return
-        sumsq = None
-        if self.clip is not None:
-            _lib.call("cn_grad_sumsq_f32", store.flat_grad.data_ptr(), store.numel, self.sumsq.data_ptr(), s)
-            sumsq = self.sumsq.data_ptr()
+        mode, sumsq, clip = self._clip_args("cn_grad_sumsq_f32")
         sched = self.lr_fn(self.step_count)
-        lr, beta1 = sched if isinstance(sched, tuple) else (sched, 0.9)
-        _lib.call("cn_adamw_step_f32", store.flat.data_ptr(), store.flat_grad.data_ptr(), self.exp_avg.data_ptr(),
-                  self.exp_avg_sq.data_ptr(), store.numel, float(lr), float(beta1), 0.98,
-                  float(lit.eps), float(lit.weight_decay), self.step_count, scale, sumsq,
-                  float(self.clip) if self.clip is not None else 0.0, s)
+        lr, beta1 = sched if isinstance(sched, tuple) else (sched, self._beta1)
+        v = self.exp_avg_sq.data_ptr() if self.exp_avg_sq is not None else None
+        if self.opt_kind == 0 and mode != self._CLIP_VALUE:  # AdamW / Adam, norm clipping or none: the original pair
+            _lib.call("cn_adamw_step_f32", store.flat.data_ptr(), store.flat_grad.data_ptr(), self.exp_avg.data_ptr(),
+                      v, store.numel, float(lr), float(beta1), self._beta2, self._eps, self._wd, self.step_count, scale,
+                      sumsq, clip, s)
+        else:
+            _lib.call("cn_optim_step_f32", self.opt_kind, mode, store.flat.data_ptr(), store.flat_grad.data_ptr(),
+                      self.exp_avg.data_ptr(), v, store.numel, float(lr), float(beta1), self._beta2, self._eps, self._wd,
+                      self.step_count, scale, sumsq, clip, s)
         store.bump()
 
     def _segmented_step(self, scale: float, s: int) -> None:
-        """clip_grad_norm_ + AdamW over the trainable runs only, each with its own step count (cn_*_seg_f32)."""
+        """Clip + optimizer over the trainable runs only, each with its own step count (cn_*_seg_f32)."""
         from . import _lib
 
-        lit, store = self.lit, self.store
+        store = self.store
         mask, step0, segs, table, chunks, _span = self._segments()
         anchor = next(i for i, t in enumerate(mask) if t)
         step_add = self._psteps[anchor] - step0
-        sumsq = None
-        if self.clip is not None:
-            _lib.call("cn_grad_sumsq_seg_f32", store.flat_grad.data_ptr(), store.numel, table.data_ptr(), len(segs),
-                      chunks, self.sumsq.data_ptr(), s)
-            sumsq = self.sumsq.data_ptr()
+        mode, sumsq, clip = self._clip_args("cn_grad_sumsq_seg_f32", table.data_ptr(), len(segs), chunks)
         sched = self.lr_fn(self.step_count)
-        lr, beta1 = sched if isinstance(sched, tuple) else (sched, 0.9)
-        _lib.call("cn_adamw_step_seg_f32", store.flat.data_ptr(), store.flat_grad.data_ptr(), self.exp_avg.data_ptr(),
-                  self.exp_avg_sq.data_ptr(), store.numel, table.data_ptr(), len(segs), chunks, step_add, float(lr),
-                  float(beta1), 0.98, float(lit.eps), float(lit.weight_decay), scale, sumsq,
-                  float(self.clip) if self.clip is not None else 0.0, s)
+        lr, beta1 = sched if isinstance(sched, tuple) else (sched, self._beta1)
+        v = self.exp_avg_sq.data_ptr() if self.exp_avg_sq is not None else None
+        if self.opt_kind == 0 and mode != self._CLIP_VALUE:
+            _lib.call("cn_adamw_step_seg_f32", store.flat.data_ptr(), store.flat_grad.data_ptr(), self.exp_avg.data_ptr(),
+                      v, store.numel, table.data_ptr(), len(segs), chunks, step_add, float(lr), float(beta1), self._beta2,
+                      self._eps, self._wd, scale, sumsq, clip, s)
+        else:
+            _lib.call("cn_optim_step_seg_f32", self.opt_kind, mode, store.flat.data_ptr(), store.flat_grad.data_ptr(),
+                      self.exp_avg.data_ptr(), v, store.numel, table.data_ptr(), len(segs), chunks, step_add, float(lr),
+                      float(beta1), self._beta2, self._eps, self._wd, scale, sumsq, clip, s)
         store.bump(mask)  # only the trainable weights changed: only their packed copies are refreshed
 
-    def training_step(self, batch: Data) -> torch.Tensor:
-        loss = self.forward_backward(batch)
-        self.optimizer_step()
+    def training_step(self, batch: Data, last: bool = False) -> torch.Tensor:
+        """One micro-batch; the optimizer steps once ``accumulate_grad_batches`` of them are summed, or at once with
+        ``last=True`` (Lightning steps on the last batch of an epoch whatever the group holds)."""
+        loss = self.forward_backward(batch, last=last)
+        if last or self._micro >= self.accumulate:
+            self.optimizer_step()
         return loss
+
+    def flush_accumulated(self) -> bool:
+        """Step a trailing incomplete group of micro-batches (the sum is still divided by ``accumulate_grad_batches``).
+        Returns whether there was one."""
+        if self.accumulate == 1 or self._micro == 0:
+            return False
+        self.optimizer_step()
+        return True

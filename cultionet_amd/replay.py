@@ -159,14 +159,17 @@ def forward(model, x: torch.Tensor, bf16: bool, run: T.Callable[[torch.Tensor], 
 #     was later handed to the compute stream would be a race. While recording, every tensor torch hands out is kept alive
 #     (the plan's ``keep`` list is an allocation sink of the engine allocator: engine.holding_allocations), so each kernel of the step has buffers of its own; the price
 #     is memory (the sum of a step's allocations instead of its peak), which is what 288 GB are for;
-#   * the optimizer (clip + AdamW: two launches with per-step scalars) stays outside the plan.
+#   * the optimizer (clip + update: one or two launches with per-step scalars) stays outside the plan;
+#   * with gradient accumulation a step has two phases with a plan each: the first micro-batch of a group zeroes the
+#     flat gradient and repacks the weights the optimizer just wrote, the later ones do neither.
 # Valid for one (batch shapes, precision, stream, store, loss kind, scratch-buffer epoch); a communicator (per-bucket
 # collectives) falls back to the eager step. Dropout > 0 replays: the per-step part of every mask seed is a device word
 # that the plan's first launch bumps (engine.begin_rng_step), the recorded seed arguments are the per-call constants. Bit-exact w.r.t. the eager step except where the eager step itself
 # is not (float-atomic parameter-gradient sums): tests/test_replay_train_gpu.py.
 # ---------------------------------------------------------------------------------------------------------------------
 class StepPlan:
-    __slots__ = ("ops", "pool", "keep", "inputs", "outputs", "key", "n_calls", "sums")
+    __slots__ = ("ops", "pool", "keep", "inputs", "outputs", "key", "n_calls", "sums", "accumulates", "grad_fills",
+                 "repacks")
 
     def __init__(self):
         self.ops: T.List[T.Tuple[int, T.Any, tuple]] = []
@@ -177,18 +180,25 @@ class StepPlan:
         self.key = None
         self.n_calls = 0
         self.sums = None  # the store's deferred-slice-sum state (engine._SliceSums) whose host table this plan rewrites
+        # the phase the plan was recorded for (gradient accumulation): a micro-step that continues a group adds to the
+        # gradients already there, and its plan holds neither a zero-fill of the flat gradient nor a weight repack
+        self.accumulates = False
+        self.grad_fills = 0  # recorded cn_fill_f32 launches into the flat gradient
+        self.repacks = 0     # recorded cn_pack_weights_batched_* launches
 
 
 def step_key(trainer, batch) -> tuple:
     """Validity of a recorded step. Holds the trainable set (``requires_grad`` of every parameter): which backward
-    launches exist depends on it, so a plan recorded under one freezing pattern never replays under another."""
+    launches exist depends on it, so a plan recorded under one freezing pattern never replays under another. Holds the
+    phase too (does the micro-step add to accumulated gradients?): a plan that zeroes the gradient never replays where
+    one must not."""
     x, y, bd = batch.x, batch.y, batch.bdist
     mask = getattr(trainer, "_mask", None)
     if mask is None:
         mask = trainer.store.trainable_mask()
     return (tuple(x.shape), x.dtype, tuple(y.shape), y.dtype, tuple(bd.shape), bd.dtype, trainer.bf16, trainer.store.uid,
             str(trainer.lit.loss_name), torch.cuda.current_stream(x.device).cuda_stream, E._OVERLAP_WGRAD,
-            E.workspace_epoch(), E.branch_streams_allowed(), mask)
+            E.workspace_epoch(), E.branch_streams_allowed(), mask, bool(getattr(trainer, "_accumulating", False)))
 
 
 def record_step(trainer, batch, eager: T.Callable) -> StepPlan:
@@ -209,8 +219,15 @@ def record_step(trainer, batch, eager: T.Callable) -> StepPlan:
         if rc != 0:
             raise _lib.HipKernelError(f"{name} failed: {_lib.ERRORS.get(rc, rc)}")
         ops.append((0, fn, args))
+        if name == "cn_fill_f32" and grad_lo <= args[0] < grad_hi:
+            plan.grad_fills += 1
+        elif name.startswith("cn_pack_weights_batched_"):
+            plan.repacks += 1
         return rc
 
+    grad_lo = trainer.store.flat_grad.data_ptr()
+    grad_hi = grad_lo + 4 * trainer.store.numel
+    plan.accumulates = bool(getattr(trainer, "_accumulating", False))
     mask = getattr(trainer, "_mask", None)
     partial = mask is not None and not all(mask)
     if partial and trainer.store._dirty is None:
@@ -231,8 +248,10 @@ def record_step(trainer, batch, eager: T.Callable) -> StepPlan:
             dst.copy_(src)
         pb = Data(x=plan.inputs[0], y=plan.inputs[1], bdist=plan.inputs[2])
         # the batched weight re-pack must be PART of the plan even if nothing changed since the last pack (of the trainable
-        # weights only when parameters are frozen: the optimizer step writes nothing else)
-        trainer.store.bump(mask if partial else None)
+        # weights only when parameters are frozen: the optimizer step writes nothing else). Not so for a micro-step that
+        # continues a group of accumulated gradients: no optimizer step lies between it and the one before
+        if not plan.accumulates:
+            trainer.store.bump(mask if partial else None)
         _lib.call = recording
         E._recorder = ops
         try:

@@ -32,7 +32,8 @@ extern "C" {
 #define CN_ERR_LAUNCH (-2)
 #define CN_ERR_LDS (-3)
 
-/* cn_version(): 100 initial ABI; 101 adds cn_grad_sumsq_seg_f32 / cn_adamw_step_seg_f32 (frozen parameters). */
+/* cn_version(): 100 initial ABI; 101 adds cn_grad_sumsq_seg_f32 / cn_adamw_step_seg_f32 (frozen parameters);
+ * 102 adds cn_optim_step_f32 / cn_optim_step_seg_f32 (Adam, SGD, RAdam; value clipping). */
 int cn_version(void);
 
 /* ---- packed weights for the implicit-GEMM kernels -------------------------------------------
@@ -322,6 +323,17 @@ int cn_grad_sumsq_seg_f32(const float* g, long n, const void* segs, int nseg, in
 int cn_adamw_step_seg_f32(float* p, const float* g, float* m, float* v, long n, const void* segs, int nseg, int nchunks,
                           int step_add, float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                           const double* sumsq, float max_norm, void* stream);
+/* Every optimizer and clip mode of the reference (v102), over the same buffers and the same segment table.
+ *   kind       0 AdamW (Adam: weight_decay 0), 1 SGD with momentum (mu = beta1; v unused, may be null), 2 RAdam with
+ *              decoupled weight decay (rectified once rho_t > 5, per segment from step + step_add)
+ *   clip_mode  0 none, 1 norm (clip = max_norm, coefficient from sumsq as above), 2 value (clip = clip_value: the scaled
+ *              gradient is clamped to [-clip, clip] inside the update; sumsq is not read). */
+int cn_optim_step_f32(int kind, int clip_mode, float* p, const float* g, float* m, float* v, long n, float lr, float beta1,
+                      float beta2, float eps, float weight_decay, int step, float grad_scale, const double* sumsq,
+                      float clip, void* stream);
+int cn_optim_step_seg_f32(int kind, int clip_mode, float* p, const float* g, float* m, float* v, long n, const void* segs,
+                          int nseg, int nchunks, int step_add, float lr, float beta1, float beta2, float eps,
+                          float weight_decay, float grad_scale, const double* sumsq, float clip, void* stream);
 
 /* ---- input / output edges ------------------------------------------------
  * prepare: EdgeDataset.get scale + clip (data/datasets.py:443-446) + NormValues z-score
