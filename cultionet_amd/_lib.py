@@ -82,6 +82,7 @@ SIGNATURES = {
     "cn_fold_timeconv_grad_f32": [P, P, I, I, I, I, P],
     "cn_prepare_chips_f32": [P, I, P, P, P, I, I, L, F, F, F, P],
     "cn_predictions_to_u16": [P, P, P, P, I, I, I, I, I, I, I, F, P],
+    "cn_augment_chips_f32": [P, I, P, I, P, I, P, P, P, P, P, P, P, P, I, I, I, I, I, F, F, F, P],
     # ---- bf16 NHWC mixed-precision path ----
     "cn_bconv_packed_elems": [I, I, I],
     "cn_pack_weights_bf16": [P, P, I, I, I, L, L, L, P],

@@ -1,0 +1,378 @@
+// Per-sample training augmentation fused into the input prologue (EdgeDataset.get,
+// data/datasets.py:443-488, and AugmenterModule.__call__, augment/augmenters.py:25-35):
+//   v = clip(raw * scale, lo, hi)  ->  one augmentation  ->  x.clip(lo, hi), bdist.clip(0, hi), y as int64  ->  z-score
+// for the nine augmenters that need no parcel labelling (augment/augmenters.py:166-330). The random CHOICES are drawn on
+// the host and arrive as a plan table; only the per-element noise is generated here (counter-based, never stored), so the
+// kernels keep no state. Two launches per batch: one over x, one over bdist + y. The op is uniform per block
+// (blockIdx.z = sample), a block owns a band of CN_AUG_BR output rows of one plane, and every write is coalesced along W.
+//
+// Plan table: CN_AUG_PLAN_WORDS int32 words per sample
+//   [0] op   [1] div   [2] top   [3] left   [4] r   [5] sigma (float bits)   [6] noise seed, low word   [7] high word
+// Perlin angle tables: CN_AUG_PERLIN_FLOATS floats per sample, theta [2][r+1][r+1] then phi [2][r+1][r+1], compact.
+//
+// Rotations. v2.RandomRotation(degrees=[d, d]) rotates counter-clockwise by d about the image centre; for a square
+// plane and d a multiple of 90 the inverse affine grid lands exactly on pixel centres, so bilinear and nearest sampling
+// both reduce to the index permutation of torch.rot90(k = d / 90, dims = (-2, -1)):
+//   rot90 : out[i][j] = in[j][N-1-i]      rot270 : out[i][j] = in[N-1-j][i]      rot180 : out[i][j] = in[N-1-i][N-1-j]
+// (torchvision is not available to the test suite; this equivalence is argued here, the permutation itself is tested.)
+// On a non-square plane the reference fills the uncovered corners with zeros; that case is refused (CN_ERR_ARG).
+#include "cn_common.h"
+
+#include <type_traits>
+
+#define CN_AUG_NONE 0
+#define CN_AUG_ROT90 1
+#define CN_AUG_ROT180 2
+#define CN_AUG_ROT270 3
+#define CN_AUG_FLIPLR 4
+#define CN_AUG_FLIPUD 5
+#define CN_AUG_GAUSSIAN 6
+#define CN_AUG_SALTPEPPER 7
+#define CN_AUG_CROPRESIZE 8
+#define CN_AUG_PERLIN 9
+#define CN_AUG_NOPS 10
+
+#define CN_AUG_PLAN_WORDS 8
+#define CN_AUG_RMAX 10
+#define CN_AUG_PERLIN_FLOATS (4 * (CN_AUG_RMAX + 1) * (CN_AUG_RMAX + 1))
+#define CN_AUG_BR 32                        // output rows per block
+#define CN_AUG_TILE (32 * 33)               // rotation tile, padded against bank conflicts
+#define CN_AUG_MAX_LDS (64 * 1024)
+
+// raw value -> [lo, hi] float, the first step of the prologue (same arithmetic as cn_prepare_chips_kernel)
+template <typename TIn>
+struct CnAugLoad {
+  const TIn* p;
+  float scale, lo, hi;
+  __device__ __forceinline__ float operator()(long i) const {
+    const float v = (float)p[i] * scale;
+    return fminf(fmaxf(v, lo), hi);
+  }
+};
+
+// bdist / y arrive in any of the stored dtypes; the switch is uniform over the launch
+struct CnAugLoadAny {
+  const void* p;
+  int dtype;  // 0 f32, 1 i32, 2 i16, 3 u16
+  float scale, lo, hi;
+  __device__ __forceinline__ float operator()(long i) const {
+    float v;
+    switch (dtype) {
+      case 0: v = ((const float*)p)[i]; break;
+      case 1: v = (float)((const int*)p)[i]; break;
+      case 2: v = (float)((const short*)p)[i]; break;
+      default: v = (float)((const unsigned short*)p)[i]; break;
+    }
+    v *= scale;
+    return fminf(fmaxf(v, lo), hi);
+  }
+};
+
+struct CnAugLoadLabel {
+  const void* p;
+  int dtype;  // 1 i32, 2 i16, 3 u16, 4 i64
+  __device__ __forceinline__ long long operator()(long i) const {
+    switch (dtype) {
+      case 1: return ((const int*)p)[i];
+      case 2: return ((const short*)p)[i];
+      case 3: return ((const unsigned short*)p)[i];
+      default: return ((const long long*)p)[i];
+    }
+  }
+};
+
+// final clip + z-score (x), final clip (bdist: m = 0, inv = 1), or a plain store (labels)
+struct CnAugStore {
+  float* p;
+  float lo, hi, m, inv;
+  __device__ __forceinline__ void operator()(long i, float v) const { p[i] = (fminf(fmaxf(v, lo), hi) - m) * inv; }
+};
+struct CnAugStoreLabel {
+  long long* p;
+  __device__ __forceinline__ void operator()(long i, long long v) const { p[i] = v; }
+};
+
+struct CnAugCrop {
+  int div, top, left;
+};
+
+// The ops every tensor of a sample goes through: none, flips, rotations, crop + resize. One plane [H][W] at `base`,
+// output rows [r0, r1). V = float (bilinear resize) or long long (nearest resize). `tile` holds CN_AUG_TILE values.
+template <typename V, typename Ld, typename St>
+__device__ __forceinline__ void cn_aug_geometry(int op, const Ld& ld, const St& st, long base, int H, int W, int r0, int r1,
+                                                CnAugCrop crop, V* tile) {
+  const int tid = threadIdx.x;
+  const int n = (r1 - r0) * W;
+  if (op == CN_AUG_ROT90 || op == CN_AUG_ROT270) {
+    // H == W == N. The block's band of output rows is a band of input COLUMNS: it goes through a 32 x 32 LDS tile so
+    // that both the global reads and the global writes run along W.
+    const int N = W, ii = tid & 31, ty = tid >> 5;
+    for (int j0 = 0; j0 < N; j0 += 32) {
+      for (int jj = ty; jj < 32; jj += 8) {
+        if (r0 + ii < r1 && j0 + jj < N) {
+          const long src = op == CN_AUG_ROT90 ? (long)(j0 + jj) * N + (N - 1 - (r0 + ii))
+                                              : (long)(N - 1 - (j0 + jj)) * N + (r0 + ii);
+          tile[jj * 33 + ii] = ld(base + src);
+        }
+      }
+      __syncthreads();
+      for (int i2 = ty; i2 < 32; i2 += 8) {  // lane = output column j0 + (tid & 31)
+        if (r0 + i2 < r1 && j0 + ii < N) st(base + (long)(r0 + i2) * N + j0 + ii, tile[ii * 33 + i2]);
+      }
+      __syncthreads();
+    }
+    return;
+  }
+  if (op == CN_AUG_CROPRESIZE) {
+    // v2.RandomCrop((H // div, W // div)) at (top, left), then v2.Resize back to (H, W). torch's scales are float32.
+    const int ch = H / crop.div, cw = W / crop.div;
+    const float sh = (float)ch / (float)H, sw = (float)cw / (float)W;
+    const long cbase = base + (long)crop.top * W + crop.left;
+    for (int idx = tid; idx < n; idx += 256) {
+      const int h = r0 + idx / W, w = idx % W;
+      if constexpr (std::is_same<V, float>::value) {
+        // bilinear, align_corners = False: source = max((d + 0.5) * s - 0.5, 0), each step rounded to float32
+        const float fy = fmaxf(__fsub_rn(__fmul_rn((float)h + 0.5f, sh), 0.5f), 0.f);
+        const float fx = fmaxf(__fsub_rn(__fmul_rn((float)w + 0.5f, sw), 0.5f), 0.f);
+        const int y0 = min((int)fy, ch - 1), x0 = min((int)fx, cw - 1);
+        const int y1 = min(y0 + 1, ch - 1), x1 = min(x0 + 1, cw - 1);
+        const float ly = fy - (float)y0, lx = fx - (float)x0;
+        const float hy = 1.f - ly, hx = 1.f - lx;
+        const float v00 = ld(cbase + (long)y0 * W + x0), v01 = ld(cbase + (long)y0 * W + x1);
+        const float v10 = ld(cbase + (long)y1 * W + x0), v11 = ld(cbase + (long)y1 * W + x1);
+        st(base + (long)h * W + w, hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11));
+      } else {
+        // nearest: source = min(floor(d * s), size - 1) with the float32 product
+        const int y0 = min((int)floorf(__fmul_rn((float)h, sh)), ch - 1);
+        const int x0 = min((int)floorf(__fmul_rn((float)w, sw)), cw - 1);
+        st(base + (long)h * W + w, ld(cbase + (long)y0 * W + x0));
+      }
+    }
+    return;
+  }
+  const bool fh = op == CN_AUG_FLIPUD || op == CN_AUG_ROT180, fw = op == CN_AUG_FLIPLR || op == CN_AUG_ROT180;
+  if (!fh && !fw) {  // none: the band is one contiguous run
+    const long b0 = base + (long)r0 * W;
+    for (int idx = tid; idx < n; idx += 256) st(b0 + idx, ld(b0 + idx));
+    return;
+  }
+  for (int idx = tid; idx < n; idx += 256) {
+    const int h = r0 + idx / W, w = idx % W;
+    const int hs = fh ? H - 1 - h : h, ws = fw ? W - 1 - w : w;
+    st(base + (long)h * W + w, ld(base + (long)hs * W + ws));
+  }
+}
+
+// Plan rows come from the host, which has validated them (cn_augment_chips_f32); a row that does not fit the plane is
+// still never followed out of bounds: it degrades to `none`.
+__device__ __forceinline__ int cn_aug_checked_op(const int* __restrict__ row, int H, int W, bool have_perlin, CnAugCrop& crop) {
+  int op = row[0];
+  crop.div = row[1]; crop.top = row[2]; crop.left = row[3];
+  if (op < 0 || op >= CN_AUG_NOPS) op = CN_AUG_NONE;
+  if ((op == CN_AUG_ROT90 || op == CN_AUG_ROT270) && H != W) op = CN_AUG_NONE;
+  if (op == CN_AUG_CROPRESIZE) {
+    const int ch = crop.div > 0 ? H / crop.div : 0, cw = crop.div > 0 ? W / crop.div : 0;
+    if (ch < 1 || cw < 1 || crop.top < 0 || crop.left < 0 || crop.top + ch > H || crop.left + cw > W) op = CN_AUG_NONE;
+  }
+  if (op == CN_AUG_PERLIN) {
+    const int r = row[4];
+    if (!have_perlin || r < 1 || r > CN_AUG_RMAX || H % r != 0 || W % r != 0) op = CN_AUG_NONE;
+  }
+  if (op == CN_AUG_GAUSSIAN && (H < 2 || W < 2 || (CN_AUG_BR + 2) * (W + 2) * (int)sizeof(float) > CN_AUG_MAX_LDS)) op = CN_AUG_NONE;
+  return op;
+}
+
+// grid (bands, C * T, B); dynamic LDS: max(rotation tile, blur band, perlin gradients)
+template <typename TIn>
+__global__ __launch_bounds__(256) void cn_augment_x_kernel(const TIn* __restrict__ x, float* __restrict__ out,
+                                                          const int* __restrict__ plan, const float* __restrict__ perlin,
+                                                          const float* __restrict__ mean, const float* __restrict__ stdv,
+                                                          int T, int H, int W, float scale, float lo, float hi) {
+  extern __shared__ float smem[];
+  const int tid = threadIdx.x, plane = blockIdx.y, b = blockIdx.z;
+  const int c = plane / T, t = plane - c * T;
+  const int r0 = blockIdx.x * CN_AUG_BR, r1 = min(r0 + CN_AUG_BR, H);
+  const int* row = plan + (long)b * CN_AUG_PLAN_WORDS;
+  CnAugCrop crop;
+  const int op = cn_aug_checked_op(row, H, W, perlin != nullptr, crop);
+  const long HW = (long)H * W;
+  const long base = ((long)b * gridDim.y + plane) * HW;
+  const CnAugLoad<TIn> ld{x, scale, lo, hi};
+  const CnAugStore st{out, lo, hi, mean ? mean[c] : 0.f, stdv ? 1.0f / stdv[c] : 1.f};
+  const int n = (r1 - r0) * W;
+
+  if (op == CN_AUG_GAUSSIAN) {
+    // v2.GaussianBlur(kernel_size=3, sigma): taps exp(-0.5 (k / sigma)^2), k = -1, 0, 1, normalised; reflect padding.
+    // The band and its one-pixel halo are staged once; each output reads its 3 x 3 neighbourhood from LDS.
+    const float sigma = __int_as_float(row[5]);
+    const float e = expf(-0.5f / (sigma * sigma));
+    const float k1 = 1.0f / (1.0f + 2.0f * e), k0 = e * k1;
+    const int SW = W + 2, rows = r1 - r0 + 2;
+    for (int idx = tid; idx < rows * SW; idx += 256) {
+      int h = r0 - 1 + idx / SW, w = idx % SW - 1;
+      h = h < 0 ? -h : (h >= H ? 2 * H - 2 - h : h);
+      w = w < 0 ? -w : (w >= W ? 2 * W - 2 - w : w);
+      smem[idx] = ld(base + (long)h * W + w);
+    }
+    __syncthreads();
+    for (int idx = tid; idx < n; idx += 256) {
+      const int hl = idx / W, w = idx % W;
+      const float* p = smem + hl * SW + w;  // top-left of the 3 x 3 window
+      const float a = k0 * p[0] + k1 * p[1] + k0 * p[2];
+      const float m = k0 * p[SW] + k1 * p[SW + 1] + k0 * p[SW + 2];
+      const float z = k0 * p[2 * SW] + k1 * p[2 * SW + 1] + k0 * p[2 * SW + 2];
+      st(base + (long)(r0 + hl) * W + w, k0 * a + k1 * m + k0 * z);
+    }
+    return;
+  }
+  if (op == CN_AUG_SALTPEPPER) {
+    // x + 0.01 * n, n standard normal by Box-Muller on two 24-bit uniforms of the element's counter
+    // (u1 in (0, 1], u2 in [0, 1)); accurate logf / sqrtf / cosf: the test tolerance relies on them.
+    const unsigned long long seed = ((unsigned long long)(unsigned)row[7] << 32) | (unsigned)row[6];
+    for (int idx = tid; idx < n; idx += 256) {
+      const long off = (long)r0 * W + idx;
+      const unsigned long long i = (unsigned long long)(plane * HW + off);
+      const float u1 = (float)((cn_splitmix64(seed + 2ull * i) >> 40) + 1ull) * 0x1p-24f;
+      const float u2 = (float)(cn_splitmix64(seed + 2ull * i + 1ull) >> 40) * 0x1p-24f;
+      const float nrm = sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
+      st(base + off, ld(base + off) + 0.01f * nrm);
+    }
+    return;
+  }
+  if (op == CN_AUG_PERLIN) {
+    // generate_perlin_noise_3d(shape=(T, H, W), res=(1, r, r), out_range=(-0.03, 0.03)), augmenter_utils.py:211-360:
+    // corner gradients (sin phi cos theta, sin phi sin theta, cos phi), quintic interpolant, 0.06 * value.
+    const int r = row[4], R1 = r + 1, ng = 2 * R1 * R1;
+    const float* tab = perlin + (long)b * CN_AUG_PERLIN_FLOATS;
+    if (tid < ng) {
+      const float th = tab[tid], ph = tab[ng + tid];
+      const float sp = sinf(ph);
+      smem[3 * tid] = sp * cosf(th);
+      smem[3 * tid + 1] = sp * sinf(th);
+      smem[3 * tid + 2] = cosf(ph);
+    }
+    __syncthreads();
+    const int dH = H / r, dW = W / r;
+    const float ft = (float)t / (float)T;
+    const float qt = ft * ft * ft * (ft * (ft * 6.f - 15.f) + 10.f);
+    for (int idx = tid; idx < n; idx += 256) {
+      const int h = r0 + idx / W, w = idx % W;
+      const int ih = h / dH, iw = w / dW;
+      const float fh = (float)(h - ih * dH) / (float)dH, fw = (float)(w - iw * dW) / (float)dW;
+      const float qh = fh * fh * fh * (fh * (fh * 6.f - 15.f) + 10.f);
+      const float qw = fw * fw * fw * (fw * (fw * 6.f - 15.f) + 10.f);
+      float nv[2][2][2];
+#pragma unroll
+      for (int k = 0; k < 2; ++k)
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int d = 0; d < 2; ++d) {
+            const float* g = smem + 3 * ((k * R1 + ih + a) * R1 + iw + d);
+            nv[k][a][d] = (ft - (float)k) * g[0] + (fh - (float)a) * g[1] + (fw - (float)d) * g[2];
+          }
+      const float n00 = nv[0][0][0] * (1.f - qt) + qt * nv[1][0][0];
+      const float n10 = nv[0][1][0] * (1.f - qt) + qt * nv[1][1][0];
+      const float n01 = nv[0][0][1] * (1.f - qt) + qt * nv[1][0][1];
+      const float n11 = nv[0][1][1] * (1.f - qt) + qt * nv[1][1][1];
+      const float n0 = (1.f - qh) * n00 + qh * n10;
+      const float n1 = (1.f - qh) * n01 + qh * n11;
+      const long off = (long)h * W + w;
+      st(base + off, ld(base + off) + 0.06f * ((1.f - qw) * n0 + qw * n1));
+    }
+    return;
+  }
+  cn_aug_geometry<float>(op, ld, st, base, H, W, r0, r1, crop, smem);
+}
+
+// grid (bands, 2, B): blockIdx.y = 0 -> bdist (same geometry as x, no noise / blur, clip to [0, hi]), 1 -> labels
+__global__ __launch_bounds__(256) void cn_augment_target_kernel(const void* __restrict__ bdist, int bdtype,
+                                                               const void* __restrict__ y, int ydtype,
+                                                               float* __restrict__ bdist_out, long long* __restrict__ y_out,
+                                                               const int* __restrict__ plan, int H, int W, float scale,
+                                                               float lo, float hi) {
+  __shared__ long long tile[CN_AUG_TILE];
+  const int b = blockIdx.z;
+  const int r0 = blockIdx.x * CN_AUG_BR, r1 = min(r0 + CN_AUG_BR, H);
+  CnAugCrop crop;
+  int op = cn_aug_checked_op(plan + (long)b * CN_AUG_PLAN_WORDS, H, W, true, crop);
+  if (op == CN_AUG_GAUSSIAN || op == CN_AUG_SALTPEPPER || op == CN_AUG_PERLIN) op = CN_AUG_NONE;  // x only
+  const long base = (long)b * H * W;
+  if (blockIdx.y == 0) {
+    if (bdist == nullptr) return;
+    const CnAugLoadAny ld{bdist, bdtype, scale, lo, hi};
+    const CnAugStore st{bdist_out, 0.f, hi, 0.f, 1.f};
+    cn_aug_geometry<float>(op, ld, st, base, H, W, r0, r1, crop, (float*)tile);
+  } else {
+    const CnAugLoadLabel ld{y, ydtype};
+    const CnAugStoreLabel st{y_out};
+    cn_aug_geometry<long long>(op, ld, st, base, H, W, r0, r1, crop, tile);
+  }
+}
+
+// x: [B][C][T][H][W] raw (xdtype: 0 f32, 1 i32, 2 i16, 3 u16) -> x_out fp32, z-scored (mean / stdv nullable);
+// bdist: [B][H][W] raw (bdtype as xdtype; nullable together with bdist_out) -> bdist_out fp32 in [0, hi];
+// y: [B][H][W] labels (ydtype: 1 i32, 2 i16, 3 u16, 4 i64) -> y_out int64.
+// plan_host / plan_dev: the SAME [B][CN_AUG_PLAN_WORDS] table in host memory (validated here, before anything is
+// launched) and in device memory (read by the kernels); perlin_dev: [B][CN_AUG_PERLIN_FLOATS], nullable when no sample
+// is `perlin`. Two launches, no allocation, no synchronisation.
+extern "C" int cn_augment_chips_f32(const void* x, int xdtype, const void* bdist, int bdtype, const void* y, int ydtype,
+                                    float* x_out, float* bdist_out, long long* y_out, const int* plan_host,
+                                    const int* plan_dev, const float* perlin_dev, const float* mean, const float* stdv,
+                                    int B, int C, int T, int H, int W, float scale, float lo, float hi, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (B <= 0 || C <= 0 || T <= 0 || H <= 0 || W <= 0) return CN_OK;
+  if (x == nullptr || x_out == nullptr || y == nullptr || y_out == nullptr || plan_host == nullptr || plan_dev == nullptr) return CN_ERR_ARG;
+  if ((bdist == nullptr) != (bdist_out == nullptr)) return CN_ERR_ARG;
+  if (xdtype < 0 || xdtype > 3 || (bdist != nullptr && (bdtype < 0 || bdtype > 3)) || ydtype < 1 || ydtype > 4) return CN_ERR_ARG;
+  if ((long)C * T > 65535 || B > 65535) return CN_ERR_ARG;
+  bool blur = false;
+  for (int b = 0; b < B; ++b) {
+    const int* row = plan_host + (long)b * CN_AUG_PLAN_WORDS;
+    switch (row[0]) {
+      case CN_AUG_NONE: case CN_AUG_ROT180: case CN_AUG_FLIPLR: case CN_AUG_FLIPUD: case CN_AUG_SALTPEPPER: break;
+      case CN_AUG_ROT90: case CN_AUG_ROT270:
+        if (H != W) return CN_ERR_ARG;
+        break;
+      case CN_AUG_GAUSSIAN: {
+        float sigma;
+        __builtin_memcpy(&sigma, &row[5], sizeof(float));
+        if (!(sigma > 0.f) || H < 2 || W < 2) return CN_ERR_ARG;
+        blur = true;
+        break;
+      }
+      case CN_AUG_CROPRESIZE: {
+        const int div = row[1], top = row[2], left = row[3];
+        if (div <= 0) return CN_ERR_ARG;
+        const int ch = H / div, cw = W / div;
+        if (ch < 1 || cw < 1 || top < 0 || left < 0 || top + ch > H || left + cw > W) return CN_ERR_ARG;
+        break;
+      }
+      case CN_AUG_PERLIN: {
+        const int r = row[4];
+        if (perlin_dev == nullptr || r < 1 || r > CN_AUG_RMAX || H % r != 0 || W % r != 0) return CN_ERR_ARG;
+        break;
+      }
+      default: return CN_ERR_ARG;
+    }
+  }
+  size_t lds = CN_AUG_TILE * sizeof(float);  // covers the perlin gradients too: 2 * 11 * 11 * 3 floats
+  if (blur) {
+    const size_t band = (size_t)(CN_AUG_BR + 2) * (W + 2) * sizeof(float);
+    if (band > CN_AUG_MAX_LDS) return CN_ERR_LDS;
+    if (band > lds) lds = band;
+  }
+  const int bands = cn_cdiv(H, CN_AUG_BR);
+  const dim3 grid(bands, C * T, B), block(256);
+  switch (xdtype) {
+    case 0: CN_LAUNCH(cn_augment_x_kernel<float>, grid, block, lds, stream, (const float*)x, x_out, plan_dev, perlin_dev, mean, stdv, T, H, W, scale, lo, hi); break;
+    case 1: CN_LAUNCH(cn_augment_x_kernel<int>, grid, block, lds, stream, (const int*)x, x_out, plan_dev, perlin_dev, mean, stdv, T, H, W, scale, lo, hi); break;
+    case 2: CN_LAUNCH(cn_augment_x_kernel<short>, grid, block, lds, stream, (const short*)x, x_out, plan_dev, perlin_dev, mean, stdv, T, H, W, scale, lo, hi); break;
+    default: CN_LAUNCH(cn_augment_x_kernel<unsigned short>, grid, block, lds, stream, (const unsigned short*)x, x_out, plan_dev, perlin_dev, mean, stdv, T, H, W, scale, lo, hi); break;
+  }
+  int rc = cn_check_launch();
+  if (rc != CN_OK) return rc;
+  CN_LAUNCH(cn_augment_target_kernel, dim3(bands, 2, B), block, 0, stream, bdist, bdtype, y, ydtype, bdist_out, y_out,
+            plan_dev, H, W, scale, lo, hi);
+  return cn_check_launch();
+}

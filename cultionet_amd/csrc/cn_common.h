@@ -31,6 +31,15 @@ __device__ __forceinline__ unsigned long long cn_step_seed(unsigned long long se
   return step != nullptr ? seed + (*step) * 0xD1B54A32D192ED03ull : seed;
 }
 
+// Counter-based random bits: element i of a stream draws cn_splitmix64(seed + i) (64-bit wrap-around sum). Nothing is
+// stored: a later pass (dropout backward) or a host restatement recomputes the same bits from (seed, i).
+__device__ __forceinline__ unsigned long long cn_splitmix64(unsigned long long z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
 static inline int cn_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // ---- XCD-aware block order -------------------------------------------------------------------------------

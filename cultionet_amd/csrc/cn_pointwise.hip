@@ -593,13 +593,6 @@ extern "C" int cn_final_combine_bwd_f32(const float* ha, const float* hb, const 
 //   channelwise != 0: one decision per (b, c) plane (Dropout2d); else one per element (Dropout).
 // y = x * keep / (1 - p). Same entry point serves backward (x := dy, accumulate into dx).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long cn_splitmix64(unsigned long long z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
 __global__ __launch_bounds__(256) void cn_dropout_kernel(const float* __restrict__ x, long xbs, float* __restrict__ y,
                                                         long ybs, int C, int L, unsigned long long thresh,
                                                         float scale, unsigned long long seed_, const unsigned long long* __restrict__ step, int channelwise,

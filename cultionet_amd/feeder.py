@@ -12,6 +12,10 @@ host arithmetic and a synchronous copy would be what limits data-parallel scalin
     handed to the compute stream with ``record_stream`` so the caching allocator cannot recycle them early.
 
 Float batches (already prepared upstream) are copied and passed through untouched.
+
+``DeviceFeeder(..., augmenter=DeviceAugmenter(...))`` augments the labelled raw batches in the same place: the plan of
+each batch is drawn on the host, and ``cn_augment_chips_f32`` takes the place of the plain prologue on the copy stream
+(cultionet_amd.augment).
 """
 from __future__ import annotations
 
@@ -21,6 +25,9 @@ import torch
 
 from .data import Data
 from .edges import prepare_chips
+
+if T.TYPE_CHECKING:
+    from .augment import DeviceAugmenter
 
 
 def pin_batch(batch: Data) -> Data:
@@ -35,12 +42,13 @@ class DeviceFeeder:
     """``for batch in feeder.iterate(host_batches): step(batch)`` -- double-buffered host -> HBM feeding."""
 
     def __init__(self, device: T.Union[str, torch.device], mean: T.Optional[torch.Tensor] = None,
-                 std: T.Optional[torch.Tensor] = None):
+                 std: T.Optional[torch.Tensor] = None, augmenter: T.Optional["DeviceAugmenter"] = None):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("DeviceFeeder feeds a GPU (there is no CPU training path)")
         self.copy_stream = torch.cuda.Stream(device=self.device)
         self.mean, self.std = mean, std
+        self.augmenter = augmenter  # cultionet_amd.augment.DeviceAugmenter for TRAINING batches; None: no augmentation
 
     def _stage(self, host: Data) -> T.Tuple[Data, "torch.cuda.Event"]:
         """Enqueue copy + prologue of one batch on the copy stream; returns (device batch, ready event)."""
@@ -50,6 +58,11 @@ class DeviceFeeder:
             for k, v in host.__dict__.items():
                 kw[k] = v.to(dev, non_blocking=True) if isinstance(v, torch.Tensor) else v
             x = kw["x"]
+            if self.augmenter is not None and x.dtype != torch.float32 and kw.get("y") is not None:
+                ev = torch.cuda.Event()  # scale -> clip -> one augmentation per chosen sample -> clip -> z-score
+                out = self.augmenter.apply(Data(**kw), self.mean, self.std)
+                ev.record(self.copy_stream)
+                return out, ev
             if x.dtype != torch.float32:  # raw reflectances: x/10000 -> clip -> z-score, one pass on the device
                 kw["x"] = prepare_chips(x, self.mean, self.std)
             bd = kw.get("bdist")

@@ -111,6 +111,12 @@ class LightningModuleMixin(_Base):
         """Per-channel z-score statistics (NormValues, utils/normalize.py:63-82) applied by the device prologue."""
         self._norm_mean, self._norm_std = mean, std
 
+    def set_augmenter(self, augmenter) -> None:
+        """A cultionet_amd.augment.DeviceAugmenter (or None): raw labelled batches are augmented by the device prologue
+        while the module is in training mode. Validation, test and predict batches never are: the reference sets
+        augment_prob = 0 on every dataset but the training split (data/datasets.py:410-411)."""
+        self._augmenter = augmenter
+
     def on_after_batch_transfer(self, batch: Data, dataloader_idx: int = 0) -> Data:
         """Lightning hook, called once the batch is on the GPU. A batch whose ``x`` is still RAW (integer
         reflectances, as stored by the reference's .pt files) is scaled / clipped / z-scored here by one HIP pass
@@ -122,6 +128,9 @@ class LightningModuleMixin(_Base):
             return batch
         from .edges import SCALE_FACTOR, prepare_chips
 
+        aug = getattr(self, "_augmenter", None)
+        if aug is not None and self.training and getattr(batch, "y", None) is not None:
+            return aug.apply(batch, getattr(self, "_norm_mean", None), getattr(self, "_norm_std", None))
         batch.x = prepare_chips(x, getattr(self, "_norm_mean", None), getattr(self, "_norm_std", None))
         bd = getattr(batch, "bdist", None)
         if bd is not None and bd.dtype != torch.float32:

@@ -343,6 +343,21 @@ int cn_prepare_chips_f32(const void* x, int dtype, float* y, const float* mean, 
                          float scale, float lo, float hi, void* stream);
 int cn_predictions_to_u16(const float* dist, const float* edge, const float* crop, unsigned short* out, int B, int H,
                           int W, int pad_top, int pad_left, int h, int w, float scale, void* stream);
+/* Training augmentation fused into the prologue: replaces the per-sample CPU augmentation of EdgeDataset.get
+ * (data/datasets.py:443-488: scale + clip, one augmenter with probability augment_prob, AugmenterModule.__call__'s
+ * clips, augment/augmenters.py:25-35, then the NormValues z-score) for the nine augmenters that need no parcel
+ * labelling (augment/augmenters.py:166-330). Per sample b, plan row [op, div, top, left, r, sigma bits, seed lo, seed hi]
+ * (8 int32 words); op: 0 none, 1 rot90, 2 rot180, 3 rot270, 4 fliplr, 5 flipud, 6 gaussian, 7 saltpepper, 8 cropresize,
+ * 9 perlin. x [B][C][T][H][W] (xdtype as prepare) -> x_out fp32; bdist [B][H][W] (bdtype as prepare; null with bdist_out)
+ * -> bdist_out fp32 in [0, hi]; y [B][H][W] (ydtype 1 i32, 2 i16, 3 u16, 4 i64) -> y_out int64. plan_host and plan_dev
+ * are the same table in host memory (validated before any launch) and device memory (read by the kernels); perlin_dev:
+ * [B][484] floats, theta [2][r+1][r+1] then phi [2][r+1][r+1] (null when no sample is perlin). A sample with op none comes
+ * out bit-identical to cn_prepare_chips_f32. Two launches. CN_ERR_ARG: unknown op, crop outside the plane, rot90 / rot270
+ * with H != W, r not dividing H and W; CN_ERR_LDS: gaussian with a row band wider than 64 KiB of LDS. */
+int cn_augment_chips_f32(const void* x, int xdtype, const void* bdist, int bdtype, const void* y, int ydtype, float* x_out,
+                         float* bdist_out, long long* y_out, const int* plan_host, const int* plan_dev,
+                         const float* perlin_dev, const float* mean, const float* stdv, int B, int C, int T, int H, int W,
+                         float scale, float lo, float hi, void* stream);
 /* sliding-window predict (BASELINE configs[4]; data/create.py:176-212, data/store.py:69-100, callbacks.py:176-227):
  * window_chips: window n = crop [r0-pad, r0-pad+S) x [c0-pad, c0-pad+S) of the zero-extended scene [C*T][H][W]
  *   (stored dtype as prepare), scaled / clipped / z-scored into fp32 [nwin][C*T][S][S]; win_rc: DEVICE int [nwin][2].
