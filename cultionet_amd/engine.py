@@ -16,6 +16,8 @@ Design (MI355X-first, not torch.autograd):
 """
 from __future__ import annotations
 
+import bisect
+import struct
 import threading
 import contextlib
 import os
@@ -680,7 +682,57 @@ def give_grad(v: Var, g: torch.Tensor) -> None:
 # flat parameter store
 # ---------------------------------------------------------------------------
 
-_SUB_TABLES_KEPT = 8  # pack tables of partial repacks (ParamStore.repack_all) cached per set of changed parameters
+class PackFormat(T.NamedTuple):
+    """One layout of the implicit-GEMM weight copies: the single-pack and the batched entry point, the element count
+    of a copy of (T, K, N), its element type, and (wptr, dst ptr, T, K, N, sk, sn, st) -> the bytes of one record of
+    the batched entry point's descriptor table."""
+    pack: str
+    batched: str
+    elems: T.Callable[[int, int, int], int]
+    dtype: torch.dtype
+    record: T.Callable[..., bytes]
+
+
+def _pack_record_f32(wptr: int, dst: int, T_: int, K: int, N: int, sk: int, sn: int, st: int) -> bytes:
+    """CnPackDesc (csrc/cn_conv.hip), 64 bytes."""
+    kp, np_ = _lib.query("cn_conv_kpad", K), _lib.query("cn_conv_npad", N)
+    return struct.pack("<QQiiiiiiqqq", wptr, dst, T_, K, N, kp, np_, 0, sk, sn, st)
+
+
+def _pack_record_bf16(wptr: int, dst: int, T_: int, K: int, N: int, sk: int, sn: int, st: int) -> bytes:
+    """CnBPackDesc (csrc/cn_bconv.hip), 72 bytes (nscale = NULL)."""
+    return struct.pack("<QQiiiiiiqqqQ", wptr, dst, T_, K, N, (K + 15) // 16, (N + 31) // 32, 0, sk, sn, st, 0)
+
+
+PACK_F32 = PackFormat(  # [tap][Kpad][Npad] fp32
+    "cn_pack_weights_f32", "cn_pack_weights_batched_f32",
+    lambda T_, K, N: T_ * _lib.query("cn_conv_kpad", K) * _lib.query("cn_conv_npad", N),
+    torch.float32, _pack_record_f32)
+PACK_BF16 = PackFormat(  # bf16 MFMA fragments (mixed-precision path)
+    "cn_pack_weights_bf16", "cn_pack_weights_batched_bf16",
+    lambda T_, K, N: _lib.query("cn_bconv_packed_elems", T_, K, N),
+    torch.bfloat16, _pack_record_bf16)
+
+
+def select_packs(offsets: T.Sequence[int], spans: T.Sequence[T.Tuple[int, int]],
+                 dirty: T.Optional[T.AbstractSet[int]]) -> T.List[int]:
+    """Indices of the pack records to refresh: all of them (``dirty`` None), else those whose source -- elements
+    [lo, hi) of the flat buffer: a dense weight tensor, or adjacent ones (a declared group) -- overlaps a parameter in
+    ``dirty`` (parameter i starts at ``offsets[i]``, ascending)."""
+    if dirty is None:
+        return list(range(len(spans)))
+    out = []
+    for r, (lo, hi) in enumerate(spans):
+        i = max(bisect.bisect_right(offsets, lo) - 1, 0)
+        while i < len(offsets) and offsets[i] < hi:
+            if i in dirty:
+                out.append(r)
+                break
+            i += 1
+    return out
+
+
+_SUB_TABLES_KEPT = 8  # pack tables (ParamStore.repack_all) cached per set of changed parameters ("any" is one of them)
 
 
 class ParamStore:
@@ -721,14 +773,13 @@ class ParamStore:
         self.uid = next(ParamStore._serial)
         self._sig = self._signature()
         self._base = self.flat.data_ptr()
-        self._packs: T.List[T.Tuple] = []      # (PackedWeight, attr, dst tensor, w ptr, T, K, N, sk, sn, st)
-        self._pack_table: T.Optional[torch.Tensor] = None
-        self._packs16: T.List[T.Tuple] = []    # the same for the bf16 MFMA-fragment copies
-        self._pack_table16: T.Optional[torch.Tensor] = None
+        self._packs: T.List[T.Tuple] = []  # (PackFormat, dst tensor, w ptr, T, K, N, sk, sn, st): every registered copy
+        self.packed_version = self.version  # the parameter values the registered copies hold (repack_all)
         # parameters written since the last repack: None = any of them (a full repack), else a set of indices (the
         # optimizer step of a model with frozen parameters writes the trainable ones only)
         self._dirty: T.Optional[T.FrozenSet[int]] = None
-        self._sub_tables: T.Dict[T.Any, T.Tuple[T.Optional[torch.Tensor], int, T.Optional[torch.Tensor], int]] = {}
+        # dirty set -> [(batched entry point, device table, records)] of its repack, most recently used last
+        self._tables: T.Dict[T.Optional[T.FrozenSet[int]], T.List[T.Tuple[str, torch.Tensor, int]]] = {}
 
     @staticmethod
     def _with_contiguous_groups(module: torch.nn.Module, params: T.List[torch.nn.Parameter]) -> T.List[torch.nn.Parameter]:
@@ -808,95 +859,43 @@ class ParamStore:
             self._sig = sig
             self.bump()
 
-    def register_pack(self, pw, attr: str, dst: torch.Tensor, w: torch.Tensor, T_: int, K: int, N: int, sk: int,
+    def register_pack(self, fmt: PackFormat, dst: torch.Tensor, w: torch.Tensor, T_: int, K: int, N: int, sk: int,
                       sn: int, st: int) -> None:
-        self._packs.append((pw, attr, dst, w.data_ptr(), T_, K, N, sk, sn, st))
-        self._pack_table = None
+        self._packs.append((fmt, dst, w.data_ptr(), T_, K, N, sk, sn, st))
+        self._tables.clear()  # (they list the copies registered so far)
 
-    def register_pack16(self, pw, attr: str, dst: torch.Tensor, w: torch.Tensor, T_: int, K: int, N: int, sk: int,
-                        sn: int, st: int) -> None:
-        self._packs16.append((pw, attr, dst, w.data_ptr(), T_, K, N, sk, sn, st))
-        self._pack_table16 = None
-
-    def _sub_table(self, packs: T.List[T.Tuple], dirty: T.FrozenSet[int], fmt: str) -> T.Tuple[T.Optional[torch.Tensor], int]:
-        """(device table, count) of the pack records whose source weight overlaps a parameter in ``dirty``."""
-        import bisect
-        import struct
-
-        buf, cnt = bytearray(), 0
-        for (_pw, _attr, dst, wptr, T_, K, N, sk, sn, st) in packs:
+    def _build_tables(self, dirty: T.Optional[T.FrozenSet[int]]) -> T.List[T.Tuple[str, torch.Tensor, int]]:
+        """The descriptor tables that refresh the copies of the parameters in ``dirty``: bf16 first, then fp32 (the
+        order recorded plans hold), none for a precision without records."""
+        spans = []
+        for (_fmt, _dst, wptr, T_, K, N, *_strides) in self._packs:
             lo = (wptr - self._base) // 4
-            hi = lo + T_ * K * N  # (the source is a dense weight tensor, or adjacent ones: a declared group)
-            i = max(bisect.bisect_right(self.offsets, lo) - 1, 0)
-            hit = False
-            while i < len(self.offsets) and self.offsets[i] < hi:
-                if i in dirty:
-                    hit = True
-                    break
-                i += 1
-            if not hit:
-                continue
-            if fmt == "f32":
-                buf += struct.pack("<QQiiiiiiqqq", wptr, dst.data_ptr(), T_, K, N, _lib.query("cn_conv_kpad", K),
-                                   _lib.query("cn_conv_npad", N), 0, sk, sn, st)
-            else:
-                buf += struct.pack("<QQiiiiiiqqqQ", wptr, dst.data_ptr(), T_, K, N, (K + 15) // 16, (N + 31) // 32, 0,
-                                   sk, sn, st, 0)
-            cnt += 1
-        if not cnt:
-            return None, 0
-        return torch.frombuffer(buf, dtype=torch.uint8).clone().to(self.flat.device), cnt
+            spans.append((lo, lo + T_ * K * N))
+        chosen = [self._packs[i] for i in select_packs(self.offsets, spans, dirty)]
+        tables = []
+        for fmt in (PACK_BF16, PACK_F32):
+            recs = [fmt.record(wptr, dst.data_ptr(), *dims) for (f, dst, wptr, *dims) in chosen if f is fmt]
+            if recs:
+                table = torch.frombuffer(bytearray(b"".join(recs)), dtype=torch.uint8).clone().to(self.flat.device)
+                tables.append((fmt.batched, table, len(recs)))
+        return tables
 
     def repack_all(self) -> None:
         """Refresh the registered packed weight copies with ONE launch per precision (after the parameters changed):
         every copy, or -- when only known parameters changed (bump with a mask) -- the copies of those."""
         dirty = self._dirty
         self._dirty = frozenset()
-        if dirty is not None:
-            key = (dirty, len(self._packs), len(self._packs16))
-            sub = self._sub_tables.pop(key, None)
-            if sub is None:
-                sub = self._sub_table(self._packs, dirty, "f32") + self._sub_table(self._packs16, dirty, "bf16")
-            self._sub_tables[key] = sub  # most recently used last; a few trainable sets are kept (gradual unfreezing)
-            while len(self._sub_tables) > _SUB_TABLES_KEPT:
-                self._sub_tables.pop(next(iter(self._sub_tables)))
-            t32, n32, t16, n16 = sub
-            for sink in getattr(_state, "alloc_sinks", None) or ():  # a plan being recorded bakes the table pointers in:
-                sink.extend(t for t in (t32, t16) if t is not None)  # it keeps the tables alive past their eviction
-            if n16:
-                _lib.call("cn_pack_weights_batched_bf16", t16.data_ptr(), n16, _stream())
-            if n32:
-                _lib.call("cn_pack_weights_batched_f32", t32.data_ptr(), n32, _stream())
-            for (pw, *_rest) in self._packs16 + self._packs:
-                pw.version = self.version
-            return
-        if self._packs16:
-            if self._pack_table16 is None:
-                import struct
-
-                buf = bytearray()
-                for (_pw, _attr, dst, wptr, T_, K, N, sk, sn, st) in self._packs16:
-                    buf += struct.pack("<QQiiiiiiqqqQ", wptr, dst.data_ptr(), T_, K, N, (K + 15) // 16, (N + 31) // 32, 0,
-                                       sk, sn, st, 0)  # 72-byte CnBPackDesc records (nscale = NULL)
-                self._pack_table16 = torch.frombuffer(buf, dtype=torch.uint8).clone().to(self.flat.device)
-            _lib.call("cn_pack_weights_batched_bf16", self._pack_table16.data_ptr(), len(self._packs16), _stream())
-            for (pw, _attr, _dst, *_rest) in self._packs16:
-                pw.version = self.version
-        if not self._packs:
-            return
-        if self._pack_table is None:
-            import struct
-
-            buf = bytearray()
-            for (_pw, _attr, dst, wptr, T_, K, N, sk, sn, st) in self._packs:
-                kp = _lib.query("cn_conv_kpad", K)
-                np_ = _lib.query("cn_conv_npad", N)
-                buf += struct.pack("<QQiiiiiiqqq", wptr, dst.data_ptr(), T_, K, N, kp, np_, 0, sk, sn, st)
-            host = torch.frombuffer(buf, dtype=torch.uint8).clone()
-            self._pack_table = host.to(self.flat.device)
-        _lib.call("cn_pack_weights_batched_f32", self._pack_table.data_ptr(), len(self._packs), _stream())
-        for (pw, _attr, _dst, *_rest) in self._packs:
-            pw.version = self.version
+        self.packed_version = self.version
+        tables = self._tables.pop(dirty, None)
+        if tables is None:
+            tables = self._build_tables(dirty)
+        self._tables[dirty] = tables  # most recently used last; a few trainable sets are kept (gradual unfreezing)
+        while len(self._tables) > _SUB_TABLES_KEPT:
+            self._tables.pop(next(iter(self._tables)))
+        for sink in getattr(_state, "alloc_sinks", None) or ():  # a plan being recorded bakes the table pointers in:
+            sink.extend(t for (_name, t, _n) in tables)          # it keeps the tables alive past their eviction
+        for (name, t, n) in tables:
+            _lib.call(name, t.data_ptr(), n, _stream())
 
 
 SEG_CHUNK = 4096  # elements per chunk of the segmented optimizer kernels (CN_SEG_CHUNK in csrc/cn_optim.hip)
@@ -1017,15 +1016,28 @@ class PackedWeight:
         self.store_id = 0
 
 
-def _pack(pw: "PackedWeight", attr: str, w: torch.Tensor, T_: int, K: int, N: int, sk: int, sn: int,
-          st: int) -> torch.Tensor:
+def _pack(fmt: PackFormat, w: torch.Tensor, T_: int, K: int, N: int, sk: int, sn: int, st: int) -> torch.Tensor:
     """Pack now (first use) into a persistent buffer and register it for the batched per-step repack."""
-    kp = _lib.query("cn_conv_kpad", K)
-    np_ = _lib.query("cn_conv_npad", N)
-    out = _alloc(T_ * kp * np_, torch.float32, w.device)
-    _lib.call("cn_pack_weights_f32", w.data_ptr(), out.data_ptr(), T_, K, N, sk, sn, st, _stream())
-    current_store().register_pack(pw, attr, out, w, T_, K, N, sk, sn, st)
+    out = _alloc(fmt.elems(T_, K, N), fmt.dtype, w.device)
+    _lib.call(fmt.pack, w.data_ptr(), out.data_ptr(), T_, K, N, sk, sn, st, _stream())
+    current_store().register_pack(fmt, out, w, T_, K, N, sk, sn, st)
     return out
+
+
+def _bwd_data_dims(T_: int, K: int, N: int, sk: int, sn: int, st: int) -> T.Tuple[int, int, int, int, int, int]:
+    """The backward-data copy of a weight is the forward copy (T, K, N, sk, sn, st) with K and N exchanged."""
+    return (T_, N, K, sn, sk, st)
+
+
+def _pack_copies(fmt: PackFormat, w: torch.Tensor, fwd: T.Optional[torch.Tensor], bwd: T.Optional[torch.Tensor],
+                 need_bwd: bool, *dims: int) -> T.Tuple[torch.Tensor, T.Optional[torch.Tensor]]:
+    """(forward, backward-data) copies of ``w`` in one format: those given, the missing ones packed from the forward
+    ``dims`` (the backward-data copy only when asked for)."""
+    if fwd is None:
+        fwd = _pack(fmt, w, *dims)
+    if need_bwd and bwd is None:
+        bwd = _pack(fmt, w, *_bwd_data_dims(*dims))
+    return fwd, bwd
 
 
 def _sync_packs(pw: "PackedWeight") -> None:
@@ -1034,73 +1046,47 @@ def _sync_packs(pw: "PackedWeight") -> None:
     if pw.store_id != st.uid:  # parameters were re-flattened into a new store: drop copies of the old one
         pw.fwd = pw.bwd = pw.fwd16 = pw.bwd16 = None
         pw.store_id = st.uid
-    if pw.version != st.version:
-        if pw.fwd is None and pw.bwd is None and pw.fwd16 is None and pw.bwd16 is None:
-            pw.version = st.version
-        else:
-            st.repack_all()
+    if st.packed_version != st.version:
+        st.repack_all()
 
 
-def _pack16(pw: "PackedWeight", attr: str, w: torch.Tensor, T_: int, K: int, N: int, sk: int, sn: int,
-            st: int) -> torch.Tensor:
-    out = _alloc(_lib.query("cn_bconv_packed_elems", T_, K, N), torch.bfloat16, w.device)
-    _lib.call("cn_pack_weights_bf16", w.data_ptr(), out.data_ptr(), T_, K, N, sk, sn, st, _stream())
-    current_store().register_pack16(pw, attr, out, w, T_, K, N, sk, sn, st)
-    return out
-
-
-def packed_conv(mod, need_bwd: bool, bf16: bool = False) -> PackedWeight:
-    """Packed weights of an nn.Conv2d / nn.Linear-like module (weight [Cout][Cin][KH][KW])."""
+def _holder(mod) -> PackedWeight:
+    """The module's PackedWeight (created at first use), its registered copies current."""
     pw = mod.__dict__.get("_cn_packed")
     if pw is None:
         pw = PackedWeight()
         mod.__dict__["_cn_packed"] = pw
     _sync_packs(pw)
+    return pw
+
+
+def _fill(pw: PackedWeight, w: torch.Tensor, need_bwd: bool, bf16: bool, *dims: int) -> PackedWeight:
+    """The holder with the copies of one precision that a caller needs (forward ``dims``)."""
+    if bf16:
+        pw.fwd16, pw.bwd16 = _pack_copies(PACK_BF16, w, pw.fwd16, pw.bwd16, need_bwd, *dims)
+    else:
+        pw.fwd, pw.bwd = _pack_copies(PACK_F32, w, pw.fwd, pw.bwd, need_bwd, *dims)
+    return pw
+
+
+def packed_conv(mod, need_bwd: bool, bf16: bool = False) -> PackedWeight:
+    """Packed weights of an nn.Conv2d / nn.Linear-like module (weight [Cout][Cin][KH][KW])."""
     w = mod.weight
     cout, cin = w.shape[0], w.shape[1]
     taps = int(w[0, 0].numel()) if w.dim() > 2 else 1
-    if bf16:
-        if pw.fwd16 is None:
-            pw.fwd16 = _pack16(pw, "fwd16", w, taps, cin, cout, taps, cin * taps, 1)
-        if need_bwd and pw.bwd16 is None:
-            pw.bwd16 = _pack16(pw, "bwd16", w, taps, cout, cin, cin * taps, taps, 1)
-        return pw
-    if pw.fwd is None:
-        pw.fwd = _pack(pw, "fwd", w, taps, cin, cout, taps, cin * taps, 1)
-    if need_bwd and pw.bwd is None:
-        pw.bwd = _pack(pw, "bwd", w, taps, cout, cin, cin * taps, taps, 1)
-    return pw
+    return _fill(_holder(mod), w, need_bwd, bf16, taps, cin, cout, taps, cin * taps, 1)
 
 
 def packed_convT(mod, need_bwd: bool, bf16: bool = False, taps_as_channels: bool = False) -> PackedWeight:
     """Packed weights of an nn.ConvTranspose2d (weight [Cin][Cout][KH][KW]). ``taps_as_channels`` (fp32, stride >=
     kernel size, _conv_transpose2d_taps): the tensor as the [Cin][Cout*KH*KW] matrix of a 1x1 transposed convolution."""
-    pw = mod.__dict__.get("_cn_packed")
-    if pw is None:
-        pw = PackedWeight()
-        mod.__dict__["_cn_packed"] = pw
-    _sync_packs(pw)
     w = mod.weight
     cin, cout = w.shape[0], w.shape[1]
     taps = int(w[0, 0].numel())
     if taps_as_channels and not bf16:
         n = cout * taps
-        if pw.fwd is None:
-            pw.fwd = _pack(pw, "fwd", w, 1, cin, n, n, 1, 0)
-        if need_bwd and pw.bwd is None:
-            pw.bwd = _pack(pw, "bwd", w, 1, n, cin, 1, n, 0)
-        return pw
-    if bf16:
-        if pw.fwd16 is None:
-            pw.fwd16 = _pack16(pw, "fwd16", w, taps, cin, cout, cout * taps, taps, 1)
-        if need_bwd and pw.bwd16 is None:
-            pw.bwd16 = _pack16(pw, "bwd16", w, taps, cout, cin, taps, cout * taps, 1)
-        return pw
-    if pw.fwd is None:
-        pw.fwd = _pack(pw, "fwd", w, taps, cin, cout, cout * taps, taps, 1)
-    if need_bwd and pw.bwd is None:
-        pw.bwd = _pack(pw, "bwd", w, taps, cout, cin, taps, cout * taps, 1)
-    return pw
+        return _fill(_holder(mod), w, need_bwd, False, 1, cin, n, n, 1, 0)
+    return _fill(_holder(mod), w, need_bwd, bf16, taps, cin, cout, cout * taps, taps, 1)
 
 
 # ---------------------------------------------------------------------------
@@ -3481,32 +3467,27 @@ def _thin_conv3x3_bf16(x: Var, mods: T.Sequence, grouped: bool, dilation: int, o
         # copy-back launches (27 per step for the three towers)
         tw.view = all(m.weight.is_contiguous() and m.weight.data_ptr() == w0.data_ptr() + 4 * per * i
                       for i, m in enumerate(mods))
-        tw.fwd16 = _alloc(_lib.query("cn_bconv_packed_elems", 9, Cin, CPt), torch.bfloat16, xt.device)
-        tw.bwd16 = _alloc(_lib.query("cn_bconv_packed_elems", 9, CPt, Cin), torch.bfloat16, xt.device)
         if tw.view:
             o = (w0.data_ptr() - store._base) // 4
             tw.wcat = store.flat[o:o + n * per].view(CPt, Cin, 3, 3)
             tw.dwcat = None  # the flat gradient slice of the moment (the bridge swaps flat_grad): looked up at use
-            s = _stream()
-            _lib.call("cn_pack_weights_bf16", tw.wcat.data_ptr(), tw.fwd16.data_ptr(), 9, Cin, CPt, 9, Cin * 9, 1, s)
-            _lib.call("cn_pack_weights_bf16", tw.wcat.data_ptr(), tw.bwd16.data_ptr(), 9, CPt, Cin, Cin * 9, 9, 1, s)
-            store.register_pack16(tw, "fwd16", tw.fwd16, tw.wcat, 9, Cin, CPt, 9, Cin * 9, 1)
-            store.register_pack16(tw, "bwd16", tw.bwd16, tw.wcat, 9, CPt, Cin, Cin * 9, 9, 1)
-            tw.version = store.version
+            tw.fwd16, tw.bwd16 = _pack_copies(PACK_BF16, tw.wcat, None, None, True, 9, Cin, CPt, 9, Cin * 9, 1)
         else:
+            tw.fwd16 = _alloc(_lib.query("cn_bconv_packed_elems", 9, Cin, CPt), torch.bfloat16, xt.device)
+            tw.bwd16 = _alloc(_lib.query("cn_bconv_packed_elems", 9, CPt, Cin), torch.bfloat16, xt.device)
             tw.wcat = _alloc((CPt, Cin, 3, 3), torch.float32, xt.device)
             tw.dwcat = _alloc_like(tw.wcat)
         mods[0].__dict__["_cn_thin16"] = tw
-    if tw.version != store.version:
-        if tw.view:  # registered with the batched per-step repack: one launch for every layer of the model
+    if tw.view:  # registered with the batched per-step repack: one launch for every layer of the model
+        if store.packed_version != store.version:
             store.repack_all()
-        else:
-            s = _stream()
-            per = CP * Cin * 9
-            for i, m in enumerate(mods):
-                _lib.call("cn_copy_f32", m.weight.data_ptr(), per, tw.wcat[i * CP].data_ptr(), per, 1, per, 0, s)
-            _lib.call("cn_pack_weights_bf16", tw.wcat.data_ptr(), tw.fwd16.data_ptr(), 9, Cin, CPt, 9, Cin * 9, 1, s)
-            _lib.call("cn_pack_weights_bf16", tw.wcat.data_ptr(), tw.bwd16.data_ptr(), 9, CPt, Cin, Cin * 9, 9, 1, s)
+    elif tw.version != store.version:
+        s = _stream()
+        per = CP * Cin * 9
+        for i, m in enumerate(mods):
+            _lib.call("cn_copy_f32", m.weight.data_ptr(), per, tw.wcat[i * CP].data_ptr(), per, 1, per, 0, s)
+        _lib.call("cn_pack_weights_bf16", tw.wcat.data_ptr(), tw.fwd16.data_ptr(), 9, Cin, CPt, 9, Cin * 9, 1, s)
+        _lib.call("cn_pack_weights_bf16", tw.wcat.data_ptr(), tw.bwd16.data_ptr(), 9, CPt, Cin, Cin * 9, 9, 1, s)
         tw.version = store.version
     _lib.call("cn_conv2d_fwd_bf16", xt.data_ptr(), ld(xt), tw.fwd16.data_ptr(), None, y.data_ptr(), 0, CPt * HW, B, Cin,
               H, W, CPt, 3, 3, 1, dilation, dilation, 0, 1, None, _stream())

@@ -792,9 +792,7 @@ def test_conv_bn_act_fused_eval_bf16(case):
 def test_pack_weights_batched_bf16_matches_single(shape):
     """The LDS-tiled batched repack (fp32 masters -> bf16 MFMA fragments, all layers in one launch) against the plain
     gather pack, for the stride patterns of Conv2d fwd / bwd-data and ConvTranspose2d fwd / bwd-data: bit-identical."""
-    import struct
-
-    from cultionet_amd import _lib
+    from cultionet_amd import engine as E, _lib
 
     cout, cin, k = shape
     taps = k * k
@@ -809,8 +807,7 @@ def test_pack_weights_batched_bf16_matches_single(shape):
         a = torch.full((n,), float("nan"), dtype=BF, device=dev)
         b = torch.full((n,), float("nan"), dtype=BF, device=dev)
         _lib.call("cn_pack_weights_bf16", w.data_ptr(), a.data_ptr(), taps, K, N, sk, sn, 1, s)
-        buf += struct.pack("<QQiiiiiiqqqQ", w.data_ptr(), b.data_ptr(), taps, K, N, (K + 15) // 16, (N + 31) // 32, 0, sk,
-                           sn, 1, 0)
+        buf += E.PACK_BF16.record(w.data_ptr(), b.data_ptr(), taps, K, N, sk, sn, 1)
         singles.append(a)
         outs.append(b)
     table = torch.frombuffer(buf, dtype=torch.uint8).clone().to(dev)

@@ -13,7 +13,6 @@ takes bf16 operands rounded to nearest even, so a weight pack that truncates is 
 """
 import ctypes
 import os
-import struct
 import subprocess
 import sys
 
@@ -667,6 +666,8 @@ def test_conv_transpose2d_bf16_exact(B, Cin, H, W, Cout, s, acc):
 @pytest.mark.parametrize("cout,cin,k", [(31, 9, 3), (129, 72, 3), (40, 136, 1)])
 def test_pack_weights_batched_equal_single(cout, cin, k):
     """cn_pack_weights_batched_f32 / cn_pack_weights_batched_bf16 write what the single packs write, bit for bit."""
+    from cultionet_amd import engine as E
+
     dev = _dev()
     L, st = lib(), stream()
     T = k * k
@@ -676,14 +677,12 @@ def test_pack_weights_batched_equal_single(cout, cin, k):
     for (T_, K, N, sk, sn, s1) in pats:
         a = pack_f32(w, T_, K, N, sk, sn, s1)
         o = torch.full_like(a, float("nan"))
-        buf += struct.pack("<QQiiiiiiqqq", w.data_ptr(), o.data_ptr(), T_, K, N, L.query("cn_conv_kpad", K),
-                           L.query("cn_conv_npad", N), 0, sk, sn, s1)
+        buf += E.PACK_F32.record(w.data_ptr(), o.data_ptr(), T_, K, N, sk, sn, s1)
         singles.append(a)
         outs.append(o)
         a16 = pack_bf16(w, T_, K, N, sk, sn, s1)
         o16 = torch.full_like(a16, float("nan"))
-        buf16 += struct.pack("<QQiiiiiiqqqQ", w.data_ptr(), o16.data_ptr(), T_, K, N, (K + 15) // 16, (N + 31) // 32, 0,
-                             sk, sn, s1, 0)
+        buf16 += E.PACK_BF16.record(w.data_ptr(), o16.data_ptr(), T_, K, N, sk, sn, s1)
         singles16.append(a16)
         outs16.append(o16)
     t32 = torch.frombuffer(buf, dtype=torch.uint8).clone().to(dev)

@@ -1103,9 +1103,7 @@ def test_conv_autotune_gives_the_same_results():
 def test_pack_weights_batched_matches_single(shape):
     """The tile-transposed batched repack (all layers in one launch) against the plain gather pack, for the four
     stride patterns of include/cultionet_hip.h (Conv2d fwd / bwd-data, ConvTranspose2d fwd / bwd-data)."""
-    import struct
-
-    from cultionet_amd import _lib
+    from cultionet_amd import engine as E, _lib
 
     cout, cin, k = shape
     taps = k * k
@@ -1120,7 +1118,7 @@ def test_pack_weights_batched_matches_single(shape):
         a = torch.full((taps * kp * np_,), float("nan"), device=dev)
         b = torch.full((taps * kp * np_,), float("nan"), device=dev)
         _lib.call("cn_pack_weights_f32", w.data_ptr(), a.data_ptr(), taps, K, N, sk, sn, 1, s)
-        buf += struct.pack("<QQiiiiiiqqq", w.data_ptr(), b.data_ptr(), taps, K, N, kp, np_, 0, sk, sn, 1)
+        buf += E.PACK_F32.record(w.data_ptr(), b.data_ptr(), taps, K, N, sk, sn, 1)
         singles.append(a)
         outs.append(b)
     table = torch.frombuffer(buf, dtype=torch.uint8).clone().to(dev)
