@@ -7,8 +7,10 @@
 #include "cn_common.h"
 
 // ---------------------------------------------------------------------------
-// Pools. (1) per (b, c): mean and max over the L = H*W pixels (+ index of the first maximum);
-//        (2) per (b, pixel): mean and max over the C channels (+ channel of the first maximum) -> pooled [B][2][L].
+// Pools. (1) per (b, c): mean and max over the L = H*W pixels (+ index of the first maximum, as nn.AdaptiveMaxPool2d);
+//        (2) per (b, pixel): mean and max over the C channels -> pooled [B][2][L], + the number of channels that tie at
+//            the maximum: einops' 'max' is torch.amax, whose gradient is split EVENLY among them.
+// A NaN wins both maxima (ATen, and sb_max_nan of the bf16 kernels); the first one keeps the index.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void cn_sca_hw_pool_kernel(const float* __restrict__ x, long xbs, int C, int L,
                                                             float* __restrict__ avg, float* __restrict__ mx,
@@ -23,7 +25,7 @@ __global__ __launch_bounds__(256) void cn_sca_hw_pool_kernel(const float* __rest
   for (int l = threadIdx.x; l < L; l += 256) {
     const float v = xp[l];
     s += v;
-    if (v > m) { m = v; mi = l; }
+    if (v > m || (v != v && m == m)) { m = v; mi = l; }
   }
   s = cn_block_sum<float, 256>(s, scratch);
   sv[threadIdx.x] = m;
@@ -33,7 +35,9 @@ __global__ __launch_bounds__(256) void cn_sca_hw_pool_kernel(const float* __rest
     if (threadIdx.x < off) {
       const float o = sv[threadIdx.x + off];
       const int oi = si[threadIdx.x + off];
-      if (o > sv[threadIdx.x] || (o == sv[threadIdx.x] && oi < si[threadIdx.x])) {
+      const float m = sv[threadIdx.x];
+      const bool first = oi < si[threadIdx.x];
+      if (o != o ? (m == m || first) : (o > m || (o == m && first))) {
         sv[threadIdx.x] = o;
         si[threadIdx.x] = oi;
       }
@@ -48,58 +52,65 @@ __global__ __launch_bounds__(256) void cn_sca_hw_pool_kernel(const float* __rest
 }
 
 __global__ __launch_bounds__(256) void cn_sca_c_pool_kernel(const float* __restrict__ x, long xbs, int C, int L,
-                                                           float* __restrict__ pooled, int* __restrict__ cidx) {
+                                                           float* __restrict__ pooled, int* __restrict__ ccnt) {
   const int l = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
   if (l >= L) return;
   const float* xp = x + b * xbs + l;
   float s = 0.f, m = -INFINITY;
-  int mi = 0;
+  int n = 0;  // channels equal to m (0 when m is NaN: nothing compares equal, no channel takes the gradient)
   for (int c = 0; c < C; ++c) {
     const float v = xp[(long)c * L];
     s += v;
-    if (v > m) { m = v; mi = c; }
+    if (v > m || v != v) { m = v; n = 1; }
+    else if (v == m) ++n;
   }
   pooled[((long)b * 2 + 0) * L + l] = s / C;
   pooled[((long)b * 2 + 1) * L + l] = m;
-  cidx[(long)b * L + l] = mi;
+  ccnt[(long)b * L + l] = n;
 }
 
 extern "C" int cn_sca_pool_fwd_f32(const float* x, long xbs, int B, int C, int L, float* avg, float* mx, int* idx,
-                                   float* pooled, int* cidx, void* stream) {
+                                   float* pooled, int* ccnt, void* stream) {
   if (B <= 0 || C <= 0 || L <= 0) return CN_OK;
   CN_LAUNCH(cn_sca_hw_pool_kernel, dim3(C, B), dim3(256), 0, (hipStream_t)stream, x, xbs, C, L, avg, mx, idx);
   CN_LAUNCH(cn_sca_c_pool_kernel, dim3((L + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, x, xbs, C, L,
-                     pooled, cidx);
+                     pooled, ccnt);
   return cn_check_launch();
 }
 
-// d x[b,c,l] (+)= davg[b,c]/L + [l == idx[b,c]] dmx[b,c] + dpooled[b,0,l]/C + [c == cidx[b,l]] dpooled[b,1,l]
-__global__ __launch_bounds__(256) void cn_sca_pool_bwd_kernel(const float* __restrict__ davg,
+// d x[b,c,l] (+)= davg[b,c]/L + [l == idx[b,c]] dmx[b,c] + dpooled[b,0,l]/C
+//                  + [x[b,c,l] == pooled[b,1,l]] dpooled[b,1,l] / ccnt[b,l]        (ccnt == 1 without ties: exact)
+__global__ __launch_bounds__(256) void cn_sca_pool_bwd_kernel(const float* __restrict__ x, long xbs,
+                                                             const float* __restrict__ davg,
                                                              const float* __restrict__ dmx,
                                                              const int* __restrict__ idx,
+                                                             const float* __restrict__ pooled,
                                                              const float* __restrict__ dpooled,
-                                                             const int* __restrict__ cidx, float* __restrict__ dx,
+                                                             const int* __restrict__ ccnt, float* __restrict__ dx,
                                                              long dxbs, int C, int L, int accumulate) {
   const int c = blockIdx.y, b = blockIdx.z;
   const float da = davg[b * C + c] / L, dm = dmx[b * C + c];
   const int mi = idx[b * C + c];
+  const float* xp = x + b * xbs + (long)c * L;
   float* dp = dx + b * dxbs + (long)c * L;
   for (int l = blockIdx.x * 256 + threadIdx.x; l < L; l += gridDim.x * 256) {
     float g = da + (l == mi ? dm : 0.f) + dpooled[((long)b * 2) * L + l] / C +
-              (cidx[(long)b * L + l] == c ? dpooled[((long)b * 2 + 1) * L + l] : 0.f);
+              (xp[l] == pooled[((long)b * 2 + 1) * L + l]
+                   ? dpooled[((long)b * 2 + 1) * L + l] / (float)ccnt[(long)b * L + l]
+                   : 0.f);
     if (accumulate) g += dp[l];
     dp[l] = g;
   }
 }
 
-extern "C" int cn_sca_pool_bwd_f32(const float* davg, const float* dmx, const int* idx, const float* dpooled,
-                                   const int* cidx, float* dx, long dxbs, int B, int C, int L, int accumulate,
-                                   void* stream) {
+extern "C" int cn_sca_pool_bwd_f32(const float* x, long xbs, const float* davg, const float* dmx, const int* idx,
+                                   const float* pooled, const float* dpooled, const int* ccnt, float* dx, long dxbs,
+                                   int B, int C, int L, int accumulate, void* stream) {
   if (B <= 0 || C <= 0 || L <= 0) return CN_OK;
   int bx = (L + 1023) / 1024;
   if (bx < 1) bx = 1;
-  CN_LAUNCH(cn_sca_pool_bwd_kernel, dim3(bx, C, B), dim3(256), 0, (hipStream_t)stream, davg, dmx, idx, dpooled,
-                     cidx, dx, dxbs, C, L, accumulate);
+  CN_LAUNCH(cn_sca_pool_bwd_kernel, dim3(bx, C, B), dim3(256), 0, (hipStream_t)stream, x, xbs, davg, dmx, idx, pooled,
+                     dpooled, ccnt, dx, dxbs, C, L, accumulate);
   return cn_check_launch();
 }
 

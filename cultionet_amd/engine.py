@@ -2064,11 +2064,11 @@ def spatial_channel_attention(skip: Var, out: Var, mod) -> Var:
     avg, mx, ca = f(B, C), f(B, C), f(B, C)
     hpre_a, hpre_m = f(B, Ch), f(B, Ch)
     idx = _alloc((B, C), torch.int32, dev)
-    cidx = _alloc((B, L), torch.int32, dev)
+    ccnt = _alloc((B, L), torch.int32, dev)  # channels tied at the channel maximum of every pixel
     pooled = f(B, 2, H, W)
     s = _stream()
     _lib.call("cn_sca_pool_fwd_f32", st.data_ptr(), bstride(st), B, C, L, avg.data_ptr(), mx.data_ptr(), idx.data_ptr(),
-              pooled.data_ptr(), cidx.data_ptr(), s)
+              pooled.data_ptr(), ccnt.data_ptr(), s)
     _lib.call("cn_sca_mlp_fwd_f32", avg.data_ptr(), mx.data_ptr(), w1a.data_ptr(), w2a.data_ptr(), w1m.data_ptr(),
               w2m.data_ptr(), hpre_a.data_ptr(), hpre_m.data_ptr(), ca.data_ptr(), B, C, Ch, s)
     # one flag for the whole block: its fused kernels write every parameter gradient of the block together (frozen
@@ -2097,8 +2097,9 @@ def spatial_channel_attention(skip: Var, out: Var, mod) -> Var:
                     dpool = _alloc_like(pooled)
                     _lib.call("cn_fill_f32", dpool.data_ptr(), dpool.numel(), 0.0, s2)
                 dx, acc = grad_buffer(skip)
-                _lib.call("cn_sca_pool_bwd_f32", davg.data_ptr(), dmx.data_ptr(), idx.data_ptr(), dpool.data_ptr(),
-                          cidx.data_ptr(), dx.data_ptr(), bstride(dx), B, C, L, acc, s2)
+                _lib.call("cn_sca_pool_bwd_f32", st.data_ptr(), bstride(st), davg.data_ptr(), dmx.data_ptr(),
+                          idx.data_ptr(), pooled.data_ptr(), dpool.data_ptr(), ccnt.data_ptr(), dx.data_ptr(),
+                          bstride(dx), B, C, L, acc, s2)
             pv.grad = None
 
         tape.add(bwd_pool, (w1a, w2a, w1m, w2m))

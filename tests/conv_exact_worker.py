@@ -91,6 +91,20 @@ def assert_exact(got, ref, what):
                              f"got {float(got[idx])}, want {float(ref[idx])}")
 
 
+def bounded(got, ref, bound, what):
+    got = got.detach().double().cpu()
+    err = (got - ref).abs()
+    ratio = float((err / bound.clamp_min(1e-300)).max())
+    print(f"BOUND {what}: worst err/bound {ratio:.3f}")
+    assert bool((err <= bound).all()), f"{what}: err/bound {ratio:.3f}"
+
+
+def half_ulp_bf16(v):
+    """Half a bf16 ulp at |v| (as float64): spacing 2^(e-8) in the binade [2^(e-1), 2^e)."""
+    _, e = torch.frexp(v.abs())
+    return torch.ldexp(torch.ones_like(v), e - 9)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # device buffers
 # ---------------------------------------------------------------------------------------------------------------------

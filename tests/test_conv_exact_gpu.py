@@ -24,6 +24,8 @@ import torch.nn.functional as F
 from conv_exact_worker import (BF, F32, GARB, U32, Canvas, assert_exact, bf16_store, bwgrad_ws_floats,
                                check_conv_bf16, check_conv_f32, conv_workspace, ints, lib, out_size, pack_bf16,
                                pack_f32, premise, rb, ref_conv, ref_convT, stream, term_bound, wgrad_ws_f32)
+from conv_exact_worker import bounded as _bounded
+from conv_exact_worker import half_ulp_bf16 as _half_ulp_bf16
 
 pytestmark = pytest.mark.gpu
 
@@ -745,20 +747,6 @@ def test_forced_tile_split_sweep():
 # ---------------------------------------------------------------------------------------------------------------------
 # layer 2: random inputs, per-element float64 bounds
 # ---------------------------------------------------------------------------------------------------------------------
-
-def _bounded(got, ref, bound, what):
-    got = got.detach().double().cpu()
-    err = (got - ref).abs()
-    ratio = float((err / bound.clamp_min(1e-300)).max())
-    print(f"BOUND {what}: worst err/bound {ratio:.3f}")
-    assert bool((err <= bound).all()), f"{what}: err/bound {ratio:.3f}"
-
-
-def _half_ulp_bf16(v):
-    """Half a bf16 ulp at |v| (as float64): spacing 2^(e-8) in the binade [2^(e-1), 2^e)."""
-    _, e = torch.frexp(v.abs())
-    return torch.ldexp(torch.ones_like(v), e - 9)
-
 
 def _randn(shape, seed, scale=1.0):
     g = torch.Generator().manual_seed(seed)

@@ -11,6 +11,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from pointwise_ref import sca_ref64 as _sca_ref64
+
 pytestmark = pytest.mark.gpu
 
 BF = torch.bfloat16
@@ -181,24 +183,6 @@ def test_sca_apply_fwd_bwd_bf16(B, C, H, W, ld, few):
               B, C, L, _s())
     torch.cuda.synchronize()
     assert torch.equal(d2, dca) and torch.equal(g2, g3)
-
-
-def _sca_ref64(mod, skip, out):
-    """The reference's SpatialChannelAttention applied as ResidualAConv does, in float64 (torch.amax channel max,
-    nn.AdaptiveMaxPool2d(1) H*W max)."""
-    fc1, fc2 = mod.channel_attention.fc1, mod.channel_attention.fc2
-    w = lambda m: m.weight.detach().double().requires_grad_(True)
-    w1a, w2a, w1m, w2m, wc = w(fc1[0]), w(fc1[2]), w(fc2[0]), w(fc2[2]), w(mod.spatial_attention.conv)
-    gamma = mod.gamma.detach().double().requires_grad_(True)
-    mlp = lambda v, a, b: F.conv2d(F.silu(F.conv2d(v, a)), b)
-    ca = torch.sigmoid(mlp(skip.mean((2, 3), keepdim=True), w1a, w2a) + mlp(F.adaptive_max_pool2d(skip, 1), w1m, w2m))
-    pooled = torch.cat([skip.mean(1, keepdim=True), skip.amax(1, keepdim=True)], 1)
-    sa = torch.sigmoid(F.conv2d(pooled, wc, padding=1))
-    y = out * (1.0 + gamma * ((ca + sa) * 0.5))
-    names = {"channel_attention.fc1.0.weight": w1a, "channel_attention.fc1.2.weight": w2a,
-             "channel_attention.fc2.0.weight": w1m, "channel_attention.fc2.2.weight": w2m,
-             "spatial_attention.conv.weight": wc, "gamma": gamma}
-    return y, names
 
 
 @pytest.mark.parametrize("B,C,H,W,few", [(2, 32, 28, 28, False), (1, 96, 25, 25, True), (2, 128, 50, 50, False),
