@@ -4,13 +4,13 @@
 //   spatial:  sa[b,hw] = sigmoid( conv3x3_{2->1}( [mean_c x, max_c x] ) )        (the 3x3 conv runs on cn_thin_*)
 //   out      *= 1 + gamma * 0.5 * (ca + sa)
 // All HBM-bound streaming / reduction kernels over NCHW planes; the C x C/2 matrices are tiny (one block per sample).
-#include "cn_common.h"
+#include "cn_index.h"
 
 // ---------------------------------------------------------------------------
 // Pools. (1) per (b, c): mean and max over the L = H*W pixels (+ index of the first maximum, as nn.AdaptiveMaxPool2d);
 //        (2) per (b, pixel): mean and max over the C channels -> pooled [B][2][L], + the number of channels that tie at
 //            the maximum: einops' 'max' is torch.amax, whose gradient is split EVENLY among them.
-// A NaN wins both maxima (ATen, and sb_max_nan of the bf16 kernels); the first one keeps the index.
+// A NaN wins both maxima (ATen; cn_max_takes for the channel maximum); the first one keeps the index.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void cn_sca_hw_pool_kernel(const float* __restrict__ x, long xbs, int C, int L,
                                                             float* __restrict__ avg, float* __restrict__ mx,
@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256) void cn_sca_c_pool_kernel(const float* __restr
   for (int c = 0; c < C; ++c) {
     const float v = xp[(long)c * L];
     s += v;
-    if (v > m || v != v) { m = v; n = 1; }
+    if (cn_max_takes(m, v)) { m = v; n = 1; }
     else if (v == m) ++n;
   }
   pooled[((long)b * 2 + 0) * L + l] = s / C;

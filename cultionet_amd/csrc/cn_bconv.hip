@@ -22,6 +22,7 @@
 // the pixel image is staged once per 32-channel chunk and shared by the four waves and all taps.
 #include <cstdlib>
 #include "cn_bf16.h"
+#include "cn_conv_geom.h"
 #include "cn_profile.h"
 #include "cn_ticket.h"
 
@@ -844,8 +845,6 @@ extern "C" int cn_pack_weights_scaled_bf16(const float* w, const float* nscale, 
 // ------------------------------------------------------------------------------------------------------------
 // host side: classes, tiles, launch
 // ------------------------------------------------------------------------------------------------------------
-static inline int cnb_floordiv(int a, int b) { return (a >= 0) ? a / b : -((-a + b - 1) / b); }
-
 // Pixel tile (TH x TW <= max_pix = 128 / 256 / 512 for WN = 4 / 2 / 1) for a logical grid: exact covers first
 // (5x25, 10x25 and 20x25 cover 100, 50 and 25 exactly).
 static void cnb_pick_tile(int Hg, int Wg, int is, int span, int max_pix, int& TH, int& TW) {
@@ -1074,13 +1073,10 @@ static int cnb_gather(int G, const bf16_t* const* xs, long ldx, const bf16_t* co
   for (int i = 0; i < G; ++i) {
     if (dils[i] < 1) return CN_ERR_ARG;
     CnBClass& k = g.cls[i];
-    k.grp = i; k.Hg = Hout; k.Wg = Wout; k.oy0 = 0; k.ox0 = 0; k.ntaps = KH * KW;
-    for (int ky = 0; ky < KH; ++ky)
-      for (int kx = 0; kx < KW; ++kx) {
-        const int t = ky * KW + kx;
-        k.doff[t] = cnb_pack_d(ky * dils[i] - pads[i], kx * dils[i] - pads[i]);
-        k.wt[t] = t;
-      }
+    k.grp = i; k.Hg = Hout; k.Wg = Wout; k.oy0 = 0; k.ox0 = 0;
+    int dy[CNB_MAX_TAPS], dx[CNB_MAX_TAPS];
+    k.ntaps = cn_gather_taps(KH, KW, pads[i], dils[i], dy, dx, k.wt);
+    for (int t = 0; t < k.ntaps; ++t) k.doff[t] = cnb_pack_d(dy[t], dx[t]);
   }
   const double flops = 2.0 * B * Hout * Wout * (double)Cout * Cin * KH * KW * G;
   return cnb_launch(g, G, stream, flops, fin);
@@ -1113,36 +1109,20 @@ static int cnb_scatter(int G, const bf16_t* const* srcs, long lds_, const bf16_t
         CnBClass& k = g.cls[nc];
         k = CnBClass{};
         k.grp = gi;
-        k.Hg = (Ho - py + stride - 1) / stride;
-        k.Wg = (Wo - px + stride - 1) / stride;
+        k.Hg = cn_parity_extent(Ho, py, stride);
+        k.Wg = cn_parity_extent(Wo, px, stride);
         if (k.Hg <= 0 || k.Wg <= 0) continue;
         k.oy0 = py; k.ox0 = px;
-        int nt = 0;
-        for (int ky = 0; ky < KH; ++ky) {
-          const int ny = py + pad - ky * dil;
-          if (((ny % stride) + stride) % stride != 0) continue;
-          for (int kx = 0; kx < KW; ++kx) {
-            const int nx = px + pad - kx * dil;
-            if (((nx % stride) + stride) % stride != 0) continue;
-            k.doff[nt] = cnb_pack_d(cnb_floordiv(ny, stride), cnb_floordiv(nx, stride));
-            k.wt[nt] = ky * KW + kx;
-            ++nt;
-          }
-        }
-        k.ntaps = nt;
-        macs += (double)k.Hg * k.Wg * nt;
+        int dy[CNB_MAX_TAPS], dx[CNB_MAX_TAPS];
+        k.ntaps = cn_parity_taps(py, px, KH, KW, stride, pad, dil, dy, dx, k.wt);
+        for (int t = 0; t < k.ntaps; ++t) k.doff[t] = cnb_pack_d(dy[t], dx[t]);
+        macs += (double)k.Hg * k.Wg * k.ntaps;
         ++nc;
       }
   }
   g.ncls = nc;
   if (nc == 0) return CN_OK;
-  // heavy parity classes first, interleaved per cell tile when their tile counts agree (round 6, as in cn_conv.hip)
-  for (int i = 1; i < nc; ++i) {
-    const CnBClass key = g.cls[i];
-    int j = i - 1;
-    while (j >= 0 && g.cls[j].ntaps < key.ntaps) { g.cls[j + 1] = g.cls[j]; --j; }
-    g.cls[j + 1] = key;
-  }
+  cn_sort_heavy_first(g.cls, nc);  // interleaved per cell tile by cnb_launch when the classes' tile counts agree
   // (batch 32, 128 -> 128: 50^2 -> 99^2 63.1 -> 57.6 us, 25^2 -> 49^2 24.8 -> 23.0, the stride-4 25^2 -> 97^2 47.1 -> 37.1 us
   // alone; bf16 step 2203.6 -> 2210.1 chips/s same box)
   g.interleave = stride > 1 ? 1 : 0;
@@ -1153,8 +1133,8 @@ static int cnb_scatter(int G, const bf16_t* const* srcs, long lds_, const bf16_t
 extern "C" int cn_conv2d_stats_rows_bf16(int B, int Hin, int Win, int Cout, int KH, int KW, int stride, int pad,
                                          int dil) {
   if (stride < 1 || dil < 1) return -1;
-  const int Hout = (Hin + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
-  const int Wout = (Win + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
+  const int Hout = cn_conv_out(Hin, KH, stride, pad, dil);
+  const int Wout = cn_conv_out(Win, KW, stride, pad, dil);
   if (Hout <= 0 || Wout <= 0) return 0;
   const int NT = (Cout + 31) / 32;
   const int WN = NT >= 4 ? 4 : (NT >= 2 ? 2 : 1);
@@ -1173,8 +1153,8 @@ extern "C" int cn_conv2d_fwd_bf16(const void* x, long ldx, const void* wp, const
                                   long y_bs, int B, int Cin, int Hin, int Win, int Cout, int KH, int KW, int stride,
                                   int pad, int dil, int accumulate, int out_kind, float* stats, void* stream) {
   if (stride < 1) return CN_ERR_ARG;
-  const int Hout = (Hin + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
-  const int Wout = (Win + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
+  const int Hout = cn_conv_out(Hin, KH, stride, pad, dil);
+  const int Wout = cn_conv_out(Win, KW, stride, pad, dil);
   const bf16_t* xs = (const bf16_t*)x;
   const bf16_t* ws = (const bf16_t*)wp;
   return cnb_gather(1, &xs, ldx, &ws, &bias, &y, ldy, y_bs, B, Cin, Hin, Win, Cout, Hout, Wout, KH, KW, stride, &pad,
@@ -1191,8 +1171,8 @@ extern "C" int cn_conv2d_fwd_fused_bf16(const void* x, long ldx, const void* wp,
                                         long ldres, void* y, long ldy, int B, int Cin, int Hin, int Win, int Cout, int KH,
                                         int KW, int stride, int pad, int dil, int act, void* stream) {
   if (stride < 1 || (Cout & 7) || act < 0 || act > 1) return CN_ERR_ARG;
-  const int Hout = (Hin + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
-  const int Wout = (Win + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
+  const int Hout = cn_conv_out(Hin, KH, stride, pad, dil);
+  const int Wout = cn_conv_out(Win, KW, stride, pad, dil);
   const bf16_t* xs = (const bf16_t*)x;
   const bf16_t* ws = (const bf16_t*)wp;
   const bf16_t* rs = (const bf16_t*)res;
@@ -1205,11 +1185,11 @@ extern "C" int cn_conv2d_fwd_grouped_bf16(int G, const void* const* xs, long ldx
                                           int Hin, int Win, int Cout, int KH, int KW, int stride, const int* pads,
                                           const int* dils, int accumulate, float* const* stats, void* stream) {
   if (stride < 1 || G < 1 || G > CNB_MAX_GROUPS) return CN_ERR_ARG;
-  const int Hout = (Hin + 2 * pads[0] - dils[0] * (KH - 1) - 1) / stride + 1;
-  const int Wout = (Win + 2 * pads[0] - dils[0] * (KW - 1) - 1) / stride + 1;
+  const int Hout = cn_conv_out(Hin, KH, stride, pads[0], dils[0]);
+  const int Wout = cn_conv_out(Win, KW, stride, pads[0], dils[0]);
   for (int i = 1; i < G; ++i)
-    if ((Hin + 2 * pads[i] - dils[i] * (KH - 1) - 1) / stride + 1 != Hout ||
-        (Win + 2 * pads[i] - dils[i] * (KW - 1) - 1) / stride + 1 != Wout)
+    if (cn_conv_out(Hin, KH, stride, pads[i], dils[i]) != Hout ||
+        cn_conv_out(Win, KW, stride, pads[i], dils[i]) != Wout)
       return CN_ERR_ARG;
   return cnb_gather(G, (const bf16_t* const*)xs, ldx, (const bf16_t* const*)wps, biases, ys, ldy, 0, B, Cin, Hin, Win,
                     Cout, Hout, Wout, KH, KW, stride, pads, dils, accumulate, 0, stats, (hipStream_t)stream);
@@ -1231,11 +1211,11 @@ extern "C" int cn_conv2d_fwd_grouped_bnstats_bf16(int G, const void* const* xs, 
   if (stride < 1 || G < 1 || G > CNB_MAX_GROUPS || stats == nullptr || means == nullptr || rstds == nullptr ||
       finalized == nullptr || (running_means == nullptr) != (running_vars == nullptr))
     return CN_ERR_ARG;
-  const int Hout = (Hin + 2 * pads[0] - dils[0] * (KH - 1) - 1) / stride + 1;
-  const int Wout = (Win + 2 * pads[0] - dils[0] * (KW - 1) - 1) / stride + 1;
+  const int Hout = cn_conv_out(Hin, KH, stride, pads[0], dils[0]);
+  const int Wout = cn_conv_out(Win, KW, stride, pads[0], dils[0]);
   for (int i = 1; i < G; ++i)
-    if ((Hin + 2 * pads[i] - dils[i] * (KH - 1) - 1) / stride + 1 != Hout ||
-        (Win + 2 * pads[i] - dils[i] * (KW - 1) - 1) / stride + 1 != Wout)
+    if (cn_conv_out(Hin, KH, stride, pads[i], dils[i]) != Hout ||
+        cn_conv_out(Win, KW, stride, pads[i], dils[i]) != Wout)
       return CN_ERR_ARG;
   CnBFinReq fin = {means, rstds, running_means, running_vars, momentum, eps, bn_ws, bn_ws_floats, 0};
   const int rc = cnb_gather(G, (const bf16_t* const*)xs, ldx, (const bf16_t* const*)wps, nullptr, ys, ldy, 0, B, Cin, Hin,
@@ -1250,8 +1230,8 @@ extern "C" int cn_conv2d_bwd_data_bf16(const void* dy, long lddy, const void* wp
                                        int Hin, int Win, int Cout, int KH, int KW, int stride, int pad, int dil,
                                        int accumulate, void* stream) {
   if (stride < 1) return CN_ERR_ARG;
-  const int Hout = (Hin + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
-  const int Wout = (Win + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
+  const int Hout = cn_conv_out(Hin, KH, stride, pad, dil);
+  const int Wout = cn_conv_out(Win, KW, stride, pad, dil);
   const bf16_t* s = (const bf16_t*)dy;
   const bf16_t* w = (const bf16_t*)wp_t;
   return cnb_scatter(1, &s, lddy, &w, nullptr, &dx, lddx, B, Cout, Hout, Wout, Cin, Hin, Win, KH, KW, stride, &pad,
@@ -1263,8 +1243,8 @@ extern "C" int cn_conv2d_bwd_data_grouped_bf16(int G, const void* const* dys, lo
                                                int KH, int KW, int stride, const int* pads, const int* dils,
                                                int accumulate, void* stream) {
   if (stride < 1 || G < 1 || G > CNB_MAX_GROUPS) return CN_ERR_ARG;
-  const int Hout = (Hin + 2 * pads[0] - dils[0] * (KH - 1) - 1) / stride + 1;
-  const int Wout = (Win + 2 * pads[0] - dils[0] * (KW - 1) - 1) / stride + 1;
+  const int Hout = cn_conv_out(Hin, KH, stride, pads[0], dils[0]);
+  const int Wout = cn_conv_out(Win, KW, stride, pads[0], dils[0]);
   return cnb_scatter(G, (const bf16_t* const*)dys, lddy, (const bf16_t* const*)wps_t, nullptr, dxs, lddx, B, Cout, Hout,
                      Wout, Cin, Hin, Win, KH, KW, stride, pads, dils, accumulate, nullptr, (hipStream_t)stream);
 }
@@ -1273,8 +1253,8 @@ extern "C" int cn_conv2d_bwd_data_grouped_bf16(int G, const void* const* dys, lo
 extern "C" int cn_conv_transpose2d_fwd_bf16(const void* x, long ldx, const void* wp, const float* bias, void* y,
                                             long ldy, int B, int Cin, int Hin, int Win, int Cout, int KH, int KW,
                                             int stride, int pad, int accumulate, void* stream) {
-  const int Hout = (Hin - 1) * stride - 2 * pad + KH;
-  const int Wout = (Win - 1) * stride - 2 * pad + KW;
+  const int Hout = cn_convt_out(Hin, KH, stride, pad, 0);
+  const int Wout = cn_convt_out(Win, KW, stride, pad, 0);
   const bf16_t* s = (const bf16_t*)x;
   const bf16_t* w = (const bf16_t*)wp;
   const int dil = 1;
@@ -1286,8 +1266,8 @@ extern "C" int cn_conv_transpose2d_fwd_bf16(const void* x, long ldx, const void*
 extern "C" int cn_conv_transpose2d_bwd_data_bf16(const void* dy, long lddy, const void* wp_t, void* dx, long lddx,
                                                  int B, int Cin, int Hin, int Win, int Cout, int KH, int KW,
                                                  int stride, int pad, int accumulate, void* stream) {
-  const int Hout = (Hin - 1) * stride - 2 * pad + KH;
-  const int Wout = (Win - 1) * stride - 2 * pad + KW;
+  const int Hout = cn_convt_out(Hin, KH, stride, pad, 0);
+  const int Wout = cn_convt_out(Win, KW, stride, pad, 0);
   const bf16_t* s = (const bf16_t*)dy;
   const bf16_t* w = (const bf16_t*)wp_t;
   const int dil = 1;

@@ -5,6 +5,7 @@
 // restated in oracle/na2d_ref.py), F.interpolate(bilinear, align_corners=True) (nn/functional.py:72-81), torch.cat /
 // residual adds (nn/modules/unet_parts.py:700-760).
 #include "cn_bf16.h"
+#include "cn_index.h"
 
 // ------------------------------------------------------------------------------------------------------------
 // layout / precision converters
@@ -182,15 +183,6 @@ extern "C" int cn_zero_bf16(void* dst, long ldd, long P, int C, void* stream) {
 // ------------------------------------------------------------------------------------------------------------
 // bilinear resize, align_corners=True (ATen fp32 index math; weights fp32, data bf16)
 // ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void bbl_src(int o, float scale, int in_size, int& i0, int& i1, float& l1) {
-#pragma clang fp contract(off)
-  const float src = scale * (float)o;
-  i0 = (int)src;
-  if (i0 > in_size - 1) i0 = in_size - 1;
-  i1 = i0 + ((i0 < in_size - 1) ? 1 : 0);
-  l1 = src - i0;
-}
-
 __global__ __launch_bounds__(256) void cn_bbilinear_fwd_kernel(const bf16_t* __restrict__ x, long ldx,
                                                               bf16_t* __restrict__ y, long ldy, int B, int C8, int Hi,
                                                               int Wi, int Ho, int Wo, float sh, float sw) {
@@ -204,8 +196,8 @@ __global__ __launch_bounds__(256) void cn_bbilinear_fwd_kernel(const bf16_t* __r
     const long b = t / Ho;
     int y0, y1, x0, x1;
     float ly, lx;
-    bbl_src(oy, sh, Hi, y0, y1, ly);
-    bbl_src(ox, sw, Wi, x0, x1, lx);
+    cn_bl_src(oy, sh, Hi, y0, y1, ly);
+    cn_bl_src(ox, sw, Wi, x0, x1, lx);
     const bf16_t* xb = x + (b * Hi * Wi) * ldx + cg * 8;
     float v00[8], v01[8], v10[8], v11[8], o[8];
     cn_unpack8(*reinterpret_cast<const u32x4*>(xb + ((long)y0 * Wi + x0) * ldx), v00);
@@ -217,45 +209,6 @@ __global__ __launch_bounds__(256) void cn_bbilinear_fwd_kernel(const bf16_t* __r
     for (int j = 0; j < 8; ++j) o[j] = hy * (hx * v00[j] + lx * v01[j]) + ly * (hx * v10[j] + lx * v11[j]);
     *reinterpret_cast<u32x4*>(y + po * ldy + cg * 8) = cn_pack8(o);
   }
-}
-
-// candidate output rows / columns reading input index i (<= 4 for resizes that shrink by less than 2x)
-__device__ __forceinline__ int bbl_candidates(int i, int in_size, int out_size, float scale, float inv_scale, int* idx,
-                                             float* wgt) {
-  int lo = (int)floorf((i - 1) * inv_scale) - 1, hi = (int)ceilf((i + 1) * inv_scale) + 1;
-  if (scale == 0.f) { lo = 0; hi = out_size - 1; }
-  lo = max(lo, 0);
-  hi = min(hi, out_size - 1);
-  // The outputs reading input index i are CONSECUTIVE (the source coordinate is monotonic; a zero weight can only be
-  // the first output of the run, whose source falls exactly on i - 1): the search only counts them and notes the first,
-  // the <= 4 weights are then recomputed with static register indices. (Storing idx[n] / wgt[n] from inside the search
-  // loop through an if-chain on n lost candidate 1 whenever a fourth one was found -- resizes growing by 1.5x..2x.)
-  int n = 0, first = 0;
-#pragma unroll 1
-  for (int o = lo; o <= hi; ++o) {
-    int i0, i1; float l1;
-    bbl_src(o, scale, in_size, i0, i1, l1);
-    float w = 0.f;
-    if (i0 == i) w += 1.f - l1;
-    if (i1 == i) w += l1;
-    if (w != 0.f) {
-      if (n == 0) first = o;
-      ++n;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const bool live = k < n;
-    const int o = live ? first + k : first;
-    int i0, i1; float l1;
-    bbl_src(o, scale, in_size, i0, i1, l1);
-    float w = 0.f;
-    if (i0 == i) w += 1.f - l1;
-    if (i1 == i) w += l1;
-    idx[k] = o;
-    wgt[k] = live ? w : 0.f;
-  }
-  return n;
 }
 
 // adjoint in gather form (deterministic): every input pixel sums the output pixels that read it
@@ -273,8 +226,8 @@ __global__ __launch_bounds__(256) void cn_bbilinear_bwd_kernel(const bf16_t* __r
     const long b = t / Hi;
     int oyv[4] = {0, 0, 0, 0}, oxv[4] = {0, 0, 0, 0};
     float wyv[4] = {0.f, 0.f, 0.f, 0.f}, wxv[4] = {0.f, 0.f, 0.f, 0.f};
-    const int ny = bbl_candidates(iy, Hi, Ho, sh, inv_sh, oyv, wyv);
-    const int nx = bbl_candidates(ix, Wi, Wo, sw, inv_sw, oxv, wxv);
+    const int ny = cn_bl_candidates(iy, Hi, Ho, sh, inv_sh, oyv, wyv);
+    const int nx = cn_bl_candidates(ix, Wi, Wo, sw, inv_sw, oxv, wxv);
     const bf16_t* db = dy + (b * Ho * Wo) * lddy + cg * 8;
     float acc[8];
 #pragma unroll
@@ -301,14 +254,14 @@ __global__ __launch_bounds__(256) void cn_bbilinear_bwd_kernel(const bf16_t* __r
       ox_lo = max(ox_lo, 0); ox_hi = min(ox_hi, Wo - 1);
       for (int oy = oy_lo; oy <= oy_hi; ++oy) {
         int y0, y1; float ly;
-        bbl_src(oy, sh, Hi, y0, y1, ly);
+        cn_bl_src(oy, sh, Hi, y0, y1, ly);
         float wy = 0.f;
         if (y0 == iy) wy += 1.f - ly;
         if (y1 == iy) wy += ly;
         if (wy == 0.f) continue;
         for (int ox = ox_lo; ox <= ox_hi; ++ox) {
           int x0, x1; float lx;
-          bbl_src(ox, sw, Wi, x0, x1, lx);
+          cn_bl_src(ox, sw, Wi, x0, x1, lx);
           float wx = 0.f;
           if (x0 == ix) wx += 1.f - lx;
           if (x1 == ix) wx += lx;
@@ -344,7 +297,7 @@ __global__ __launch_bounds__(256) void cn_bbilinear_fwd_rows_kernel(const bf16_t
   const int oy = blockIdx.x, b = blockIdx.y;
   int y0, y1;
   float ly;
-  bbl_src(oy, sh, Hi, y0, y1, ly);
+  cn_bl_src(oy, sh, Hi, y0, y1, ly);
   const float hy = 1.f - ly;
   const bf16_t* r0 = x + ((long)b * Hi + y0) * Wi * ldx;
   const bf16_t* r1 = x + ((long)b * Hi + y1) * Wi * ldx;
@@ -354,7 +307,7 @@ __global__ __launch_bounds__(256) void cn_bbilinear_fwd_rows_kernel(const bf16_t
     const int ox = i / C8, cg = i - ox * C8;
     int x0, x1;
     float lx;
-    bbl_src(ox, sw, Wi, x0, x1, lx);
+    cn_bl_src(ox, sw, Wi, x0, x1, lx);
     float v00[8], v01[8], v10[8], v11[8], o[8];
     cn_unpack8(*reinterpret_cast<const u32x4*>(r0 + (long)x0 * ldx + cg * 8), v00);
     cn_unpack8(*reinterpret_cast<const u32x4*>(r0 + (long)x1 * ldx + cg * 8), v01);
@@ -378,7 +331,7 @@ __device__ __forceinline__ int bbl_candidates_n(int i, int in_size, int out_size
 #pragma unroll 1
   for (int o = lo; o <= hi; ++o) {
     int i0, i1; float l1;
-    bbl_src(o, scale, in_size, i0, i1, l1);
+    cn_bl_src(o, scale, in_size, i0, i1, l1);
     float w = 0.f;
     if (i0 == i) w += 1.f - l1;
     if (i1 == i) w += l1;
@@ -472,10 +425,6 @@ static int bbl_max_candidates(int in_size, int out_size) {
   return (int)(2.0 / scale) + 2;
 }
 
-static inline float bbl_scale(int in_size, int out_size) {
-  return out_size > 1 ? (float)(in_size - 1) / (float)(out_size - 1) : 0.f;
-}
-
 extern "C" int cn_bilinear_fwd_bf16(const void* x, long ldx, void* y, long ldy, int B, int C, int Hi, int Wi, int Ho,
                                     int Wo, void* stream) {
   if (B <= 0 || C <= 0) return CN_OK;
@@ -483,11 +432,11 @@ extern "C" int cn_bilinear_fwd_bf16(const void* x, long ldx, void* y, long ldy, 
   if (Ho <= 0 || Wo <= 0 || Hi <= 0 || Wi <= 0) return CN_OK;
   if (B <= 65535 && (long)Wo * (C >> 3) < (1L << 30))
     CN_LAUNCH(cn_bbilinear_fwd_rows_kernel, dim3(Ho, B), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                       ldx, (bf16_t*)y, ldy, C >> 3, Hi, Wi, Ho, Wo, bbl_scale(Hi, Ho), bbl_scale(Wi, Wo));
+                       ldx, (bf16_t*)y, ldy, C >> 3, Hi, Wi, Ho, Wo, cn_bl_scale(Hi, Ho), cn_bl_scale(Wi, Wo));
   else
     CN_LAUNCH(cn_bbilinear_fwd_kernel, dim3(bops_blocks((long)B * Ho * Wo * (C >> 3))), dim3(256), 0,
                        (hipStream_t)stream, (const bf16_t*)x, ldx, (bf16_t*)y, ldy, B, C >> 3, Hi, Wi, Ho, Wo,
-                       bbl_scale(Hi, Ho), bbl_scale(Wi, Wo));
+                       cn_bl_scale(Hi, Ho), cn_bl_scale(Wi, Wo));
   return cn_check_launch();
 }
 
@@ -495,7 +444,7 @@ extern "C" int cn_bilinear_bwd_bf16(const void* dy, long lddy, void* dx, long ld
                                     int Ho, int Wo, int accumulate, void* stream) {
   if (B <= 0 || C <= 0) return CN_OK;
   if (C & 7) return CN_ERR_ARG;
-  const float sh = bbl_scale(Hi, Ho), sw = bbl_scale(Wi, Wo);
+  const float sh = cn_bl_scale(Hi, Ho), sw = cn_bl_scale(Wi, Wo);
   if (Ho <= 0 || Wo <= 0 || Hi <= 0 || Wi <= 0) return CN_OK;
   const float ish = sh > 0.f ? 1.f / sh : 0.f, isw = sw > 0.f ? 1.f / sw : 0.f;
   if (B <= 65535 && Wi <= BBL_MAXW && (long)Wi * (C >> 3) < (1L << 30) && bbl_max_candidates(Hi, Ho) <= BBL_MAXC &&
@@ -513,47 +462,13 @@ extern "C" int cn_bilinear_bwd_bf16(const void* dy, long lddy, void* dx, long ld
 // neighborhood attention core: qkv bf16 [B][H][W][3C] (channel = which*C + head*D + d), out bf16 [B][H][W][C];
 // attn / dattn fp32 [B][heads][9][H][W] (saved probabilities / dS scratch). One lane per (pixel, head), head fastest.
 // ------------------------------------------------------------------------------------------------------------
-#define NAB_K 3
-#define NAB_KK 9
-
-__device__ __forceinline__ int nab_window_start(int i, int len, int dil) {
-  if (dil <= 1) return max(i - 1, 0) + ((i + 1 >= len) ? (len - i - 2) : 0);
-  const int ni = i - dil;
-  if (ni < 0) return i % dil;
-  if (i + dil >= len) {
-    const int imodd = i % dil;
-    const int a = (len / dil) * dil;
-    const int b = len - a;
-    if (imodd < b) return len - b + imodd - 2 * dil;
-    return a + imodd - NAB_K * dil;
-  }
-  return ni;
-}
-
-// attn_drop (nn.Dropout on the soft-maxed logits): keep/(1-p) factor of tap t from the same counter hash as the fp32
-// kernels (cn_na2d.hip na_keep), recomputed in forward and backward; 1.0 when dropout is off.
-__device__ __forceinline__ unsigned long long nab_splitmix64(unsigned long long z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__device__ __forceinline__ float nab_keep(unsigned long long thresh, float scale, unsigned long long seed, long bh,
-                                          int t, int HW, int p) {
-  if (thresh == 0ull) return 1.0f;
-  const unsigned long long i = ((unsigned long long)bh * NAB_KK + t) * (unsigned long long)HW + p;
-  return nab_splitmix64(seed + i) >= thresh ? scale : 0.f;
-}
-static inline unsigned long long nab_thresh(float p) {
-  if (!(p > 0.f)) return 0ull;
-  const double t = (double)p * 18446744073709551616.0;  // p * 2^64
-  return t >= 18446744073709551615.0 ? ~0ull : (unsigned long long)t;
-}
+#define NAB_K CN_NA_K
+#define NAB_KK CN_NA_KK
 
 // ---- dropout on bf16 NHWC activations ---------------------------------------------------------------------------
 // nn.Dropout2d after the encoder blocks (convolution.py:495,511) and natten's proj_drop, on the mixed-precision path.
-// The SAME counter-based masks as cn_dropout_f32 (cn_pointwise.hip): channelwise: one decision per (b, c) from
-// splitmix64(seed + b*C + c); elementwise: splitmix64(seed + (b*C + c)*HW + pixel). y = x * keep / (1 - p); the same
+// Counter-based masks (cn_index.h): channelwise: one decision per (b, c) from cn_splitmix64(seed + b*C + c);
+// elementwise: cn_splitmix64(seed + (b*C + c)*HW + pixel). y = x * keep / (1 - p); the same
 // entry point serves backward (x := dy, accumulate into dx).
 __global__ __launch_bounds__(256) void cn_bdropout_kernel(const bf16_t* __restrict__ x, long ldx, bf16_t* __restrict__ y,
                                                          long ldy, long P, int C, int HW, unsigned long long thresh,
@@ -573,7 +488,7 @@ __global__ __launch_bounds__(256) void cn_bdropout_kernel(const bf16_t* __restri
     for (int j = 0; j < 8; ++j) {
       const unsigned long long plane = (unsigned long long)b * C + c0 + j;
       const unsigned long long ctr = channelwise ? plane : plane * (unsigned long long)HW + pix;
-      v[j] *= nab_splitmix64(seed + ctr) >= thresh ? scale : 0.f;
+      v[j] *= cn_splitmix64(seed + ctr) >= thresh ? scale : 0.f;
     }
     bf16_t* yp = y + row * ldy + c0;
     if (accumulate) {
@@ -596,7 +511,7 @@ extern "C" int cn_dropout_bf16(const void* x, long ldx, void* y, long ldy, int B
   long blocks = (n + 255) / 256;
   if (blocks > 16384) blocks = 16384;
   CN_LAUNCH(cn_bdropout_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, ldx,
-            (bf16_t*)y, ldy, P, C, HW, nab_thresh(p), 1.0f / (1.0f - p), seed, step, channelwise, accumulate);
+            (bf16_t*)y, ldy, P, C, HW, cn_dropout_thresh(p), 1.0f / (1.0f - p), seed, step, channelwise, accumulate);
   return cn_check_launch();
 }
 
@@ -637,7 +552,7 @@ __global__ __launch_bounds__(256) void cn_bna_fwd_kernel(const bf16_t* __restric
   const int p = (int)(bp % HW);
   const int b = (int)(bp / HW);
   const int y = p / W, x = p - y * W;
-  const int sy = nab_window_start(y, H, dil), sx = nab_window_start(x, W, dil);
+  const int sy = cn_na_window_start(y, H, dil), sx = cn_na_window_start(x, W, dil);
   const bf16_t* base = qkv + ((long)b * HW) * ldq + h * D;
   float q[D];
   nab_load<D>(base + (long)p * ldq, q);
@@ -667,7 +582,7 @@ __global__ __launch_bounds__(256) void cn_bna_fwd_kernel(const bf16_t* __restric
   for (int t = 0; t < NAB_KK; ++t) {
     lg[t] *= inv;
     if (attn != nullptr) ap[(long)t * HW] = lg[t];
-    lg[t] *= nab_keep(dthresh, dscale, dseed, (long)b * heads + h, t, HW, p);
+    lg[t] *= cn_na_keep(dthresh, dscale, dseed, (long)b * heads + h, t, HW, p);
     const int kp = (sy + (t / 3) * dil) * W + sx + (t % 3) * dil;
     float vv[D];
     nab_load<D>(base + (long)kp * ldq + 2 * C, vv);
@@ -696,7 +611,7 @@ __global__ __launch_bounds__(256) void cn_bna_bwd_q_kernel(const bf16_t* __restr
   const int p = (int)(bp % HW);
   const int b = (int)(bp / HW);
   const int y = p / W, x = p - y * W;
-  const int sy = nab_window_start(y, H, dil), sx = nab_window_start(x, W, dil);
+  const int sy = cn_na_window_start(y, H, dil), sx = cn_na_window_start(x, W, dil);
   const bf16_t* base = qkv + ((long)b * HW) * ldq + h * D;
   float g[D];
   nab_load<D>(dout + ((long)b * HW + p) * ldo + h * D, g);
@@ -711,7 +626,7 @@ __global__ __launch_bounds__(256) void cn_bna_bwd_q_kernel(const bf16_t* __restr
     float s = 0.f;
 #pragma unroll
     for (int d = 0; d < D; ++d) s += g[d] * vv[d];
-    s *= nab_keep(dthresh, dscale, dseed, (long)b * heads + h, t, HW, p);
+    s *= cn_na_keep(dthresh, dscale, dseed, (long)b * heads + h, t, HW, p);
     dp[t] = s;
     pr[t] = ap[(long)t * HW];
     dot += pr[t] * s;
@@ -765,18 +680,18 @@ __global__ __launch_bounds__(256) void cn_bna_bwd_kv_kernel(const bf16_t* __rest
   for (int my = -2; my <= 2; ++my) {
     const int qy = y + my * dil;
     if (qy < 0 || qy >= H) continue;
-    const int offy = y - nab_window_start(qy, H, dil);
+    const int offy = y - cn_na_window_start(qy, H, dil);
     if (offy < 0 || offy > 2 * dil) continue;
     const int ti = offy / dil;
     for (int mx = -2; mx <= 2; ++mx) {
       const int qx = x + mx * dil;
       if (qx < 0 || qx >= W) continue;
-      const int offx = x - nab_window_start(qx, W, dil);
+      const int offx = x - cn_na_window_start(qx, W, dil);
       if (offx < 0 || offx > 2 * dil) continue;
       const int t = ti * NAB_K + offx / dil;
       const int qpix = qy * W + qx;
       const float ds = dap[(long)t * HW + qpix];
-      const float pr = ap[(long)t * HW + qpix] * nab_keep(dthresh, dscale, dseed, (long)b * heads + h, t, HW, qpix);
+      const float pr = ap[(long)t * HW + qpix] * cn_na_keep(dthresh, dscale, dseed, (long)b * heads + h, t, HW, qpix);
       float qv[D], gv[D];
       nab_load<D>(qb + (long)qpix * ldq, qv);
       nab_load<D>(gb + (long)qpix * ldo, gv);
@@ -813,7 +728,7 @@ extern "C" int cn_na2d_fwd_bf16(const void* qkv, long ldq, void* out, long ldo, 
   const dim3 grid((unsigned)((n + 255) / 256));
   if (!(attn_drop >= 0.f && attn_drop < 1.f)) return CN_ERR_ARG;
   NAB_DISPATCH(D, cn_bna_fwd_kernel, (const bf16_t*)qkv, ldq, (bf16_t*)out, ldo, attn, B, C, heads, H, W, dilation,
-               scale, nab_thresh(attn_drop), 1.0f / (1.0f - attn_drop), seed, step);
+               scale, cn_dropout_thresh(attn_drop), 1.0f / (1.0f - attn_drop), seed, step);
   return cn_check_launch();
 }
 
@@ -829,7 +744,7 @@ extern "C" int cn_na2d_bwd_bf16(const void* qkv, long ldq, const void* dout, lon
   const long n = (long)B * H * W * heads;
   const dim3 grid((unsigned)((n + 255) / 256));
   if (!(attn_drop >= 0.f && attn_drop < 1.f)) return CN_ERR_ARG;
-  const unsigned long long th = nab_thresh(attn_drop);
+  const unsigned long long th = cn_dropout_thresh(attn_drop);
   const float ds = 1.0f / (1.0f - attn_drop);
   NAB_DISPATCH(D, cn_bna_bwd_q_kernel, (const bf16_t*)qkv, ldq, (const bf16_t*)dout, ldo, attn, dattn, (bf16_t*)dqkv,
                lddq, B, C, heads, H, W, dilation, scale, th, ds, seed, step);

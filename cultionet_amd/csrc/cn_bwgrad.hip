@@ -23,6 +23,7 @@
 //   cycles of LDS for 288 cycles of matrix pipe -- the multiplication phase was LDS-bound (2888 of a tile's 5090 cycles,
 //   tools/bwgrad_stamps.py). Two P fragments x (2 taps x 2 Q fragments) + the centre's = 14 reads per k-step: 224.
 #include "cn_bf16.h"
+#include "cn_conv_geom.h"
 #include "cn_profile.h"
 #include "cn_slicesum.h"
 
@@ -641,8 +642,8 @@ extern "C" long cn_bwgrad_workspace_floats(int B, int Cin, int Hin, int Win, int
   g.B = B;
   if (!transposed) {
     g.CP = Cout; g.CQ = Cin; g.s = stride;
-    g.Hg = (Hin + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
-    g.Wg = (Win + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
+    g.Hg = cn_conv_out(Hin, KH, stride, pad, dil);
+    g.Wg = cn_conv_out(Win, KW, stride, pad, dil);
   } else {
     g.CP = Cin; g.CQ = Cout; g.s = stride; g.Hg = Hin; g.Wg = Win;
   }
@@ -658,8 +659,8 @@ extern "C" int cn_conv2d_bwd_weight_bf16(const void* x, long ldx, const void* dy
   CnBWgGeom g = {};
   g.P = (const bf16_t*)dy; g.ldp = lddy; g.Q = (const bf16_t*)x; g.ldq = ldx;
   g.B = B; g.CP = Cout; g.CQ = Cin; g.s = stride;
-  g.Hg = (Hin + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
-  g.Wg = (Win + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
+  g.Hg = cn_conv_out(Hin, KH, stride, pad, dil);
+  g.Wg = cn_conv_out(Win, KW, stride, pad, dil);
   g.Hq = Hin; g.Wq = Win;
   const int rc = cnw_plan(g, KH, KW, pad, dil);
   if (rc != CN_OK) return rc;
@@ -675,7 +676,7 @@ extern "C" int cn_conv_transpose2d_bwd_weight_bf16(const void* x, long ldx, cons
   g.P = (const bf16_t*)x; g.ldp = ldx; g.Q = (const bf16_t*)dy; g.ldq = lddy;
   g.B = B; g.CP = Cin; g.CQ = Cout; g.s = stride;
   g.Hg = Hin; g.Wg = Win;
-  g.Hq = (Hin - 1) * stride - 2 * pad + KH; g.Wq = (Win - 1) * stride - 2 * pad + KW;
+  g.Hq = cn_convt_out(Hin, KH, stride, pad, 0); g.Wq = cn_convt_out(Win, KW, stride, pad, 0);
   const int rc = cnw_plan(g, KH, KW, pad, 1);
   if (rc != CN_OK) return rc;
   return cnw_run(g, dw, ws, ws_floats, (hipStream_t)stream);

@@ -1261,8 +1261,6 @@ int cn_conv_igemm_launch(CnConvGeom& g, hipStream_t stream) {
   return run(c, g);
 }
 
-static inline int floordiv(int a, int b) { return (a >= 0) ? a / b : -((-a + b - 1) / b); }
-
 // Fills the group tables; shared_y when every group names the same output (their results are summed).
 static int cn_set_groups(CnConvGeom& g, int G, const float* const* xs, const float* const* wps,
                          const float* const* biases, float* const* ys) {
@@ -1307,12 +1305,7 @@ static int cn_gather_conv_g(int G, const float* const* xs, long xbs, const float
     CnConvClass& k = g.cls[i];
     k.grp = i;
     k.Hg = Hout; k.Wg = Wout; k.oy0 = 0; k.ox0 = 0;
-    k.ntaps = KH * KW;
-    for (int ky = 0; ky < KH; ++ky)
-      for (int kx = 0; kx < KW; ++kx) {
-        const int t = ky * KW + kx;
-        k.dy[t] = ky * dils[i] - pads[i]; k.dx[t] = kx * dils[i] - pads[i]; k.wt[t] = t;
-      }
+    k.ntaps = cn_gather_taps(KH, KW, pads[i], dils[i], k.dy, k.dx, k.wt);
   }
   g.accumulate = accumulate;
   return cn_conv_igemm_launch(g, stream);
@@ -1332,8 +1325,8 @@ extern "C" int cn_conv2d_fwd_f32(const float* x, long xbs, const float* wp, cons
                                  int stride, int pad, int dil, int accumulate, void* stream) {
   cn_bind_ws(stream);
   if (stride < 1) return CN_ERR_ARG;  // before it is divided by
-  const int Hout = (Hin + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
-  const int Wout = (Win + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
+  const int Hout = cn_conv_out(Hin, KH, stride, pad, dil);
+  const int Wout = cn_conv_out(Win, KW, stride, pad, dil);
   return cn_gather_conv(x, xbs, wp, bias, y, ybs, B, Cin, Hin, Win, Cout, Hout, Wout, KH, KW, stride, pad, dil,
                         accumulate, (hipStream_t)stream);
 }
@@ -1368,34 +1361,17 @@ static int cn_scatter_conv_g(int G, const float* const* srcs, long sbs, const fl
       for (int px = 0; px < stride; ++px) {
         CnConvClass& k = g.cls[nc];
         k.grp = gi;
-        k.Hg = (Ho - py + stride - 1) / stride;
-        k.Wg = (Wo - px + stride - 1) / stride;
+        k.Hg = cn_parity_extent(Ho, py, stride);
+        k.Wg = cn_parity_extent(Wo, px, stride);
         if (k.Hg <= 0 || k.Wg <= 0) continue;
         k.oy0 = py; k.ox0 = px;
-        int nt = 0;
-        for (int ky = 0; ky < KH; ++ky) {
-          const int ny = py + pad - ky * dil;
-          if (((ny % stride) + stride) % stride != 0) continue;
-          for (int kx = 0; kx < KW; ++kx) {
-            const int nx = px + pad - kx * dil;
-            if (((nx % stride) + stride) % stride != 0) continue;
-            k.dy[nt] = floordiv(ny, stride); k.dx[nt] = floordiv(nx, stride); k.wt[nt] = ky * KW + kx;
-            ++nt;
-          }
-        }
-        k.ntaps = nt;
+        k.ntaps = cn_parity_taps(py, px, KH, KW, stride, pad, dil, k.dy, k.dx, k.wt);
         ++nc;
       }
   }
   g.ncls = nc;
   if (nc == 0) return CN_OK;
-  // heavy classes first (stable: insertion sort over <= 16 classes), interleaved by cn_plan when their tile counts agree
-  for (int i = 1; i < nc; ++i) {
-    const CnConvClass key = g.cls[i];
-    int j = i - 1;
-    while (j >= 0 && g.cls[j].ntaps < key.ntaps) { g.cls[j + 1] = g.cls[j]; --j; }
-    g.cls[j + 1] = key;
-  }
+  cn_sort_heavy_first(g.cls, nc);  // interleaved by cn_plan when the classes' tile counts agree
   g.want_interleave = stride > 1 ? 1 : 0;  // (8 x 50^2 -> 100^2, 128 -> 128: 114.1 -> 105.7 us alone; the step does not move)
   return cn_conv_igemm_launch(g, stream);
 }
@@ -1413,8 +1389,8 @@ extern "C" int cn_conv2d_bwd_data_f32(const float* dy, long dybs, const float* w
                                       int pad, int dil, int accumulate, void* stream) {
   cn_bind_ws(stream);
   if (stride < 1) return CN_ERR_ARG;  // before it is divided by
-  const int Hout = (Hin + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
-  const int Wout = (Win + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
+  const int Hout = cn_conv_out(Hin, KH, stride, pad, dil);
+  const int Wout = cn_conv_out(Win, KW, stride, pad, dil);
   return cn_scatter_conv(dy, dybs, wp_t, nullptr, dx, dxbs, B, Cout, Hout, Wout, Cin, Hin, Win, KH, KW, stride,
                          pad, dil, accumulate, (hipStream_t)stream);
 }
@@ -1430,11 +1406,11 @@ extern "C" int cn_conv2d_fwd_grouped_f32(int G, const float* const* xs, long xbs
   cn_bind_ws(stream);
   if (G < 1 || G > CN_MAX_GROUPS) return CN_ERR_ARG;
   if (stride < 1) return CN_ERR_ARG;  // before it is divided by
-  const int Hout = (Hin + 2 * pads[0] - dils[0] * (KH - 1) - 1) / stride + 1;
-  const int Wout = (Win + 2 * pads[0] - dils[0] * (KW - 1) - 1) / stride + 1;
+  const int Hout = cn_conv_out(Hin, KH, stride, pads[0], dils[0]);
+  const int Wout = cn_conv_out(Win, KW, stride, pads[0], dils[0]);
   for (int i = 1; i < G; ++i)
-    if ((Hin + 2 * pads[i] - dils[i] * (KH - 1) - 1) / stride + 1 != Hout ||
-        (Win + 2 * pads[i] - dils[i] * (KW - 1) - 1) / stride + 1 != Wout)
+    if (cn_conv_out(Hin, KH, stride, pads[i], dils[i]) != Hout ||
+        cn_conv_out(Win, KW, stride, pads[i], dils[i]) != Wout)
       return CN_ERR_ARG;
   return cn_gather_conv_g(G, xs, xbs, wps, biases, ys, ybs, B, Cin, Hin, Win, Cout, Hout, Wout, KH, KW, stride,
                           pads, dils, accumulate, (hipStream_t)stream);
@@ -1450,11 +1426,11 @@ extern "C" int cn_conv2d_bwd_data_grouped_f32(int G, const float* const* dys, lo
   cn_bind_ws(stream);
   if (G < 1 || G > CN_MAX_GROUPS) return CN_ERR_ARG;
   if (stride < 1) return CN_ERR_ARG;  // before it is divided by
-  const int Hout = (Hin + 2 * pads[0] - dils[0] * (khs[0] - 1) - 1) / stride + 1;
-  const int Wout = (Win + 2 * pads[0] - dils[0] * (kws[0] - 1) - 1) / stride + 1;
+  const int Hout = cn_conv_out(Hin, khs[0], stride, pads[0], dils[0]);
+  const int Wout = cn_conv_out(Win, kws[0], stride, pads[0], dils[0]);
   for (int i = 1; i < G; ++i)
-    if ((Hin + 2 * pads[i] - dils[i] * (khs[i] - 1) - 1) / stride + 1 != Hout ||
-        (Win + 2 * pads[i] - dils[i] * (kws[i] - 1) - 1) / stride + 1 != Wout)
+    if (cn_conv_out(Hin, khs[i], stride, pads[i], dils[i]) != Hout ||
+        cn_conv_out(Win, kws[i], stride, pads[i], dils[i]) != Wout)
       return CN_ERR_ARG;
   return cn_scatter_conv_g(G, dys, dybs, wps_t, nullptr, dxs, dxbs, B, Cout, Hout, Wout, Cin, Hin, Win, khs, kws,
                            stride, pads, dils, accumulate, (hipStream_t)stream);
@@ -1472,8 +1448,8 @@ extern "C" int cn_conv_transpose2d_fwd_f32(const float* x, long xbs, const float
                                            void* stream) {
   cn_bind_ws(stream);
   if (out_pad < 0 || (out_pad > 0 && out_pad >= stride)) return CN_ERR_ARG;
-  const int Hout = (Hin - 1) * stride - 2 * pad + KH + out_pad;
-  const int Wout = (Win - 1) * stride - 2 * pad + KW + out_pad;
+  const int Hout = cn_convt_out(Hin, KH, stride, pad, out_pad);
+  const int Wout = cn_convt_out(Win, KW, stride, pad, out_pad);
   return cn_scatter_conv(x, xbs, wp, bias, y, ybs, B, Cin, Hin, Win, Cout, Hout, Wout, KH, KW, stride, pad, 1,
                          accumulate, (hipStream_t)stream);
 }
@@ -1485,8 +1461,8 @@ extern "C" int cn_conv_transpose2d_bwd_data_f32(const float* dy, long dybs, cons
                                                 void* stream) {
   cn_bind_ws(stream);
   if (out_pad < 0 || (out_pad > 0 && out_pad >= stride)) return CN_ERR_ARG;
-  const int Hout = (Hin - 1) * stride - 2 * pad + KH + out_pad;
-  const int Wout = (Win - 1) * stride - 2 * pad + KW + out_pad;
+  const int Hout = cn_convt_out(Hin, KH, stride, pad, out_pad);
+  const int Wout = cn_convt_out(Win, KW, stride, pad, out_pad);
   return cn_gather_conv(dy, dybs, wp_t, nullptr, dx, dxbs, B, Cout, Hout, Wout, Cin, Hin, Win, KH, KW, stride, pad,
                         1, accumulate, (hipStream_t)stream);
 }

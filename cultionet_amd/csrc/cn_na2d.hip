@@ -6,40 +6,10 @@
 // The surrounding qkv / proj Linear layers run as 1x1 convolutions on the MFMA kernel
 // (cn_conv.hip), so q,k,v arrive as channel blocks of one [B, 3C, H, W] tensor:
 // channel of (which, head, d) = which*C + head*D + d  (== natten's reshape(B,H,W,3,heads,D)).
-#include "cn_common.h"
+#include "cn_index.h"
 
-#define NA_K 3
-#define NA_KK 9
-
-// natten get_window_start (K = 3, n = 1)
-__device__ __forceinline__ int na_window_start(int i, int len, int dil) {
-  if (dil <= 1) return max(i - 1, 0) + ((i + 1 >= len) ? (len - i - 2) : 0);
-  const int ni = i - dil;
-  if (ni < 0) return i % dil;
-  if (i + dil >= len) {
-    const int imodd = i % dil;
-    const int a = (len / dil) * dil;
-    const int b = len - a;
-    if (imodd < b) return len - b + imodd - 2 * dil;
-    return a + imodd - NA_K * dil;
-  }
-  return ni;
-}
-
-// attn_drop (nn.Dropout on the soft-maxed logits): keep/(1-p) factor of tap t, recomputed from a counter hash
-// (same splitmix64 stream as cn_dropout_f32) in forward and backward; 1.0 when drop is off.
-__device__ __forceinline__ unsigned long long na_splitmix64(unsigned long long z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__device__ __forceinline__ float na_keep(unsigned long long thresh, float scale, unsigned long long seed, long bh,
-                                         int t, int HW, int p) {
-  if (thresh == 0ull) return 1.0f;
-  const unsigned long long i = ((unsigned long long)bh * NA_KK + t) * (unsigned long long)HW + p;
-  return na_splitmix64(seed + i) >= thresh ? scale : 0.f;
-}
+#define NA_K CN_NA_K
+#define NA_KK CN_NA_KK
 
 // qkv [B][3C][H][W] (batch stride qbs); out [B][C][H][W]; attn [B][heads][9][H][W] (saved probs).
 template <int D>
@@ -56,7 +26,7 @@ __global__ __launch_bounds__(256) void cn_na2d_fwd_kernel(const float* __restric
   const int p = bx * 256 + threadIdx.x;
   if (p >= HW) return;
   const int y = p / W, x = p - y * W;
-  const int sy = na_window_start(y, H, dil), sx = na_window_start(x, W, dil);
+  const int sy = cn_na_window_start(y, H, dil), sx = cn_na_window_start(x, W, dil);
   const float* qp = qkv + b * qbs + (long)(h * DD) * HW;
   const float* kp = qp + (long)C * HW;
   const float* vp = kp + (long)C * HW;
@@ -93,7 +63,7 @@ __global__ __launch_bounds__(256) void cn_na2d_fwd_kernel(const float* __restric
   for (int t = 0; t < NA_KK; ++t) {
     lg[t] *= inv;
     if (attn) ap[(long)t * HW] = lg[t];
-    lg[t] *= na_keep(dthresh, dscale, dseed, (long)b * heads + h, t, HW, p);
+    lg[t] *= cn_na_keep(dthresh, dscale, dseed, (long)b * heads + h, t, HW, p);
   }
   float* op = out + b * obs + (long)(h * DD) * HW + p;
 #pragma unroll 4
@@ -123,7 +93,7 @@ __global__ __launch_bounds__(256) void cn_na2d_bwd_q_kernel(const float* __restr
   const int p = bx * 256 + threadIdx.x;
   if (p >= HW) return;
   const int y = p / W, x = p - y * W;
-  const int sy = na_window_start(y, H, dil), sx = na_window_start(x, W, dil);
+  const int sy = cn_na_window_start(y, H, dil), sx = cn_na_window_start(x, W, dil);
   const float* kp = qkv + b * qbs + (long)(C + h * DD) * HW;
   const float* vp = kp + (long)C * HW;
   const float* dop = dout + b * dobs + (long)(h * DD) * HW + p;
@@ -148,7 +118,7 @@ __global__ __launch_bounds__(256) void cn_na2d_bwd_q_kernel(const float* __restr
 #pragma unroll
   for (int t = 0; t < NA_KK; ++t) {
     pr[t] = ap[(long)t * HW];
-    dp[t] *= na_keep(dthresh, dscale, dseed, (long)b * heads + h, t, HW, p);
+    dp[t] *= cn_na_keep(dthresh, dscale, dseed, (long)b * heads + h, t, HW, p);
     dot += pr[t] * dp[t];
   }
   float* dap = dattn + ((long)(b * heads + h) * NA_KK) * HW + p;
@@ -206,18 +176,18 @@ __global__ __launch_bounds__(256) void cn_na2d_bwd_kv_kernel(const float* __rest
     for (int my = -2; my <= 2; ++my) {
       const int qy = y + my * dil;
       if (qy < 0 || qy >= H) continue;
-      const int offy = y - na_window_start(qy, H, dil);
+      const int offy = y - cn_na_window_start(qy, H, dil);
       if (offy < 0 || offy > 2 * dil) continue;  // same residue class => divisible by dil
       const int i = offy / dil;
       for (int mx = -2; mx <= 2; ++mx) {
         const int qx = x + mx * dil;
         if (qx < 0 || qx >= W) continue;
-        const int offx = x - na_window_start(qx, W, dil);
+        const int offx = x - cn_na_window_start(qx, W, dil);
         if (offx < 0 || offx > 2 * dil) continue;
         const int t = i * NA_K + offx / dil;
         const int qpix = qy * W + qx;
         const float ds = dap[(long)t * HW + qpix];
-        const float pr = ap[(long)t * HW + qpix] * na_keep(dthresh, dscale, dseed, (long)b * heads + h, t, HW, qpix);
+        const float pr = ap[(long)t * HW + qpix] * cn_na_keep(dthresh, dscale, dseed, (long)b * heads + h, t, HW, qpix);
 #pragma unroll
         for (int d = 0; d < CH; ++d) {
           if (D > 0 || d0 + d < DD) {
@@ -251,12 +221,6 @@ __global__ __launch_bounds__(256) void cn_na2d_bwd_kv_kernel(const float* __rest
   }
 
 // kernel_size must be 3 (every NATTEN_PARAMS entry used by TowerUNet: unet_parts.py:19-40).
-static unsigned long long na_thresh(float p) {
-  if (!(p > 0.f)) return 0ull;
-  const double t = (double)p * 18446744073709551616.0;
-  return t >= 18446744073709551615.0 ? ~0ull : (unsigned long long)t;
-}
-
 extern "C" int cn_na2d_fwd_f32(const float* qkv, long qbs, float* out, long obs, float* attn, int B, int C,
                                int heads, int H, int W, int kernel_size, int dilation, float attn_drop,
                                unsigned long long seed, const unsigned long long* step, void* stream_) {
@@ -268,7 +232,7 @@ extern "C" int cn_na2d_fwd_f32(const float* qkv, long qbs, float* out, long obs,
   dim3 grid(cn_xcd_grid((long)((H * W + 255) / 256) * heads * B));  // XCD-aware order, decoded in the kernels
   if (!(attn_drop >= 0.f && attn_drop < 1.f)) return CN_ERR_ARG;
   NA_DISPATCH(D, cn_na2d_fwd_kernel, qkv, qbs, out, obs, attn, B, C, heads, H, W, dilation, scale,
-              na_thresh(attn_drop), 1.0f / (1.0f - attn_drop), seed, step);
+              cn_dropout_thresh(attn_drop), 1.0f / (1.0f - attn_drop), seed, step);
   return cn_check_launch();
 }
 
@@ -283,7 +247,7 @@ extern "C" int cn_na2d_bwd_f32(const float* qkv, long qbs, const float* dout, lo
   const float scale = 1.0f / sqrtf((float)D);
   dim3 grid(cn_xcd_grid((long)((H * W + 255) / 256) * heads * B));  // XCD-aware order, decoded in the kernels
   if (!(attn_drop >= 0.f && attn_drop < 1.f)) return CN_ERR_ARG;
-  const unsigned long long th = na_thresh(attn_drop);
+  const unsigned long long th = cn_dropout_thresh(attn_drop);
   const float ds = 1.0f / (1.0f - attn_drop);
   NA_DISPATCH(D, cn_na2d_bwd_q_kernel, qkv, qbs, dout, dobs, attn, dattn, dqkv, dqbs, B, C, heads, H, W, dilation,
               scale, th, ds, seed, step);

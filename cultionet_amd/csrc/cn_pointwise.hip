@@ -5,20 +5,12 @@
 // (/root/reference/src/cultionet/nn/functional.py:72-81), torch.cat in TowerUNetBlock /
 // TowerUNetFinal (nn/modules/unet_parts.py:281-309,700-760), TowerUNetFinalCombine + SigmoidCrisp
 // (unet_parts.py:43-193).
-#include "cn_common.h"
+#include "cn_index.h"
 
 // ---------------------------------------------------------------------------
 // Bilinear resize, align_corners=True. Planes = B*C, both tensors [B][C][H][W] with batch strides.
-// src index math follows ATen's area_pixel_compute_source_index (fp32).
+// Source indices and weights: cn_bl_src (cn_index.h).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void bl_src(int o, float scale, int in_size, int& i0, int& i1, float& l1) {
-#pragma clang fp contract(off)  // ATen rounds scale*o before subtracting floor(): an fma here shifts lambda by ~1e-6
-  const float src = scale * (float)o;
-  i0 = (int)src;
-  if (i0 > in_size - 1) i0 = in_size - 1;
-  i1 = i0 + ((i0 < in_size - 1) ? 1 : 0);
-  l1 = src - i0;
-}
 
 // The source may live on a larger stored grid Hp x Wp (row pitch Wp, plane Hp*Wp) of which [0,Hi) x [0,Wi) is the image:
 // the output_padding grid the engine's ConvTranspose2d writes (cn_conv_transpose2d_fwd_f32).
@@ -31,8 +23,8 @@ __global__ __launch_bounds__(256) void cn_bilinear_fwd_kernel(const float* __res
   const int oy = p / Wo, ox = p - oy * Wo;
   int y0, y1, x0, x1;
   float ly, lx;
-  bl_src(oy, sh, Hi, y0, y1, ly);
-  bl_src(ox, sw, Wi, x0, x1, lx);
+  cn_bl_src(oy, sh, Hi, y0, y1, ly);
+  cn_bl_src(ox, sw, Wi, x0, x1, lx);
   const float* xp = x + b * xbs + (long)c * Hp * Wp;
   const float hy = 1.f - ly, hx = 1.f - lx;
   const float v = hy * (hx * xp[y0 * Wp + x0] + lx * xp[y0 * Wp + x1]) +
@@ -71,7 +63,7 @@ __global__ __launch_bounds__(256) void cn_bilinear_bwd_kernel(const float* __res
       float wx = 0.f;
       if (ox <= ox_hi) {
         int x0, x1; float lx;
-        bl_src(ox, sw, Wi, x0, x1, lx);
+        cn_bl_src(ox, sw, Wi, x0, x1, lx);
         if (x0 == ix) wx += 1.f - lx;
         if (x1 == ix) wx += lx;
       }
@@ -79,7 +71,7 @@ __global__ __launch_bounds__(256) void cn_bilinear_bwd_kernel(const float* __res
     }
     for (int oy = oy_lo; oy <= oy_hi; ++oy) {
       int y0, y1; float ly;
-      bl_src(oy, sh, Hi, y0, y1, ly);
+      cn_bl_src(oy, sh, Hi, y0, y1, ly);
       float wy = 0.f;
       if (y0 == iy) wy += 1.f - ly;
       if (y1 == iy) wy += ly;
@@ -95,14 +87,14 @@ __global__ __launch_bounds__(256) void cn_bilinear_bwd_kernel(const float* __res
   }
   for (int oy = oy_lo; oy <= oy_hi; ++oy) {
     int y0, y1; float ly;
-    bl_src(oy, sh, Hi, y0, y1, ly);
+    cn_bl_src(oy, sh, Hi, y0, y1, ly);
     float wy = 0.f;
     if (y0 == iy) wy += 1.f - ly;
     if (y1 == iy) wy += ly;
     if (wy == 0.f) continue;
     for (int ox = ox_lo; ox <= ox_hi; ++ox) {
       int x0, x1; float lx;
-      bl_src(ox, sw, Wi, x0, x1, lx);
+      cn_bl_src(ox, sw, Wi, x0, x1, lx);
       float wx = 0.f;
       if (x0 == ix) wx += 1.f - lx;
       if (x1 == ix) wx += lx;
@@ -118,43 +110,6 @@ __global__ __launch_bounds__(256) void cn_bilinear_bwd_kernel(const float* __res
 // only on the pixel, so a lane computes them ONCE and reuses them for BL_CH channels (the per-channel work is the
 // <= 16 weighted loads). Pixels with more candidates than that (never, for scale > 0.5) take the general path.
 #define BL_CH 16
-__device__ __forceinline__ int bl_candidates(int i, int in_size, int out_size, float scale, float inv_scale, int* idx,
-                                             float* wgt) {
-  int lo = (int)floorf((i - 1) * inv_scale) - 1, hi = (int)ceilf((i + 1) * inv_scale) + 1;
-  if (scale == 0.f) { lo = 0; hi = out_size - 1; }
-  lo = max(lo, 0);
-  hi = min(hi, out_size - 1);
-  // The outputs reading input index i are CONSECUTIVE (the source coordinate is monotonic; a zero weight can only be
-  // the first output of the run, whose source falls exactly on i - 1): the search only counts them and notes the first,
-  // the <= 4 weights are then recomputed with static register indices. (Storing idx[n] / wgt[n] from inside the search
-  // loop through an if-chain on n lost candidate 1 whenever a fourth one was found -- resizes growing by 1.5x..2x.)
-  int n = 0, first = 0;
-#pragma unroll 1
-  for (int o = lo; o <= hi; ++o) {
-    int i0, i1; float l1;
-    bl_src(o, scale, in_size, i0, i1, l1);
-    float w = 0.f;
-    if (i0 == i) w += 1.f - l1;
-    if (i1 == i) w += l1;
-    if (w != 0.f) {
-      if (n == 0) first = o;
-      ++n;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const bool live = k < n;
-    const int o = live ? first + k : first;
-    int i0, i1; float l1;
-    bl_src(o, scale, in_size, i0, i1, l1);
-    float w = 0.f;
-    if (i0 == i) w += 1.f - l1;
-    if (i1 == i) w += l1;
-    idx[k] = o;
-    wgt[k] = live ? w : 0.f;
-  }
-  return n;
-}
 
 __global__ __launch_bounds__(256) void cn_bilinear_bwd_near_kernel(const float* __restrict__ dy, long dybs,
                                                                   float* __restrict__ dx, long dxbs, int C, int Hi,
@@ -168,8 +123,8 @@ __global__ __launch_bounds__(256) void cn_bilinear_bwd_near_kernel(const float* 
   const bool padding = iy >= Hi || ix >= Wi;  // outside the image on the stored grid: written as zeros below (ny = 0)
   int oyv[4] = {0, 0, 0, 0}, oxv[4] = {0, 0, 0, 0};
   float wyv[4] = {0.f, 0.f, 0.f, 0.f}, wxv[4] = {0.f, 0.f, 0.f, 0.f};
-  const int ny = padding ? 0 : bl_candidates(iy, Hi, Ho, sh, inv_sh, oyv, wyv);
-  const int nx = padding ? 0 : bl_candidates(ix, Wi, Wo, sw, inv_sw, oxv, wxv);
+  const int ny = padding ? 0 : cn_bl_candidates(iy, Hi, Ho, sh, inv_sh, oyv, wyv);
+  const int nx = padding ? 0 : cn_bl_candidates(ix, Wi, Wo, sw, inv_sw, oxv, wxv);
   int c_end = c_begin + BL_CH;
   if (c_end > C) c_end = C;
   if (ny <= 4 && nx <= 4) {
@@ -231,14 +186,14 @@ __global__ __launch_bounds__(256) void cn_bilinear_bwd_near_kernel(const float* 
     float acc = 0.f;
     for (int oy = oy_lo; oy <= oy_hi; ++oy) {
       int y0, y1; float ly;
-      bl_src(oy, sh, Hi, y0, y1, ly);
+      cn_bl_src(oy, sh, Hi, y0, y1, ly);
       float wy = 0.f;
       if (y0 == iy) wy += 1.f - ly;
       if (y1 == iy) wy += ly;
       if (wy == 0.f) continue;
       for (int ox = ox_lo; ox <= ox_hi; ++ox) {
         int x0, x1; float lx;
-        bl_src(ox, sw, Wi, x0, x1, lx);
+        cn_bl_src(ox, sw, Wi, x0, x1, lx);
         float wx = 0.f;
         if (x0 == ix) wx += 1.f - lx;
         if (x1 == ix) wx += lx;
@@ -250,10 +205,6 @@ __global__ __launch_bounds__(256) void cn_bilinear_bwd_near_kernel(const float* 
   }
 }
 
-static inline float bl_scale(int in_size, int out_size) {
-  return out_size > 1 ? (float)(in_size - 1) / (float)(out_size - 1) : 0.f;
-}
-
 // Hp x Wp: stored grid of the SOURCE (>= Hi x Wi; the image is its top-left Hi x Wi; 0 = dense, Hp = Hi, Wp = Wi).
 extern "C" int cn_bilinear_fwd_f32(const float* x, long xbs, float* y, long ybs, int B, int C, int Hi, int Wi, int Ho,
                                    int Wo, int Hp, int Wp, void* stream) {
@@ -263,7 +214,7 @@ extern "C" int cn_bilinear_fwd_f32(const float* x, long xbs, float* y, long ybs,
   if (Hp < Hi || Wp < Wi) return CN_ERR_ARG;
   dim3 grid((Ho * Wo + 255) / 256, C, B);
   CN_LAUNCH(cn_bilinear_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, xbs, y, ybs, C, Hi, Wi, Ho,
-                     Wo, bl_scale(Hi, Ho), bl_scale(Wi, Wo), Hp, Wp);
+                     Wo, cn_bl_scale(Hi, Ho), cn_bl_scale(Wi, Wo), Hp, Wp);
   return cn_check_launch();
 }
 
@@ -274,7 +225,7 @@ extern "C" int cn_bilinear_bwd_f32(const float* dy, long dybs, float* dx, long d
   if (Hp <= 0) Hp = Hi;
   if (Wp <= 0) Wp = Wi;
   if (Hp < Hi || Wp < Wi) return CN_ERR_ARG;
-  const float sh = bl_scale(Hi, Ho), sw = bl_scale(Wi, Wo);
+  const float sh = cn_bl_scale(Hi, Ho), sw = cn_bl_scale(Wi, Wo);
   if (2 * Hi > Ho && 2 * Wi > Wo && (long)B * C * Hi * Wi >= 1 << 16) {  // near-1:1 resize of a large tensor
     dim3 gridn((Hp * Wp + 255) / 256, (C + BL_CH - 1) / BL_CH, B);
     CN_LAUNCH(cn_bilinear_bwd_near_kernel, gridn, dim3(256), 0, (hipStream_t)stream, dy, dybs, dx, dxbs, C,
@@ -327,8 +278,8 @@ __global__ __launch_bounds__(256) void cn_convt_taps_fwd_kernel(const float* __r
   if (Ho == Hy && Wo == Wy) {  // no resize behind the transposed convolution
     y0 = y1 = oy; x0 = x1 = ox; ly = lx = 0.f;
   } else {
-    bl_src(oy, sh, Hy, y0, y1, ly);
-    bl_src(ox, sw, Wy, x0, x1, lx);
+    cn_bl_src(oy, sh, Hy, y0, y1, ly);
+    cn_bl_src(ox, sw, Wy, x0, x1, lx);
   }
   const float hy = 1.f - ly, hx = 1.f - lx;
   const int o00 = ct_src(y0, x0, K, s, pad, Hc, Wc), o01 = ct_src(y0, x1, K, s, pad, Hc, Wc);
@@ -369,8 +320,8 @@ __global__ __launch_bounds__(256) void cn_convt_taps_bwd_kernel(const float* __r
     if (Ho == Hy && Wo == Wy) {
       ny = nx = 1; oyv[0] = p; oxv[0] = q; wyv[0] = wxv[0] = 1.f;
     } else {
-      ny = bl_candidates(p, Hy, Ho, sh, inv_sh, oyv, wyv);
-      nx = bl_candidates(q, Wy, Wo, sw, inv_sw, oxv, wxv);
+      ny = cn_bl_candidates(p, Hy, Ho, sh, inv_sh, oyv, wyv);
+      nx = cn_bl_candidates(q, Wy, Wo, sw, inv_sw, oxv, wxv);
     }
   }
   if (ny > 4) ny = 4;  // (a resize that shrinks by 2x or more would need the general adjoint: refused by the launcher)
@@ -394,7 +345,7 @@ extern "C" int cn_convt_taps_fwd_f32(const float* P, long pbs, const float* bias
   if (Hy < 1 || Wy < 1 || Ho < 1 || Wo < 1) return CN_ERR_ARG;
   dim3 grid((Ho * Wo + 255) / 256, (C + CT_CH - 1) / CT_CH, B);
   CN_LAUNCH(cn_convt_taps_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, P, pbs, bias, z, zbs, C, Hc, Wc, K, stride,
-            pad, Hy, Wy, Ho, Wo, bl_scale(Hy, Ho), bl_scale(Wy, Wo));
+            pad, Hy, Wy, Ho, Wo, cn_bl_scale(Hy, Ho), cn_bl_scale(Wy, Wo));
   return cn_check_launch();
 }
 
@@ -405,7 +356,7 @@ extern "C" int cn_convt_taps_bwd_f32(const float* dz, long dzbs, float* dP, long
   const int Hy = (Hc - 1) * stride - 2 * pad + K, Wy = (Wc - 1) * stride - 2 * pad + K;
   if (Hy < 1 || Wy < 1 || Ho < 1 || Wo < 1) return CN_ERR_ARG;
   if (2 * Hy <= Ho || 2 * Wy <= Wo) return CN_ERR_ARG;  // <= 4 outputs read an input pixel only for resizes below 2x
-  const float sh = bl_scale(Hy, Ho), sw = bl_scale(Wy, Wo);
+  const float sh = cn_bl_scale(Hy, Ho), sw = cn_bl_scale(Wy, Wo);
   dim3 grid((K * K * Hc * Wc + 255) / 256, (C + CT_CH - 1) / CT_CH, B);
   CN_LAUNCH(cn_convt_taps_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, dz, dzbs, dP, dpbs, C, Hc, Wc, K, stride,
             pad, Hy, Wy, Ho, Wo, sh, sw, sh > 0.f ? 1.f / sh : 0.f, sw > 0.f ? 1.f / sw : 0.f);
@@ -589,7 +540,7 @@ extern "C" int cn_final_combine_bwd_f32(const float* ha, const float* hb, const 
 
 // ---------------------------------------------------------------------------
 // Dropout (nn.Dropout2d after each encoder block: convolution.py:495,511; natten attn_drop / proj_drop).
-// Counter-based mask: keep(i) = splitmix64(seed + i) >= p * 2^64, never stored -- backward recomputes it.
+// Counter-based mask: keep(i) = cn_splitmix64(seed + i) >= cn_dropout_thresh(p), never stored -- backward recomputes it.
 //   channelwise != 0: one decision per (b, c) plane (Dropout2d); else one per element (Dropout).
 // y = x * keep / (1 - p). Same entry point serves backward (x := dy, accumulate into dx).
 // ---------------------------------------------------------------------------
@@ -616,12 +567,10 @@ extern "C" int cn_dropout_f32(const float* x, long xbs, float* y, long ybs, int 
                               void* stream) {
   if (B <= 0 || C <= 0 || L <= 0) return CN_OK;
   if (!(p >= 0.f && p < 1.f)) return CN_ERR_ARG;
-  const double t = (double)p * 18446744073709551616.0;  // p * 2^64
-  const unsigned long long thresh = t >= 18446744073709551615.0 ? ~0ull : (unsigned long long)t;
   int bx = (L + 1023) / 1024;
   if (bx < 1) bx = 1;
   CN_LAUNCH(cn_dropout_kernel, dim3(bx, C, B), dim3(256), 0, (hipStream_t)stream, x, xbs, y, ybs, C, L,
-                     thresh, 1.0f / (1.0f - p), seed, step, channelwise, accumulate);
+                     cn_dropout_thresh(p), 1.0f / (1.0f - p), seed, step, channelwise, accumulate);
   return cn_check_launch();
 }
 
@@ -637,12 +586,9 @@ extern "C" int cn_rng_advance_u64(unsigned long long* word, unsigned long long v
 
 // ---------------------------------------------------------------------------
 // F.adaptive_max_pool2d (pool_by_max=True: convolution.py:499-503). Window of output o along one axis:
-// [floor(o*In/Out), ceil((o+1)*In/Out)). idx: int32 flat argmax inside the input plane (first max, as ATen).
+// [cn_amp_start, cn_amp_end). idx: int32 flat argmax inside the input plane (first max, as ATen).
 // Backward in gather form (windows may overlap when In % Out != 0): deterministic, no atomics.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ int amp_start(int o, int in, int out) { return (int)(((long)o * in) / out); }
-__device__ __forceinline__ int amp_end(int o, int in, int out) { return (int)((((long)(o + 1)) * in + out - 1) / out); }
-
 __global__ __launch_bounds__(256) void cn_adaptive_maxpool_fwd_kernel(const float* __restrict__ x, long xbs,
                                                                      float* __restrict__ y, long ybs,
                                                                      int* __restrict__ idx, int C, int Hi, int Wi,
@@ -651,15 +597,15 @@ __global__ __launch_bounds__(256) void cn_adaptive_maxpool_fwd_kernel(const floa
   if (p >= Ho * Wo) return;
   const int c = blockIdx.y, b = blockIdx.z;
   const int oy = p / Wo, ox = p - oy * Wo;
-  const int y0 = amp_start(oy, Hi, Ho), y1 = amp_end(oy, Hi, Ho);
-  const int x0 = amp_start(ox, Wi, Wo), x1 = amp_end(ox, Wi, Wo);
+  const int y0 = cn_amp_start(oy, Hi, Ho), y1 = cn_amp_end(oy, Hi, Ho);
+  const int x0 = cn_amp_start(ox, Wi, Wo), x1 = cn_amp_end(ox, Wi, Wo);
   const float* xp = x + b * xbs + (long)c * Hi * Wi;
   float best = -INFINITY;
   int bi = y0 * Wi + x0;
   for (int iy = y0; iy < y1; ++iy)
     for (int ix = x0; ix < x1; ++ix) {
       const float v = xp[iy * Wi + ix];
-      if (v > best || v != v) { best = v; bi = iy * Wi + ix; }
+      if (cn_max_takes(best, v)) { best = v; bi = iy * Wi + ix; }
     }
   y[b * ybs + (long)c * Ho * Wo + p] = best;
   if (idx) idx[((long)b * C + c) * Ho * Wo + p] = bi;

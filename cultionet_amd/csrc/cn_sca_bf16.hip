@@ -12,6 +12,7 @@
 //     scan order; a NaN wins (ATen: val > max || isnan(val), so the last NaN);
 //   channel max (einops.reduce 'max' = torch.amax): the gradient is split evenly across the tied channels.
 #include "cn_bf16.h"
+#include "cn_index.h"
 
 // ---------------------------------------------------------------------------
 // block tiling of the SCA passes: 256 threads = R pixel rows x G channel groups (G = C/8, R = 256/G, threads past R*G
@@ -37,9 +38,6 @@ __device__ __forceinline__ bool sb_better(float av, int ai, float bv, int bi) {
   if (av != bv) return av > bv;
   return ai < bi;
 }
-
-// torch.amax over channels propagates a NaN
-__device__ __forceinline__ float sb_max_nan(float m, float v) { return (v > m || v != v) ? v : m; }
 
 // ---- pool forward ---------------------------------------------------------------------------------------------------
 // pooled[b][0][l] = mean_c x, pooled[b][1][l] = max_c x (fp32 NCHW, the 3x3 conv's input);
@@ -72,7 +70,7 @@ __global__ __launch_bounds__(256) void cn_sca_pool_fwd_bf16_kernel(const bf16_t*
         cs[j] += v[j];
         if (ci[j] < 0 || v[j] > cm[j] || v[j] != v[j]) { cm[j] = v[j]; ci[j] = l; }
         ps += v[j];
-        pm = sb_max_nan(pm, v[j]);
+        pm = cn_max_nan(pm, v[j]);
       }
     }
     s_ps[it * 256 + t] = ps;
@@ -95,7 +93,7 @@ __global__ __launch_bounds__(256) void cn_sca_pool_fwd_bf16_kernel(const bf16_t*
     float s = 0.f, m = -INFINITY;
     for (int k = 0; k < G; ++k) {
       s += ps[k];
-      m = sb_max_nan(m, pm[k]);
+      m = cn_max_nan(m, pm[k]);
     }
     pooled[(long)b * 2 * L + l] = s / C;
     pooled[(long)b * 2 * L + L + l] = m;
@@ -185,7 +183,7 @@ __global__ __launch_bounds__(256) void cn_sca_pool_bwd_bf16_kernel(const bf16_t*
       float v[8];
       cn_unpack8(*reinterpret_cast<const u32x4*>(x + ((long)b * L + l) * ldx + g * 8), v);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) pm = sb_max_nan(pm, v[j]);
+      for (int j = 0; j < 8; ++j) pm = cn_max_nan(pm, v[j]);
 #pragma unroll
       for (int j = 0; j < 8; ++j) pn += v[j] == pm ? 1.f : 0.f;
     }
@@ -427,14 +425,11 @@ extern "C" int cn_sca_apply_bwd_bf16(const void* dy, long ldd, const void* out, 
 }
 
 // ---------------------------------------------------------------------------
-// F.adaptive_max_pool2d on bf16 NHWC. Window of output o along an axis: [floor(o*In/Out), ceil((o+1)*In/Out)), as in
-// cn_adaptive_maxpool_*_f32 (windows overlap when In % Out != 0). idx (nullable without backward): int32
+// F.adaptive_max_pool2d on bf16 NHWC. Window of output o along an axis: [cn_amp_start, cn_amp_end) (windows overlap
+// when In % Out != 0). idx (nullable without backward): int32
 // [B*Ho*Wo][C], the flat input pixel iy*Wi + ix of the first maximum in row-major window order (a NaN wins, as in
 // ATen). Backward is a gather over the outputs whose windows can hold the input pixel: deterministic, no atomics.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ int bamp_start(int o, int in, int out) { return (int)(((long)o * in) / out); }
-__device__ __forceinline__ int bamp_end(int o, int in, int out) { return (int)((((long)(o + 1)) * in + out - 1) / out); }
-
 __global__ __launch_bounds__(256) void cn_adaptive_maxpool_fwd_bf16_kernel(const bf16_t* __restrict__ x, long ldx,
                                                                           bf16_t* __restrict__ y, long ldy,
                                                                           int* __restrict__ idx, int B, int C, int Hi,
@@ -447,8 +442,8 @@ __global__ __launch_bounds__(256) void cn_adaptive_maxpool_fwd_bf16_kernel(const
     const int b = (int)(po / ((long)Ho * Wo));
     const int op = (int)(po - (long)b * Ho * Wo);
     const int oy = op / Wo, ox = op - oy * Wo;
-    const int y0 = bamp_start(oy, Hi, Ho), y1 = bamp_end(oy, Hi, Ho);
-    const int x0 = bamp_start(ox, Wi, Wo), x1 = bamp_end(ox, Wi, Wo);
+    const int y0 = cn_amp_start(oy, Hi, Ho), y1 = cn_amp_end(oy, Hi, Ho);
+    const int x0 = cn_amp_start(ox, Wi, Wo), x1 = cn_amp_end(ox, Wi, Wo);
     const bf16_t* xb = x + (long)b * Hi * Wi * ldx + c0;
     float best[8];
     int bi[8];
@@ -461,7 +456,7 @@ __global__ __launch_bounds__(256) void cn_adaptive_maxpool_fwd_bf16_kernel(const
         cn_unpack8(*reinterpret_cast<const u32x4*>(xb + (long)p * ldx), v);
 #pragma unroll
         for (int j = 0; j < 8; ++j)
-          if (v[j] > best[j] || v[j] != v[j]) { best[j] = v[j]; bi[j] = p; }
+          if (cn_max_takes(best[j], v[j])) { best[j] = v[j]; bi[j] = p; }
       }
     *reinterpret_cast<u32x4*>(y + po * ldy + c0) = cn_pack8(best);
     if (idx) {

@@ -13,6 +13,7 @@
 // /root/reference/src/cultionet/nn/modules/convolution.py:45-120.
 #include <cstdlib>
 #include "cn_common.h"
+#include "cn_conv_geom.h"
 #include "cn_profile.h"
 #include "cn_slicesum.h"
 
@@ -1158,8 +1159,8 @@ extern "C" int cn_conv2d_bwd_weight_grouped_f32(int G, const float* const* xs, l
                                                 int Cout, int KH, int KW, int stride, int pad, int dil, float* ws,
                                                 long ws_floats, void* stream) {
   if (stride < 1) return CN_ERR_ARG;  // before it is divided by
-  const int Hout = (Hin + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
-  const int Wout = (Win + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
+  const int Hout = cn_conv_out(Hin, KH, stride, pad, dil);
+  const int Wout = cn_conv_out(Win, KW, stride, pad, dil);
   return cn_wgrad_generic_g(G, dys, dybs, Cout, Hout, Wout, xs, xbs, Cin, Hin, Win, stride, KH, KW, dil, pad, dws, B,
                             ws, ws_floats, (hipStream_t)stream);
 }
@@ -1169,8 +1170,8 @@ extern "C" int cn_conv2d_bwd_weight_f32(const float* x, long xbs, const float* d
                                         int Cin, int Hin, int Win, int Cout, int KH, int KW, int stride, int pad,
                                         int dil, float* ws, long ws_floats, void* stream) {
   if (stride < 1) return CN_ERR_ARG;  // before it is divided by
-  const int Hout = (Hin + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
-  const int Wout = (Win + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
+  const int Hout = cn_conv_out(Hin, KH, stride, pad, dil);
+  const int Wout = cn_conv_out(Win, KW, stride, pad, dil);
   return cn_wgrad_generic(dy, dybs, Cout, Hout, Wout, x, xbs, Cin, Hin, Win, stride, KH, KW, dil, pad, dw, B, ws,
                           ws_floats, (hipStream_t)stream);
 }
@@ -1181,8 +1182,8 @@ extern "C" int cn_conv_transpose2d_bwd_weight_f32(const float* x, long xbs, cons
                                                   int stride, int pad, int out_pad, float* ws, long ws_floats,
                                                   void* stream) {
   if (out_pad < 0 || (out_pad > 0 && out_pad >= stride)) return CN_ERR_ARG;
-  const int Hout = (Hin - 1) * stride - 2 * pad + KH + out_pad;  // dy lives on the output_padding grid (cn_conv.hip)
-  const int Wout = (Win - 1) * stride - 2 * pad + KW + out_pad;
+  const int Hout = cn_convt_out(Hin, KH, stride, pad, out_pad);  // dy lives on the output_padding grid (cn_conv.hip)
+  const int Wout = cn_convt_out(Win, KW, stride, pad, out_pad);
   return cn_wgrad_generic(x, xbs, Cin, Hin, Win, dy, dybs, Cout, Hout, Wout, stride, KH, KW, 1, pad, dw, B, ws,
                           ws_floats, (hipStream_t)stream);
 }

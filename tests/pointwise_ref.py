@@ -2,7 +2,7 @@
 on the CPU by tests/test_pointwise_ref.py. Plain torch / numpy: no GPU, no import of the package's kernels.
 
 * resize_matrix: F.interpolate(mode="bilinear", align_corners=True) as a matrix. The WEIGHTS are the fp32 ones ATen
-  (and bl_src of cn_pointwise.hip) computes -- index arithmetic restated in numpy.float32 -- held in float64; the
+  (and cn_bl_src of cn_index.h) computes -- index arithmetic restated in numpy.float32 -- held in float64; the
   contraction is float64. A float64 F.interpolate computes the weights in double and sits hundreds of fp32 units away.
 * sca_ref64: SpatialChannelAttention as ResidualAConv applies it (nn.AdaptiveMaxPool2d(1) for the H*W maximum: first
   maximum; torch.amax for the channel maximum: gradient split evenly among ties).

@@ -860,8 +860,11 @@ def test_conv2d_f32_random_bound(case, ws):
     with conv_workspace(ws):
         xc = Canvas(x.shape, F32, dev, fill=GARB, data=x)
         yc = Canvas(y64.shape, F32, dev)
-        L.call("cn_conv2d_fwd_f32", xc.ptr, xc.pitch, pack_f32(wd, T, Cin, Cout, T, Cin * T, 1).data_ptr(),
-               b.float().to(dev).data_ptr(), yc.ptr, yc.pitch, B, Cin, H, W, Cout, k, k, s, p, d, 0, st)
+        # both operands stay referenced until the launch is queued: a temporary pack would be freed as soon as its
+        # pointer is taken, and the bias allocated next may land inside its block and overwrite the first weights
+        wp, bd = pack_f32(wd, T, Cin, Cout, T, Cin * T, 1), b.float().to(dev)
+        L.call("cn_conv2d_fwd_f32", xc.ptr, xc.pitch, wp.data_ptr(), bd.data_ptr(), yc.ptr, yc.pitch, B, Cin, H, W, Cout,
+               k, k, s, p, d, 0, st)
         dyc = Canvas(dy.shape, F32, dev, fill=GARB, data=dy)
         dxc = Canvas(x.shape, F32, dev)
         L.call("cn_conv2d_bwd_data_f32", dyc.ptr, dyc.pitch, pack_f32(wd, T, Cout, Cin, Cin * T, T, 1).data_ptr(),
