@@ -14,6 +14,7 @@ NHWC, slack after the end); inputs sit in buffers whose gaps hold a finite garba
 """
 from __future__ import annotations
 
+import math
 import os
 import sys
 
@@ -142,6 +143,57 @@ class Canvas:
         c = self.buf.clone()
         self.view(c).fill_(self.fill)
         assert torch.equal(c, torch.full_like(c, self.fill)), f"{what}: written outside the tensor"
+
+
+NAN = float("nan")
+RED = 9  # roundings of cn_block_sum<float, 256>: 6 wave levels + 3 adds of the four wave totals
+
+
+def dev():
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    return torch.device("cuda:0")
+
+
+def canary(cv, what):
+    """Canvas.assert_canary that also works for a NaN fill."""
+    c = cv.buf.clone()
+    cv.view(c).fill_(cv.fill)
+    ok = bool(c.isnan().all()) if cv.fill != cv.fill else bool((c == cv.fill).all())
+    assert ok, f"{what}: written outside the tensor"
+
+
+class Flat:
+    """A dense tensor of any shape at the front of a filled buffer with SLACK elements behind it."""
+
+    def __init__(self, shape, dev, fill=NAN, dtype=F32, data=None):
+        self.n, self.fill = math.prod(int(d) for d in shape), fill
+        self.buf = torch.full((self.n + SLACK,), fill, dtype=dtype, device=dev)
+        self.t = self.buf[:self.n].view(*shape)
+        if data is not None:
+            self.t.copy_(data.to(dev).to(dtype))
+
+    @property
+    def ptr(self):
+        return self.buf.data_ptr()
+
+    def assert_slack(self, what):
+        s = self.buf[self.n:]
+        ok = bool(s.isnan().all()) if self.fill != self.fill else bool((s == self.fill).all())
+        assert ok, f"{what}: written past the end"
+
+
+def same(got, ref, what):
+    """torch.equal that lets NaN equal NaN."""
+    got, ref = got.detach().double().cpu(), ref.double()
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    ok = (got == ref) | (got.isnan() & ref.isnan())
+    assert bool(ok.all()), f"{what}: {int((~ok).sum())} of {ref.numel()} differ; first at {tuple((~ok).nonzero()[0].tolist())}"
+
+
+def act_err(v, e_v, a):
+    """Error of an fp32 sigmoid / SiLU a(v) evaluated at v +- e_v: slope within [-0.1, 1.1] times e_v, plus
+    (|v| + 8) u relative for the expf, the add and the division (see test_fused_bf16_random_bound)."""
+    return 1.1 * e_v + (v.abs() + e_v + 8) * U32 * (a.abs() + e_v)
 
 
 def lib():

@@ -17,6 +17,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from conv_exact_worker import half_ulp_bf16, ints
+
 U32 = 2.0 ** -24
 
 
@@ -67,22 +69,27 @@ def candidates(n_in: int, n_out: int) -> torch.Tensor:
 # spatial-channel attention
 # ---------------------------------------------------------------------------------------------------------------------
 
-def sca_ref64(mod, skip, out):
+def sca_ref64(mod, skip, out, paths=False):
     """The reference's SpatialChannelAttention applied as ResidualAConv does, in float64 (torch.amax channel max,
-    nn.AdaptiveMaxPool2d(1) H*W max). Returns y and the float64 leaves of the parameters by name."""
+    nn.AdaptiveMaxPool2d(1) H*W max). Returns y and the float64 leaves of the parameters by name.
+
+    paths=True: each of the four pools (H*W average, H*W max, channel mean, channel max) reads its own leaf copy of
+    skip, and the four leaves are returned as a third value: after y.backward() their .grad are the four paths'
+    gradients into skip (their sum is d skip; `skip` itself then receives no gradient)."""
     fc1, fc2 = mod.channel_attention.fc1, mod.channel_attention.fc2
     w = lambda m: m.weight.detach().double().requires_grad_(True)
     w1a, w2a, w1m, w2m, wc = w(fc1[0]), w(fc1[2]), w(fc2[0]), w(fc2[2]), w(mod.spatial_attention.conv)
     gamma = mod.gamma.detach().double().requires_grad_(True)
     mlp = lambda v, a, b: F.conv2d(F.silu(F.conv2d(v, a)), b)
-    ca = torch.sigmoid(mlp(skip.mean((2, 3), keepdim=True), w1a, w2a) + mlp(F.adaptive_max_pool2d(skip, 1), w1m, w2m))
-    pooled = torch.cat([skip.mean(1, keepdim=True), skip.amax(1, keepdim=True)], 1)
+    s = [skip.detach().clone().requires_grad_(True) for _ in range(4)] if paths else [skip] * 4
+    ca = torch.sigmoid(mlp(s[0].mean((2, 3), keepdim=True), w1a, w2a) + mlp(F.adaptive_max_pool2d(s[1], 1), w1m, w2m))
+    pooled = torch.cat([s[2].mean(1, keepdim=True), s[3].amax(1, keepdim=True)], 1)
     sa = torch.sigmoid(F.conv2d(pooled, wc, padding=1))
     y = out * (1.0 + gamma * ((ca + sa) * 0.5))
     names = {"channel_attention.fc1.0.weight": w1a, "channel_attention.fc1.2.weight": w2a,
              "channel_attention.fc2.0.weight": w1m, "channel_attention.fc2.2.weight": w2m,
              "spatial_attention.conv.weight": wc, "gamma": gamma}
-    return y, names
+    return (y, names, s) if paths else (y, names)
 
 
 def sca_pools64(x):
@@ -90,6 +97,163 @@ def sca_pools64(x):
     B, C = x.shape[:2]
     mx, idx = F.adaptive_max_pool2d(x, 1, return_indices=True)
     return x.mean((2, 3)), mx.view(B, C), idx.view(B, C), x.mean(1), x.amax(1)
+
+
+def sca_pool_bwd_terms64(x, davg, dmx, dpool):
+    """float64 autograd of the four pools, path by path: the gradients into x of the H*W average (davg / L), the H*W
+    max (dmx to the FIRST maximum, nn.AdaptiveMaxPool2d(1)), the channel mean (dpool[:, 0] / C) and the channel max
+    (dpool[:, 1] split evenly among the tied channels, torch.amax), and the sum of their absolute values."""
+    B, C = x.shape[:2]
+    xr = x.clone().requires_grad_(True)
+    terms = [(xr.mean((2, 3)), davg), (F.adaptive_max_pool2d(xr, 1).view(B, C), dmx), (xr.mean(1), dpool[:, 0]),
+             (xr.amax(1), dpool[:, 1])]
+    grads = [torch.autograd.grad((t * d).sum(), xr, retain_graph=True)[0] for t, d in terms]
+    return grads, sum(g.abs() for g in grads)
+
+
+def sca_att64(ca, sconv, gamma):
+    """att = 1 + g (a + sa), g = gamma / 2 (exact), with its fp32 error: sigmoid (|s| + 8) u sa, the add, the product
+    and the add of 1 (one rounding each)."""
+    B, C = ca.shape
+    g = 0.5 * float(gamma)
+    sa = torch.sigmoid(sconv)                                  # [B,1,H,W]
+    inner = ca.view(B, C, 1, 1) + sa
+    e_inner = (sconv.abs() + 8) * U32 * sa + U32 * inner
+    att = 1 + g * inner
+    mag = 1 + abs(g) * inner
+    e_att = abs(g) * e_inner + U32 * abs(g) * inner + U32 * mag
+    return g, sa, inner, e_inner, att, mag, e_att
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# bf16 spatial-channel attention and adaptive max pool (cn_sca_bf16.hip): tiling, cases, inputs, bounds
+# ---------------------------------------------------------------------------------------------------------------------
+
+def sca_tile(C, L):
+    """G, R, pixels per block, blocks per image: 256 threads = R pixel rows x G = C/8 channel groups (R = 256 // G,
+    threads past R*G idle), a block walks 8 such rows of pixels of one image."""
+    G = C // 8
+    R = 256 // G
+    return G, R, 8 * R, -(-L // (8 * R))
+
+
+# B, C, H, W, ld -- the corners of the tiling (see sca_tile)
+SCA_BF16_SHAPES = [
+    (2, 8, 5, 7, 16),          # 2048 px/block (s_max / s_dmax / s_dmean full), one partial block
+    (1, 8, 3, 683, 8),         # L = 2049: one pixel in the second block
+    (2, 24, 9, 11, 32),        # G = 3, R = 85: 680 px/block, one idle thread
+    (1, 24, 3, 227, 24),       # L = 681: one pixel in the second block
+    (1, 96, 25, 25, 104),      # 168 px/block
+    (2, 1024, 5, 7, 1024),     # the launcher's limit: R = 2, 16 px/block, s_cs full
+    (2, 256, 33, 33, 264),
+]
+# B, C, H, W -- planes of 2^k pixels: the backward's fl(1/L) and davg * fl(1/L) are exact
+SCA_BF16_POW2 = [(2, 8, 32, 64), (2, 24, 32, 32), (1, 96, 16, 16), (1, 1024, 4, 8)]
+SCA_POOL_BWD_D = 7  # fp32 roundings of cn_sca_pool_bwd_bf16 before the store, see sca_pool_bwd_bound
+
+
+def bf_randn(shape, seed, scale=1.0):
+    """bf16-representable N(0, scale^2) values as float64."""
+    g = torch.Generator().manual_seed(seed)
+    return (torch.randn(tuple(shape), generator=g, dtype=torch.float64) * scale).float().to(torch.bfloat16).double()
+
+
+def f32_randn(shape, seed, scale=1.0):
+    """fp32-representable N(0, scale^2) values as float64."""
+    g = torch.Generator().manual_seed(seed)
+    return (torch.randn(tuple(shape), generator=g, dtype=torch.float64) * scale).float().double()
+
+
+def bf_few(shape, seed):
+    """Multiples of 1/2 from five values (-1 .. 1): ties everywhere."""
+    g = torch.Generator().manual_seed(seed)
+    return torch.randint(-2, 3, tuple(shape), generator=g, dtype=torch.int64).double() * 0.5
+
+
+def bf16_store_bound(ref, D, A, old=None):
+    """Per-element bound of a bf16 store of an fp32 value that took D roundings on the way, each at most u = 2^-24 of
+    A (the same expression on absolute values), and was then added to the buffer's old value (one more rounding, on
+    A + |old|): e = D u A [+ u (A + |old|)]; the store rounds once more, half a bf16 ulp at |ref| + e."""
+    e = D * U32 * A
+    if old is not None:
+        e = e + U32 * (A + old.abs())
+    return e + half_ulp_bf16(ref.abs() + e)
+
+
+def sca_pool_bwd_inputs(B, C, H, W, few, seed):
+    """x (bf16-representable; few-valued or random), fp32 davg, dmx ~ N(0, 16), dpool ~ N(0, 1), bf16 base."""
+    x = bf_few((B, C, H, W), seed) if few else bf_randn((B, C, H, W), seed)
+    return x, f32_randn((B, C), seed + 1, 4.0), f32_randn((B, C), seed + 2, 4.0), \
+        f32_randn((B, 2, H, W), seed + 3), bf_randn((B, C, H, W), seed + 4, 0.05)
+
+
+def sca_pool_bwd_bound(ref, A, old=None):
+    """cn_sca_pool_bwd_bf16: fl(1/L) (1) and davg * fl(1/L) (1), dpool0 / C (1), dpool1 / n (1), three adds (3):
+    D = 7 on A = the sum of the four absolute terms; dmx and the masks are exact. `old`: the accumulated-into value."""
+    return bf16_store_bound(ref, SCA_POOL_BWD_D, A, old)
+
+
+def sca_pool_bwd_exact_inputs(B, C, H, W, seed):
+    """The exact layer's data: per pixel 1, 2, 4 or 8 channels hold the pixel's maximum (1/2 or 1), the others are
+    smaller multiples of 1/2; davg = integers * L, dmx integers, dpool0 = integers * C, dpool1 = integers * 8, base
+    integers: every quotient and every sum of the kernel is an integer."""
+    g = torch.Generator().manual_seed(seed)
+    n = 2 ** torch.randint(0, 4, (B, 1, H, W), generator=g)
+    rank = torch.rand(B, C, H, W, generator=g).argsort(1).argsort(1)
+    top = torch.randint(1, 3, (B, 1, H, W), generator=g).double() * 0.5
+    low = torch.randint(-2, 1, (B, C, H, W), generator=g, dtype=torch.int64).double() * 0.5
+    x = torch.where(rank < n, top.expand(B, C, H, W), low)
+    L = H * W
+    davg, dmx = ints((B, C), -3, 3, seed + 1) * L, ints((B, C), -3, 3, seed + 2)
+    dpool = torch.stack([ints((B, H, W), -3, 3, seed + 3) * C, ints((B, H, W), -3, 3, seed + 4) * 8], 1)
+    return x, davg, dmx, dpool, ints((B, C, H, W), -8, 8, seed + 5)
+
+
+def maxpool_bwd64(x, dy, size):
+    """F.adaptive_max_pool2d's float64 y, idx, dx, the same on |dy| and the number of windows whose first maximum
+    each input pixel is."""
+    xr = x.clone().requires_grad_(True)
+    y, idx = F.adaptive_max_pool2d(xr, size, return_indices=True)
+    dx, dxa, cnt = (torch.autograd.grad(y, xr, g, retain_graph=True)[0] for g in (dy, dy.abs(), torch.ones_like(dy)))
+    return y.detach(), idx, dx, dxa, cnt
+
+
+# B, C, H, W, ld, few-valued x, accumulate: every bounded pool-backward case of the GPU module
+SCA_POOL_BWD_BOUNDED = [s + (few, acc) for s in SCA_BF16_SHAPES for few in (True, False) for acc in (0, 1)]
+
+
+def sca_gate_bound(v, att, mag, e_att, old=None):
+    """bf16 store of v * att [+ old] (cn_sca_apply_fwd_bf16's y, cn_sca_apply_bwd_bf16's dout), att = 1 + g (ca + sa)
+    within e_att of the fp32 factor (sca_att64): the factor's error, the product's rounding, with `old` one more add,
+    then the store. Returns the float64 value and its bound."""
+    ref = v * att + (0.0 if old is None else old)
+    e = v.abs() * e_att + U32 * v.abs() * (mag + e_att)
+    if old is not None:
+        e = e + U32 * (v.abs() * (mag + e_att) + old.abs())
+    return ref, e + half_ulp_bf16(ref.abs() + e)
+
+
+# B, C, Hi, Wi, Ho, Wo, ld
+MAXPOOL_BF16_CASES = [
+    (2, 8, 7, 7, 3, 3, 16),          # windows [0,3) [2,5) [4,7): four of them share a pixel
+    (1, 24, 25, 25, 12, 12, 32),
+    (2, 8, 5, 9, 5, 9, 8),           # the identity window
+]
+
+
+def maxpool_inputs(B, C, Hi, Wi, Ho, Wo, seed):
+    """Few-valued x (multiples of 1/2) with a strict maximum planted, in every plane, on one pixel that four windows
+    share and on one that two share (where the windows overlap at all)."""
+    x = bf_few((B, C, Hi, Wi), seed)
+    own = lambda n_in, n_out: [sum(1 for o in range(n_out) if (o * n_in) // n_out <= i < -(-(o + 1) * n_in // n_out))
+                               for i in range(n_in)]
+    ny, nx = own(Hi, Ho), own(Wi, Wo)
+    if max(ny) > 1 and max(nx) > 1:
+        y2, x2 = ny.index(2), nx.index(2)
+        x[:, :, y2, x2] = 2.0                       # in 2 x 2 windows
+        x1 = max(i for i, n in enumerate(nx) if n == 1 and abs(i - x2) > 2)
+        x[:, :, y2, x1] = 1.5                       # in 2 x 1 windows
+    return x
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -20,18 +20,13 @@ import torch
 import torch.nn.functional as F
 
 import pointwise_ref as R
-from conv_exact_worker import (BF, F32, GARB, SLACK, U32, Canvas, assert_exact, bounded, half_ulp_bf16, ints, lib,
+from conv_exact_worker import (BF, F32, GARB, RED, U32, Canvas, Flat, assert_exact, bounded, half_ulp_bf16, ints, lib,
                                premise, rb, stream, term_bound)
+from conv_exact_worker import act_err as _act_err, canary as _canary, dev as _dev, same as _same
 
 pytestmark = pytest.mark.gpu
 
 NAN = float("nan")
-RED = 9  # roundings of cn_block_sum<float, 256>: 6 wave levels + 3 adds of the four wave totals
-
-
-def _dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
 
 
 def _randn(shape, seed, scale=1.0):
@@ -44,48 +39,6 @@ def _few(shape, seed):
     """Integers from five values (-2..2): ties everywhere."""
     g = torch.Generator().manual_seed(seed)
     return torch.randint(-2, 3, tuple(shape), generator=g, dtype=torch.int64).double()
-
-
-def _canary(cv, what):
-    """Canvas.assert_canary that also works for a NaN fill."""
-    c = cv.buf.clone()
-    cv.view(c).fill_(cv.fill)
-    ok = bool(c.isnan().all()) if cv.fill != cv.fill else bool((c == cv.fill).all())
-    assert ok, f"{what}: written outside the tensor"
-
-
-class Flat:
-    """A dense tensor of any shape at the front of a filled buffer with SLACK elements behind it."""
-
-    def __init__(self, shape, dev, fill=NAN, dtype=F32, data=None):
-        self.n, self.fill = int(np.prod(shape)), fill
-        self.buf = torch.full((self.n + SLACK,), fill, dtype=dtype, device=dev)
-        self.t = self.buf[:self.n].view(*shape)
-        if data is not None:
-            self.t.copy_(data.to(dev).to(dtype))
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr()
-
-    def assert_slack(self, what):
-        s = self.buf[self.n:]
-        ok = bool(s.isnan().all()) if self.fill != self.fill else bool((s == self.fill).all())
-        assert ok, f"{what}: written past the end"
-
-
-def _same(got, ref, what):
-    """torch.equal that lets NaN equal NaN."""
-    got, ref = got.detach().double().cpu(), ref.double()
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    ok = (got == ref) | (got.isnan() & ref.isnan())
-    assert bool(ok.all()), f"{what}: {int((~ok).sum())} of {ref.numel()} differ; first at {tuple((~ok).nonzero()[0].tolist())}"
-
-
-def _act_err(v, e_v, a):
-    """Error of an fp32 sigmoid / SiLU a(v) evaluated at v +- e_v: slope within [-0.1, 1.1] times e_v, plus
-    (|v| + 8) u relative for the expf, the add and the division (see test_fused_bf16_random_bound)."""
-    return 1.1 * e_v + (v.abs() + e_v + 8) * U32 * (a.abs() + e_v)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -527,12 +480,8 @@ def _sca_pool_bwd(x, davg, dmx, dpool, base, accumulate):
 
 def _sca_pool_bwd_ref(x, davg, dmx, dpool):
     """float64 autograd of the four pools (and the same on absolute values, term by term, for the bound)."""
-    B, C = x.shape[:2]
-    xr = x.clone().requires_grad_(True)
-    terms = [(xr.mean((2, 3)), davg), (F.adaptive_max_pool2d(xr, 1).view(B, C), dmx), (xr.mean(1), dpool[:, 0]),
-             (xr.amax(1), dpool[:, 1])]
-    grads = [torch.autograd.grad((t * d).sum(), xr, retain_graph=True)[0] for t, d in terms]
-    return sum(grads), sum(g.abs() for g in grads)
+    grads, asum = R.sca_pool_bwd_terms64(x, davg, dmx, dpool)
+    return sum(grads), asum
 
 
 @pytest.mark.parametrize("B,C,H,W", [(2, 6, 3, 5), (2, 5, 25, 25), (1, 7, 33, 33)])
@@ -704,18 +653,7 @@ def test_sca_mlp_f32_refuses_more_than_1024_channels():
 # fp32 spatial-channel attention: apply
 # ---------------------------------------------------------------------------------------------------------------------
 
-def _att64(ca, sconv, gamma):
-    """att = 1 + g (a + sa), g = gamma / 2 (exact), with its fp32 error: sigmoid (|s| + 8) u sa, the add, the product
-    and the add of 1 (one rounding each)."""
-    B, C = ca.shape
-    g = 0.5 * float(gamma)
-    sa = torch.sigmoid(sconv)                                  # [B,1,H,W]
-    inner = ca.view(B, C, 1, 1) + sa
-    e_inner = (sconv.abs() + 8) * U32 * sa + U32 * inner
-    att = 1 + g * inner
-    mag = 1 + abs(g) * inner
-    e_att = abs(g) * e_inner + U32 * abs(g) * inner + U32 * mag
-    return g, sa, inner, e_inner, att, mag, e_att
+_att64 = R.sca_att64
 
 
 @pytest.mark.parametrize("B,C,H,W,gamma", [(2, 5, 25, 25, 0.9), (1, 3, 33, 33, -0.7), (2, 6, 3, 5, 0.9)])

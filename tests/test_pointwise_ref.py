@@ -199,3 +199,169 @@ def test_stitch_ref_matches_scalar_loops():
                     want[k, r0 + y, c0 + x] = int(v)
     assert np.array_equal(got, want)
     assert got[1, 4 + 1, 0 + 1] == 0  # the NaN
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# bf16 spatial-channel attention / max pool: the per-element bounds can fail
+# ---------------------------------------------------------------------------------------------------------------------
+from conv_exact_worker import rb  # noqa: E402
+
+
+def _flagged(value64, ref, bound, touched, what, need=True):
+    """A kernel computing `value64` perfectly (one rounding to bf16) must violate the bound at more than half of the
+    elements the change touches."""
+    n = int(touched.sum())
+    if n == 0:
+        assert not need, f"{what}: the mutant changes nothing"
+        return None
+    frac = float(((rb(value64) - ref).abs() > bound)[touched].double().mean())
+    print(f"MUTANT {what}: {100 * frac:.1f} % of {n} touched elements flagged")
+    assert frac > 0.5, f"{what}: only {100 * frac:.1f} % of {n} touched elements violate the bound"
+    return frac
+
+
+def _pool_bwd_emulate32(x, davg, dmx, dpool, old):
+    """The kernel's order in fp32: davg * fl(1/L), + dm, + dpool0 / C, + dpool1 / n, + old."""
+    f = torch.float32
+    B, C, H, W = x.shape
+    L = H * W
+    cx = x.amax(1, keepdim=True)
+    tie = x == cx
+    n = tie.sum(1, keepdim=True).to(f)
+    first = F.adaptive_max_pool2d(x, 1, return_indices=True)[1].view(B, C, 1)
+    at = (torch.arange(L).view(1, 1, L) == first).view(B, C, H, W)
+    invL = torch.tensor(1.0, dtype=f) / torch.tensor(float(L), dtype=f)
+    o = davg.to(f).view(B, C, 1, 1) * invL
+    o = o + torch.where(at, dmx.to(f).view(B, C, 1, 1), torch.zeros((), dtype=f))
+    o = o + (dpool[:, :1].to(f) / torch.tensor(float(C), dtype=f))
+    o = o + torch.where(tie, dpool[:, 1:].to(f) / n, torch.zeros((), dtype=f))
+    if old is not None:
+        o = o + old.to(f)
+    assert o.dtype == f
+    return o.double()
+
+
+@pytest.mark.parametrize("B,C,H,W,ld,few,acc", R.SCA_POOL_BWD_BOUNDED)
+def test_sca_pool_bwd_bf16_bound_passes_the_kernel_and_fails_mutants(B, C, H, W, ld, few, acc):
+    """D = 7 (+ the accumulate's add): a perfect kernel (float64 rounded once to bf16) and an fp32 emulation of the
+    kernel's order pass at every element; leaving out any of the four terms, giving the channel-max gradient to the
+    first tied channel only, giving the H*W max to the last maximum, or ignoring `accumulate`, fails at more than half
+    of the elements it changes."""
+    x, davg, dmx, dpool, base = R.sca_pool_bwd_inputs(B, C, H, W, few, 900 + C + H)
+    old = base if acc else None
+    g, A = R.sca_pool_bwd_terms64(x, davg, dmx, dpool)
+    ref = sum(g) + (base if acc else 0.0)
+    bound = R.sca_pool_bwd_bound(ref, A, old)
+    what = f"pool bwd {B}x{C}x{H}x{W} few={few} acc={acc}"
+    assert bool(((rb(ref) - ref).abs() <= bound).all()), "a perfect kernel fails the bound"
+    emu = rb(_pool_bwd_emulate32(x, davg, dmx, dpool, old))
+    ratio = float(((emu - ref).abs() / bound).max())
+    print(f"BOUND {what} fp32 emulation: worst err/bound {ratio:.3f}")
+    assert ratio <= 1.0
+    for k, name in enumerate(("H*W average", "H*W max", "channel mean", "channel max")):
+        _flagged(ref - g[k], ref, bound, g[k] != 0, f"{what} without the {name}")
+    if acc:
+        _flagged(ref - base, ref, bound, base != 0, f"{what} ignoring accumulate")
+    if not few:
+        return  # random x ties by accident at a handful of elements at most: the tie rules are judged on few-valued x
+    # channel max to the first tied channel only
+    tie = x == x.amax(1, keepdim=True)
+    firstc = tie & (tie.cumsum(1) == 1)
+    m = ref - g[3] + torch.where(firstc, dpool[:, 1:].expand_as(x), torch.zeros(()).double())
+    _flagged(m, ref, bound, m != ref, f"{what} channel max to the first tie")
+    # H*W max to the last maximum
+    xf = x.flatten(2)
+    last = (H * W - 1) - xf.flip(2).argmax(2)
+    assert bool((xf.gather(2, last.unsqueeze(2)).squeeze(2) == xf.amax(2)).all())
+    glast = torch.zeros_like(xf).scatter_(2, last.unsqueeze(2), dmx.unsqueeze(2)).view_as(x)
+    m = ref - g[1] + glast
+    _flagged(m, ref, bound, m != ref, f"{what} H*W max to the last maximum")
+
+
+@pytest.mark.parametrize("B,C,H,W", R.SCA_BF16_POW2)
+def test_sca_pool_bwd_bf16_exact_inputs(B, C, H, W):
+    """The exact layer's data: 1, 2, 4 or 8 channels at every pixel's maximum (all four occur), ties in the H*W max,
+    every float64 dx an integer of at most 256, and the fp32 emulation of the kernel equal to it."""
+    x, davg, dmx, dpool, base = R.sca_pool_bwd_exact_inputs(B, C, H, W, 950 + C)
+    n = (x == x.amax(1, keepdim=True)).sum(1)
+    assert sorted(n.unique().tolist()) == [1, 2, 4, 8]
+    assert bool((R.sca_pools64(x)[2] > 0).any()) and bool(((x == x.amax((2, 3), keepdim=True)).sum((2, 3)) > 1).any())
+    g, A = R.sca_pool_bwd_terms64(x, davg, dmx, dpool)
+    for old in (None, base):
+        ref = sum(g) + (0.0 if old is None else old)
+        assert torch.equal(ref, ref.round()) and float(ref.abs().max()) <= 256 and torch.equal(rb(ref), ref)
+        assert torch.equal(_pool_bwd_emulate32(x, davg, dmx, dpool, old), ref)
+
+
+def _occurrence_rank(idx):
+    """Per output of [B,C,Ho,Wo] indices: how many earlier outputs (row-major) of the plane chose the same pixel."""
+    B, C = idx.shape[:2]
+    flat = idx.flatten(2)
+    n = flat.shape[2]
+    key = flat * n + torch.arange(n).view(1, 1, n)          # sort by pixel, then by output position
+    order = key.argsort(2)
+    sp = flat.gather(2, order)
+    pos = torch.arange(n).view(1, 1, n).expand(B, C, n)
+    start = torch.where(torch.cat([torch.ones(B, C, 1, dtype=torch.bool), sp[:, :, 1:] != sp[:, :, :-1]], 2), pos, 0)
+    rank_sorted = pos - start.cummax(2)[0]
+    return torch.zeros_like(flat).scatter_(2, order, rank_sorted).view_as(idx)
+
+
+@pytest.mark.parametrize("B,C,Hi,Wi,Ho,Wo,ld", R.MAXPOOL_BF16_CASES)
+@pytest.mark.parametrize("acc", [0, 1])
+def test_maxpool_bwd_bf16_bound_passes_the_kernel_and_fails_the_mutant(B, C, Hi, Wi, Ho, Wo, ld, acc):
+    """D = windows per pixel + accumulate on sum |dy| + |old|. A perfect kernel passes; a kernel that drops the
+    second window of a pixel that is the first maximum of several fails at more than half of those pixels."""
+    x = R.maxpool_inputs(B, C, Hi, Wi, Ho, Wo, 960)
+    dy, base = R.bf_randn((B, C, Ho, Wo), 961), R.bf_randn((B, C, Hi, Wi), 962, 0.05)
+    y, idx, dx, dxa, cnt = R.maxpool_bwd64(x, dy, (Ho, Wo))
+    ref = dx + (base if acc else 0.0)
+    bound = R.bf16_store_bound(ref, cnt, dxa) if not acc else R.bf16_store_bound(ref, cnt, dxa, base)
+    assert bool(((rb(ref) - ref).abs() <= bound).all())
+    overlap = Hi % Ho != 0
+    if overlap:
+        assert bool((cnt == 2).any()) and bool((cnt == 4).any())
+    rank = _occurrence_rank(idx)
+    keep = torch.where(rank == 1, torch.zeros_like(dy), dy)
+    m = torch.zeros(B, C, Hi * Wi, dtype=torch.float64).scatter_add_(2, idx.flatten(2), keep.flatten(2)).view_as(x)
+    assert torch.equal(torch.zeros(B, C, Hi * Wi, dtype=torch.float64).scatter_add_(2, idx.flatten(2), dy.flatten(2))
+                       .view_as(x), dx)
+    m = m + (base if acc else 0.0)
+    _flagged(m, ref, bound, m != ref, f"max pool bwd {Hi}x{Wi}->{Ho}x{Wo} acc={acc} second window dropped",
+             need=overlap)
+
+
+@pytest.mark.parametrize("B,C,H,W,ld", R.SCA_BF16_SHAPES)
+@pytest.mark.parametrize("acc", [0, 1])
+def test_sca_apply_dout_bf16_bound_passes_the_kernel_and_fails_the_mutant(B, C, H, W, ld, acc):
+    """dout = dy (1 + g (ca + sigmoid(sconv))) [+ old]: a perfect kernel passes; one without the sigmoid term fails."""
+    dy, base = R.bf_randn((B, C, H, W), 970), R.bf_randn((B, C, H, W), 971, 0.1)
+    ca, sconv = torch.sigmoid(R.f32_randn((B, C), 972)).float().double(), R.f32_randn((B, 1, H, W), 973, 2.0)
+    gamma = float(torch.tensor(0.9).float())
+    g, sa, inner, e_inner, att, mag, e_att = R.sca_att64(ca, sconv, gamma)
+    old = base if acc else None
+    ref, bound = R.sca_gate_bound(dy, att, mag, e_att, old)
+    assert bool(((rb(ref) - ref).abs() <= bound).all())
+    m = dy * (1 + g * ca.view(B, C, 1, 1)) + (base if acc else 0.0)
+    _flagged(m, ref, bound, m != ref, f"apply dout {B}x{C}x{H}x{W} acc={acc} without sigmoid(sconv)")
+
+
+def test_sca_ref_paths_sum_to_the_skip_gradient():
+    """sca_ref64(paths=True): the four paths' gradients add up to the default form's d skip, y is unchanged."""
+    from oracle import towerunet_oracle as O
+
+    torch.manual_seed(3)
+    mod = O.SpatialChannelAttention(16, "SiLU").double()
+    with torch.no_grad():
+        mod.gamma.fill_(0.8)
+    skip, out, dy = (_rand((2, 16, 5, 7), s).double() for s in (1, 2, 3))
+    s1 = skip.clone().requires_grad_(True)
+    y1, pw1 = R.sca_ref64(mod, s1, out)
+    y1.backward(dy)
+    y2, pw2, leaves = R.sca_ref64(mod, skip, out, paths=True)
+    y2.backward(dy)
+    assert torch.equal(y1, y2) and len(leaves) == 4 and all(float(l.grad.abs().max()) > 0 for l in leaves)
+    tot = sum(l.grad for l in leaves)
+    assert float((tot - s1.grad).abs().max()) <= 1e-14 * float(s1.grad.abs().max())
+    for n in pw1:
+        assert torch.equal(pw1[n].grad, pw2[n].grad) or float((pw1[n].grad - pw2[n].grad).abs().max()) <= 1e-14
