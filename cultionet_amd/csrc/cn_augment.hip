@@ -5,6 +5,9 @@
 // the host and arrive as a plan table; only the per-element noise is generated here (counter-based, never stored), so the
 // kernels keep no state. Two launches per batch: one over x, one over bdist + y. The op is uniform per block
 // (blockIdx.z = sample), a block owns a band of CN_AUG_BR output rows of one plane, and every write is coalesced along W.
+// A tenth op, `roll` (augment/augmenters.py:154-163, augment/augmenter_utils.py:57-108,168-193), shifts each labelled
+// parcel along T by its own amount: it reads the parcel labels of cn_label_parcels_i32 (cn_parcels.hip) and a table of
+// CN_AUG_PARCELS shifts per sample, and is reached through cn_augment_parcels_f32 only.
 //
 // Plan table: CN_AUG_PLAN_WORDS int32 words per sample
 //   [0] op   [1] div   [2] top   [3] left   [4] r   [5] sigma (float bits)   [6] noise seed, low word   [7] high word
@@ -30,10 +33,12 @@
 #define CN_AUG_SALTPEPPER 7
 #define CN_AUG_CROPRESIZE 8
 #define CN_AUG_PERLIN 9
-#define CN_AUG_NOPS 10
+#define CN_AUG_ROLL 10
+#define CN_AUG_NOPS 11
 
 #define CN_AUG_PLAN_WORDS 8
 #define CN_AUG_RMAX 10
+#define CN_AUG_PARCELS 256                  // shifts per sample: the reference keeps its segments as uint8
 #define CN_AUG_PERLIN_FLOATS (4 * (CN_AUG_RMAX + 1) * (CN_AUG_RMAX + 1))
 #define CN_AUG_BR 32                        // output rows per block
 #define CN_AUG_TILE (32 * 33)               // rotation tile, padded against bank conflicts
@@ -165,7 +170,8 @@ __device__ __forceinline__ void cn_aug_geometry(int op, const Ld& ld, const St& 
 
 // Plan rows come from the host, which has validated them (cn_augment_chips_f32); a row that does not fit the plane is
 // still never followed out of bounds: it degrades to `none`.
-__device__ __forceinline__ int cn_aug_checked_op(const int* __restrict__ row, int H, int W, bool have_perlin, CnAugCrop& crop) {
+__device__ __forceinline__ int cn_aug_checked_op(const int* __restrict__ row, int H, int W, bool have_perlin, bool have_parcels,
+                                                 CnAugCrop& crop) {
   int op = row[0];
   crop.div = row[1]; crop.top = row[2]; crop.left = row[3];
   if (op < 0 || op >= CN_AUG_NOPS) op = CN_AUG_NONE;
@@ -178,14 +184,16 @@ __device__ __forceinline__ int cn_aug_checked_op(const int* __restrict__ row, in
     const int r = row[4];
     if (!have_perlin || r < 1 || r > CN_AUG_RMAX || H % r != 0 || W % r != 0) op = CN_AUG_NONE;
   }
+  if (op == CN_AUG_ROLL && !have_parcels) op = CN_AUG_NONE;
   if (op == CN_AUG_GAUSSIAN && (H < 2 || W < 2 || (CN_AUG_BR + 2) * (W + 2) * (int)sizeof(float) > CN_AUG_MAX_LDS)) op = CN_AUG_NONE;
   return op;
 }
 
-// grid (bands, C * T, B); dynamic LDS: max(rotation tile, blur band, perlin gradients)
+// grid (bands, C * T, B); dynamic LDS: max(rotation tile, blur band, perlin gradients, parcel shifts)
 template <typename TIn>
 __global__ __launch_bounds__(256) void cn_augment_x_kernel(const TIn* __restrict__ x, float* __restrict__ out,
                                                           const int* __restrict__ plan, const float* __restrict__ perlin,
+                                                          const int* __restrict__ labels, const int* __restrict__ parcel,
                                                           const float* __restrict__ mean, const float* __restrict__ stdv,
                                                           int T, int H, int W, float scale, float lo, float hi) {
   extern __shared__ float smem[];
@@ -194,7 +202,7 @@ __global__ __launch_bounds__(256) void cn_augment_x_kernel(const TIn* __restrict
   const int r0 = blockIdx.x * CN_AUG_BR, r1 = min(r0 + CN_AUG_BR, H);
   const int* row = plan + (long)b * CN_AUG_PLAN_WORDS;
   CnAugCrop crop;
-  const int op = cn_aug_checked_op(row, H, W, perlin != nullptr, crop);
+  const int op = cn_aug_checked_op(row, H, W, perlin != nullptr, labels != nullptr && parcel != nullptr, crop);
   const long HW = (long)H * W;
   const long base = ((long)b * gridDim.y + plane) * HW;
   const CnAugLoad<TIn> ld{x, scale, lo, hi};
@@ -282,6 +290,26 @@ __global__ __launch_bounds__(256) void cn_augment_x_kernel(const TIn* __restrict
     }
     return;
   }
+  if (op == CN_AUG_ROLL) {
+    // torch.roll(xseg, s, dims=2) where segments == prop.label: out[t] = in[(t - s) mod T], s the shift of the pixel's
+    // parcel. The segments are uint8 in the reference, so label k shares the shift of k & 255 and 256, 512, ... stay put.
+    // A shift that does not fit T degrades to 0 (the host has refused it already).
+    int* shift = (int*)smem;
+    if (tid < CN_AUG_PARCELS) {
+      const int s = parcel[(long)b * CN_AUG_PARCELS + tid];
+      shift[tid] = (tid == 0 || s <= -T || s >= T) ? 0 : s;
+    }
+    __syncthreads();
+    const long lbase = (long)b * HW, cbase = base - (long)t * HW;  // plane t = 0 of this channel
+    for (int idx = tid; idx < n; idx += 256) {
+      const long off = (long)r0 * W + idx;
+      int ts = t - shift[labels[lbase + off] & (CN_AUG_PARCELS - 1)];
+      ts += ts < 0 ? T : 0;
+      ts -= ts >= T ? T : 0;
+      st(base + off, ld(cbase + (long)ts * HW + off));
+    }
+    return;
+  }
   cn_aug_geometry<float>(op, ld, st, base, H, W, r0, r1, crop, smem);
 }
 
@@ -295,8 +323,8 @@ __global__ __launch_bounds__(256) void cn_augment_target_kernel(const void* __re
   const int b = blockIdx.z;
   const int r0 = blockIdx.x * CN_AUG_BR, r1 = min(r0 + CN_AUG_BR, H);
   CnAugCrop crop;
-  int op = cn_aug_checked_op(plan + (long)b * CN_AUG_PLAN_WORDS, H, W, true, crop);
-  if (op == CN_AUG_GAUSSIAN || op == CN_AUG_SALTPEPPER || op == CN_AUG_PERLIN) op = CN_AUG_NONE;  // x only
+  int op = cn_aug_checked_op(plan + (long)b * CN_AUG_PLAN_WORDS, H, W, true, true, crop);
+  if (op == CN_AUG_GAUSSIAN || op == CN_AUG_SALTPEPPER || op == CN_AUG_PERLIN || op == CN_AUG_ROLL) op = CN_AUG_NONE;  // x only
   const long base = (long)b * H * W;
   if (blockIdx.y == 0) {
     if (bdist == nullptr) return;
@@ -315,11 +343,14 @@ __global__ __launch_bounds__(256) void cn_augment_target_kernel(const void* __re
 // y: [B][H][W] labels (ydtype: 1 i32, 2 i16, 3 u16, 4 i64) -> y_out int64.
 // plan_host / plan_dev: the SAME [B][CN_AUG_PLAN_WORDS] table in host memory (validated here, before anything is
 // launched) and in device memory (read by the kernels); perlin_dev: [B][CN_AUG_PERLIN_FLOATS], nullable when no sample
-// is `perlin`. Two launches, no allocation, no synchronisation.
-extern "C" int cn_augment_chips_f32(const void* x, int xdtype, const void* bdist, int bdtype, const void* y, int ydtype,
-                                    float* x_out, float* bdist_out, long long* y_out, const int* plan_host,
-                                    const int* plan_dev, const float* perlin_dev, const float* mean, const float* stdv,
-                                    int B, int C, int T, int H, int W, float scale, float lo, float hi, void* stream_) {
+// is `perlin`. labels_dev: [B][H][W] parcel labels (cn_label_parcels_i32); parcel_host / parcel_dev: the SAME
+// [B][CN_AUG_PARCELS] table of shifts in host and in device memory; all three nullable when no sample is `roll`.
+// Two launches, no allocation, no synchronisation.
+extern "C" int cn_augment_parcels_f32(const void* x, int xdtype, const void* bdist, int bdtype, const void* y, int ydtype,
+                                      float* x_out, float* bdist_out, long long* y_out, const int* plan_host,
+                                      const int* plan_dev, const float* perlin_dev, const int* labels_dev,
+                                      const int* parcel_host, const int* parcel_dev, const float* mean, const float* stdv,
+                                      int B, int C, int T, int H, int W, float scale, float lo, float hi, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (B <= 0 || C <= 0 || T <= 0 || H <= 0 || W <= 0) return CN_OK;
   if (x == nullptr || x_out == nullptr || y == nullptr || y_out == nullptr || plan_host == nullptr || plan_dev == nullptr) return CN_ERR_ARG;
@@ -353,10 +384,18 @@ extern "C" int cn_augment_chips_f32(const void* x, int xdtype, const void* bdist
         if (perlin_dev == nullptr || r < 1 || r > CN_AUG_RMAX || H % r != 0 || W % r != 0) return CN_ERR_ARG;
         break;
       }
+      case CN_AUG_ROLL: {
+        if (labels_dev == nullptr || parcel_host == nullptr || parcel_dev == nullptr) return CN_ERR_ARG;
+        const int* tab = parcel_host + (long)b * CN_AUG_PARCELS;
+        if (tab[0] != 0) return CN_ERR_ARG;
+        for (int k = 1; k < CN_AUG_PARCELS; ++k)
+          if (tab[k] <= -T || tab[k] >= T) return CN_ERR_ARG;
+        break;
+      }
       default: return CN_ERR_ARG;
     }
   }
-  size_t lds = CN_AUG_TILE * sizeof(float);  // covers the perlin gradients too: 2 * 11 * 11 * 3 floats
+  size_t lds = CN_AUG_TILE * sizeof(float);  // covers the perlin gradients (2 * 11 * 11 * 3 floats) and the parcel shifts too
   if (blur) {
     const size_t band = (size_t)(CN_AUG_BR + 2) * (W + 2) * sizeof(float);
     if (band > CN_AUG_MAX_LDS) return CN_ERR_LDS;
@@ -365,14 +404,23 @@ extern "C" int cn_augment_chips_f32(const void* x, int xdtype, const void* bdist
   const int bands = cn_cdiv(H, CN_AUG_BR);
   const dim3 grid(bands, C * T, B), block(256);
   switch (xdtype) {
-    case 0: CN_LAUNCH(cn_augment_x_kernel<float>, grid, block, lds, stream, (const float*)x, x_out, plan_dev, perlin_dev, mean, stdv, T, H, W, scale, lo, hi); break;
-    case 1: CN_LAUNCH(cn_augment_x_kernel<int>, grid, block, lds, stream, (const int*)x, x_out, plan_dev, perlin_dev, mean, stdv, T, H, W, scale, lo, hi); break;
-    case 2: CN_LAUNCH(cn_augment_x_kernel<short>, grid, block, lds, stream, (const short*)x, x_out, plan_dev, perlin_dev, mean, stdv, T, H, W, scale, lo, hi); break;
-    default: CN_LAUNCH(cn_augment_x_kernel<unsigned short>, grid, block, lds, stream, (const unsigned short*)x, x_out, plan_dev, perlin_dev, mean, stdv, T, H, W, scale, lo, hi); break;
+    case 0: CN_LAUNCH(cn_augment_x_kernel<float>, grid, block, lds, stream, (const float*)x, x_out, plan_dev, perlin_dev, labels_dev, parcel_dev, mean, stdv, T, H, W, scale, lo, hi); break;
+    case 1: CN_LAUNCH(cn_augment_x_kernel<int>, grid, block, lds, stream, (const int*)x, x_out, plan_dev, perlin_dev, labels_dev, parcel_dev, mean, stdv, T, H, W, scale, lo, hi); break;
+    case 2: CN_LAUNCH(cn_augment_x_kernel<short>, grid, block, lds, stream, (const short*)x, x_out, plan_dev, perlin_dev, labels_dev, parcel_dev, mean, stdv, T, H, W, scale, lo, hi); break;
+    default: CN_LAUNCH(cn_augment_x_kernel<unsigned short>, grid, block, lds, stream, (const unsigned short*)x, x_out, plan_dev, perlin_dev, labels_dev, parcel_dev, mean, stdv, T, H, W, scale, lo, hi); break;
   }
   int rc = cn_check_launch();
   if (rc != CN_OK) return rc;
   CN_LAUNCH(cn_augment_target_kernel, dim3(bands, 2, B), block, 0, stream, bdist, bdtype, y, ydtype, bdist_out, y_out,
             plan_dev, H, W, scale, lo, hi);
   return cn_check_launch();
+}
+
+// The nine ops that need no parcel labelling: a `roll` row is CN_ERR_ARG here, as every unknown op.
+extern "C" int cn_augment_chips_f32(const void* x, int xdtype, const void* bdist, int bdtype, const void* y, int ydtype,
+                                    float* x_out, float* bdist_out, long long* y_out, const int* plan_host,
+                                    const int* plan_dev, const float* perlin_dev, const float* mean, const float* stdv,
+                                    int B, int C, int T, int H, int W, float scale, float lo, float hi, void* stream_) {
+  return cn_augment_parcels_f32(x, xdtype, bdist, bdtype, y, ydtype, x_out, bdist_out, y_out, plan_host, plan_dev, perlin_dev,
+                                nullptr, nullptr, nullptr, mean, stdv, B, C, T, H, W, scale, lo, hi, stream_);
 }

@@ -360,6 +360,28 @@ int cn_augment_chips_f32(const void* x, int xdtype, const void* bdist, int bdtyp
                          float* bdist_out, long long* y_out, const int* plan_host, const int* plan_dev,
                          const float* perlin_dev, const float* mean, const float* stdv, int B, int C, int T, int H, int W,
                          float scale, float lo, float hi, void* stream);
+/* Parcel labelling: the first step of the five parcel augmenters of EdgeDataset.get, batch.segments =
+ * np.uint8(nd_label(batch.y == 1)[0]) followed by regionprops (data/datasets.py:453-466). y [B][H][W] (ydtype 1 i32,
+ * 2 i16, 3 u16, 4 i64); foreground is y == crop_value (the reference hard-codes 1, see its FIXME at datasets.py:460);
+ * 4-neighbour connectivity, scipy.ndimage.label's default structure. labels [B][H][W] int32: 0 on background, parcels
+ * 1..n in raster order of their first pixel, which is scipy's numbering; counts [B] = n. The labels are NOT wrapped to
+ * uint8 here: the consumer does that. Deterministic; one launch (one workgroup per sample), no allocation, no
+ * synchronisation. CN_ERR_ARG: null pointer, unknown ydtype, non-positive dimension, H * W >= 2^31. */
+int cn_label_parcels_i32(const void* y, int ydtype, long long crop_value, int* labels, int* counts, int B, int H, int W,
+                         void* stream);
+/* cn_augment_chips_f32 plus op 10 = roll (Roll.forward, augment/augmenters.py:154-163; roll_time and insert_parcel,
+ * augment/augmenter_utils.py:57-108,168-193): every parcel is rolled along T by its own shift,
+ *   x_out[b][c][t][h][w] = zscore(clip(v(x[b][c][(t - s) mod T][h][w]))),  s = parcel[b][labels[b][h][w] & 255],
+ * a true modulus, as torch.roll(xseg, s, dims=2); bdist and y of a roll sample pass as under `none`. labels_dev: [B][H][W]
+ * from cn_label_parcels_i32; parcel_host and parcel_dev: the same [B][256] int32 table in host memory (validated before
+ * any launch) and in device memory. `& 255` with entry 0 fixed at 0 is the reference's np.uint8 wrap: parcel 256 stays
+ * put, parcel 257 moves with parcel 1. With the three pointers null this is cn_augment_chips_f32. Two launches.
+ * CN_ERR_ARG, besides those of cn_augment_chips_f32, for a roll row: labels or tables null, |s| >= T, entry 0 not 0. */
+int cn_augment_parcels_f32(const void* x, int xdtype, const void* bdist, int bdtype, const void* y, int ydtype, float* x_out,
+                           float* bdist_out, long long* y_out, const int* plan_host, const int* plan_dev,
+                           const float* perlin_dev, const int* labels_dev, const int* parcel_host, const int* parcel_dev,
+                           const float* mean, const float* stdv, int B, int C, int T, int H, int W, float scale, float lo,
+                           float hi, void* stream);
 /* sliding-window predict (BASELINE configs[4]; data/create.py:176-212, data/store.py:69-100, callbacks.py:176-227):
  * window_chips: window n = crop [r0-pad, r0-pad+S) x [c0-pad, c0-pad+S) of the zero-extended scene [C*T][H][W]
  *   (stored dtype as prepare), scaled / clipped / z-scored into fp32 [nwin][C*T][S][S]; win_rc: DEVICE int [nwin][2].
