@@ -3067,52 +3067,14 @@ def _conv_transpose2d_bf16(x: Var, mod, stride: int, padding: int) -> Var:
 
 def _bn_act_bf16(x: Var, bn, act: int, residual: T.Optional[Var], training: bool,
                  out: T.Optional[torch.Tensor]) -> Var:
-    if _dense16(x.t) and (out is None or _dense16(out)):
-        # G = 1 of the grouped entry point: same arithmetic, the finalize is ONE coalesced, ticketed launch
-        return _bn_act_group_bf16([x], [bn], act, residual, True, training, [out] if out is not None else None)
-    tape = current_tape()
-    xt = x.t
-    B, C, H, W = xt.shape
-    P = B * H * W
-    dev = xt.device
-    y = _check(out) if out is not None else _new(xt.shape, xt)
-    mean = _alloc(C, torch.float32, dev)
-    rstd = _alloc(C, torch.float32, dev)
-    rt = _check(residual.t) if residual is not None else None
-    use_batch = training or (bn.running_mean is None)
-    _note_bn_update(training)
-    sums = x.stats if use_batch else None
-    _lib.call("cn_bn_act_fwd_bf16", xt.data_ptr(), ld(xt), bn.weight.data_ptr(), bn.bias.data_ptr(),
-              bn.running_mean.data_ptr() if bn.running_mean is not None else None,
-              bn.running_var.data_ptr() if bn.running_var is not None else None,
-              rt.data_ptr() if rt is not None else None, ld(rt) if rt is not None else 0, y.data_ptr(), ld(y),
-              mean.data_ptr(), rstd.data_ptr(), _bn_ws16(C, dev), P, C, 1 if use_batch else 0, _bn_momentum(bn),
-              float(bn.eps), act, sums.data_ptr() if sums is not None else None,
-              sums.shape[0] if sums is not None else 0, _stream())
-    gamma, beta = bn.weight, bn.bias
-    # frozen gamma / beta with a live input: the fused kernel still writes their slices (never read)
-    yv = Var(y, _req(tape, (x, residual), (gamma, beta)))
-    if yv.req:
-        store = current_store()
-
-        def bwd():
-            dy = yv.grad
-            if dy is None:
-                return
-            if residual is not None:
-                give_grad(residual, dy)
-            if x.req:
-                dx, acc = grad_buffer(x)
-                dxp, dxl = dx.data_ptr(), ld(dx)
-            else:
-                dxp, dxl, acc = None, 0, 0
-            _lib.call("cn_bn_act_bwd_bf16", xt.data_ptr(), ld(xt), dy.data_ptr(), ld(dy), mean.data_ptr(),
-                      rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), dxp, dxl, store.grad_of(gamma).data_ptr(),
-                      store.grad_of(beta).data_ptr(), _bn_ws16(C, dev), P, C, 1 if use_batch else 0, act, acc, _stream())
-            yv.grad = None
-
-        tape.add(bwd, (gamma, beta))
-    return yv
+    # every bf16 BatchNorm kernel walks P = B*H*W pixel rows at one stride: a view with gaps between rows or images (a
+    # spatial crop of a larger buffer) has no kernel, and launching one on it would read / write the wrong pixels
+    for what, t in (("input", x.t), ("output", out)):
+        if t is not None and not _dense16(t):
+            raise NotImplementedError(f"bn_act (bf16): the {what} must be one run of NHWC pixel rows (one pixel stride "
+                                      "over the whole batch); a view with gaps between rows or images has no kernel")
+    # G = 1 of the grouped entry point: same arithmetic, the finalize is ONE coalesced, ticketed launch
+    return _bn_act_group_bf16([x], [bn], act, residual, True, training, [out] if out is not None else None)
 
 
 _bng_ws: T.Dict[T.Tuple, torch.Tensor] = {}
