@@ -85,6 +85,7 @@ SIGNATURES = {
     "cn_augment_chips_f32": [P, I, P, I, P, I, P, P, P, P, P, P, P, P, I, I, I, I, I, F, F, F, P],
     "cn_label_parcels_i32": [P, I, L, P, P, I, I, I, P],  # crop_value: long long, as wide as long here
     "cn_augment_parcels_f32": [P, I, P, I, P, I, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, F, F, P],
+    "cn_augment_series_f32": [P, I, P, I, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, P, P, I, I, I, I, I, F, F, F, P],
     # ---- bf16 NHWC mixed-precision path ----
     "cn_bconv_packed_elems": [I, I, I],
     "cn_pack_weights_bf16": [P, P, I, I, I, L, L, L, P],

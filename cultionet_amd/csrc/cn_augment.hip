@@ -8,6 +8,9 @@
 // A tenth op, `roll` (augment/augmenters.py:154-163, augment/augmenter_utils.py:57-108,168-193), shifts each labelled
 // parcel along T by its own amount: it reads the parcel labels of cn_label_parcels_i32 (cn_parcels.hip) and a table of
 // CN_AUG_PARCELS shifts per sample, and is reached through cn_augment_parcels_f32 only.
+// The four time-series ops (tswarp, tsnoise, tsdrift, tspeaks; augment_time, augment/augmenter_utils.py:111-165) work on
+// whole pixel series and have a kernel of their own, cn_augment_series_kernel, reached through cn_augment_series_f32 only:
+// the plane kernel leaves a series sample alone, the target kernel treats it as `none`.
 //
 // Plan table: CN_AUG_PLAN_WORDS int32 words per sample
 //   [0] op   [1] div   [2] top   [3] left   [4] r   [5] sigma (float bits)   [6] noise seed, low word   [7] high word
@@ -34,7 +37,13 @@
 #define CN_AUG_CROPRESIZE 8
 #define CN_AUG_PERLIN 9
 #define CN_AUG_ROLL 10
-#define CN_AUG_NOPS 11
+#define CN_AUG_NOPS 11                      // ops of the plane kernel
+#define CN_AUG_TSWARP 11                    // the series ops: cn_augment_series_kernel, cn_augment_series_f32 only
+#define CN_AUG_TSNOISE 12
+#define CN_AUG_TSDRIFT 13
+#define CN_AUG_TSPEAKS 14
+#define CN_AUG_TMAX 64                      // longest series the series kernel holds
+#define CN_AUG_SERIES_NT 256                // pixels per block of the series kernel, halved while two columns do not fit LDS
 
 #define CN_AUG_PLAN_WORDS 8
 #define CN_AUG_RMAX 10
@@ -201,6 +210,7 @@ __global__ __launch_bounds__(256) void cn_augment_x_kernel(const TIn* __restrict
   const int c = plane / T, t = plane - c * T;
   const int r0 = blockIdx.x * CN_AUG_BR, r1 = min(r0 + CN_AUG_BR, H);
   const int* row = plan + (long)b * CN_AUG_PLAN_WORDS;
+  if (row[0] >= CN_AUG_TSWARP && row[0] <= CN_AUG_TSPEAKS) return;  // cn_augment_series_kernel writes this sample
   CnAugCrop crop;
   const int op = cn_aug_checked_op(row, H, W, perlin != nullptr, labels != nullptr && parcel != nullptr, crop);
   const long HW = (long)H * W;
@@ -338,6 +348,101 @@ __global__ __launch_bounds__(256) void cn_augment_target_kernel(const void* __re
   }
 }
 
+// The four time-series ops of the parcel augmenters (augment_time, augment/augmenter_utils.py:111-165, with tsaug's
+// TimeWarp / Drift / AddNoise): tswarp, tsnoise, tsdrift, tspeaks. The random CURVES are drawn on the host, one set per
+// parcel slot k = label & 255 (the reference's uint8 segments, as in `roll`), and arrive as a packed table per series
+// sample (`row` of them, `rows[row]` = the sample):
+//   pos [256][T] source times in [0, T-1]   drift [256][C][T]   nscale [256]      slot 0 holds the identity
+// A thread owns one pixel of one channel and keeps its whole series in a column of LDS (element t at [t * tile + tid]:
+// consecutive lanes, consecutive banks), a second column holds the result while its range is taken. With v the
+// prologue's load:
+//   u = tspeaks && k != 0 ? concat(resize(v, T / 2), resize(v, T - T / 2)) : v (F.interpolate, linear, align_corners=False)
+//   w[t] = warp ? u[j] + (p - j) (u[j1] - u[j]),  p = pos[k][t], j = min(floor p, T-1), j1 = min(j + 1, T-1)  :  u[t]
+//   d[t] = w[t] + drift[k][c][t] (max w - min w)                                (tsdrift only)
+//   e[t] = d[t] + n nscale[k] (max d - min d)                                   (where nscale[k] > 0; n as in saltpepper)
+//   out[t] = store(clip(e[t], 0, 1))
+// With identity tables every step returns its input bit for bit (p - j = 0, drift = 0), so such a pixel equals
+// cn_prepare_chips_f32. A thread touches its own columns only: there is no barrier. grid (pixel tiles, C, series rows).
+template <typename TIn>
+__global__ __launch_bounds__(CN_AUG_SERIES_NT) void cn_augment_series_kernel(
+    const TIn* __restrict__ x, float* __restrict__ out, const int* __restrict__ plan, const int* __restrict__ labels,
+    const float* __restrict__ tables, const int* __restrict__ rows, const float* __restrict__ mean,
+    const float* __restrict__ stdv, int B, int T, int H, int W, float scale, float lo, float hi) {
+  extern __shared__ float smem[];
+  const int tile = blockDim.x, tid = threadIdx.x, C = gridDim.y, c = blockIdx.y;
+  const int b = rows[blockIdx.z];
+  const long HW = (long)H * W, pix = (long)blockIdx.x * tile + tid;
+  if (b < 0 || b >= B || pix >= HW) return;
+  const int* row = plan + (long)b * CN_AUG_PLAN_WORDS;
+  const int op = row[0];
+  const CnAugLoad<TIn> ld{x, scale, lo, hi};
+  const CnAugStore st{out, lo, hi, mean ? mean[c] : 0.f, stdv ? 1.0f / stdv[c] : 1.f};
+  const long base = ((long)b * C + c) * T * HW + pix;
+  float* v = smem + tid;
+  float* e = smem + T * tile + tid;
+#pragma unroll 4
+  for (int t = 0; t < T; ++t) v[t * tile] = ld(base + (long)t * HW);  // several loads in flight
+
+  const int k = labels[(long)b * HW + pix] & (CN_AUG_PARCELS - 1);
+  const bool peaks = op == CN_AUG_TSPEAKS && k != 0;  // slot 0 is no prop: augment_time never sees those pixels
+  const bool warp = op == CN_AUG_TSWARP || op == CN_AUG_TSPEAKS;
+  const float* tab = tables + (long)blockIdx.z * CN_AUG_PARCELS * (T + C * T + 1);
+  const float* pos = tab + k * T;
+  const float* drift = tab + CN_AUG_PARCELS * T + (k * C + c) * T;
+  const float nscale = tab[CN_AUG_PARCELS * T * (1 + C) + k];
+
+  // u[i]: the series itself, or for tspeaks its two halves, each the whole series resized
+  const int Ta = T / 2;
+  const float sa = (float)T / (float)Ta, sb = (float)T / (float)(T - Ta);
+  auto u_at = [&](int i) -> float {
+    if (!peaks) return v[i * tile];
+    const int ii = i < Ta ? i : i - Ta;
+    const float s = fmaxf(((float)ii + 0.5f) * (i < Ta ? sa : sb) - 0.5f, 0.f);
+    const int i0 = min((int)s, T - 1), i1 = min(i0 + 1, T - 1);
+    const float l = s - (float)i0;
+    return (1.f - l) * v[i0 * tile] + l * v[i1 * tile];
+  };
+  float mn = INFINITY, mx = -INFINITY;
+  for (int t = 0; t < T; ++t) {
+    float w;
+    if (warp) {
+      // the host has refused a source time outside [0, T-1]; it is clamped all the same, so that no column is left
+      const float p = fminf(fmaxf(pos[t], 0.f), (float)(T - 1));
+      const int j = min((int)p, T - 1), j1 = min(j + 1, T - 1);
+      const float a = u_at(j);
+      w = a + (p - (float)j) * (u_at(j1) - a);
+    } else {
+      w = v[t * tile];
+    }
+    e[t * tile] = w;
+    mn = fminf(mn, w);
+    mx = fmaxf(mx, w);
+  }
+  if (op == CN_AUG_TSDRIFT) {
+    const float r = mx - mn;
+    mn = INFINITY;
+    mx = -INFINITY;
+    for (int t = 0; t < T; ++t) {
+      const float d = e[t * tile] + drift[t] * r;
+      e[t * tile] = d;
+      mn = fminf(mn, d);
+      mx = fmaxf(mx, d);
+    }
+  }
+  if (nscale > 0.f) {  // the counter and the Box-Muller step of saltpepper
+    const unsigned long long seed = ((unsigned long long)(unsigned)row[7] << 32) | (unsigned)row[6];
+    const float amp = nscale * (mx - mn);
+    for (int t = 0; t < T; ++t) {
+      const unsigned long long i = (unsigned long long)(((long)c * T + t) * HW + pix);
+      const float u1 = (float)((cn_splitmix64(seed + 2ull * i) >> 40) + 1ull) * 0x1p-24f;
+      const float u2 = (float)(cn_splitmix64(seed + 2ull * i + 1ull) >> 40) * 0x1p-24f;
+      const float nrm = sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
+      e[t * tile] += nrm * amp;
+    }
+  }
+  for (int t = 0; t < T; ++t) st(base + (long)t * HW, fminf(fmaxf(e[t * tile], 0.f), 1.f));
+}
+
 // x: [B][C][T][H][W] raw (xdtype: 0 f32, 1 i32, 2 i16, 3 u16) -> x_out fp32, z-scored (mean / stdv nullable);
 // bdist: [B][H][W] raw (bdtype as xdtype; nullable together with bdist_out) -> bdist_out fp32 in [0, hi];
 // y: [B][H][W] labels (ydtype: 1 i32, 2 i16, 3 u16, 4 i64) -> y_out int64.
@@ -345,22 +450,56 @@ __global__ __launch_bounds__(256) void cn_augment_target_kernel(const void* __re
 // launched) and in device memory (read by the kernels); perlin_dev: [B][CN_AUG_PERLIN_FLOATS], nullable when no sample
 // is `perlin`. labels_dev: [B][H][W] parcel labels (cn_label_parcels_i32); parcel_host / parcel_dev: the SAME
 // [B][CN_AUG_PARCELS] table of shifts in host and in device memory; all three nullable when no sample is `roll`.
-// Two launches, no allocation, no synchronisation.
-extern "C" int cn_augment_parcels_f32(const void* x, int xdtype, const void* bdist, int bdtype, const void* y, int ydtype,
-                                      float* x_out, float* bdist_out, long long* y_out, const int* plan_host,
-                                      const int* plan_dev, const float* perlin_dev, const int* labels_dev,
-                                      const int* parcel_host, const int* parcel_dev, const float* mean, const float* stdv,
-                                      int B, int C, int T, int H, int W, float scale, float lo, float hi, void* stream_) {
+// series_host / series_dev: the SAME [nrows][256 * (T + C * T + 1)] packed tables of the series samples (pos, drift,
+// nscale; see cn_augment_series_kernel) in host and in device memory; rows_host / rows_dev: the SAME [nrows] sample
+// indices, increasing, one per series sample; all nullable with nrows = 0, and a series op is then an unknown op.
+// Two launches, three with a series sample; no allocation, no synchronisation.
+static int cn_augment_run(const void* x, int xdtype, const void* bdist, int bdtype, const void* y, int ydtype,
+                          float* x_out, float* bdist_out, long long* y_out, const int* plan_host, const int* plan_dev,
+                          const float* perlin_dev, const int* labels_dev, const int* parcel_host, const int* parcel_dev,
+                          const float* series_host, const float* series_dev, const int* rows_host, const int* rows_dev,
+                          int nrows, const float* mean, const float* stdv, int B, int C, int T, int H, int W,
+                          float scale, float lo, float hi, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (B <= 0 || C <= 0 || T <= 0 || H <= 0 || W <= 0) return CN_OK;
   if (x == nullptr || x_out == nullptr || y == nullptr || y_out == nullptr || plan_host == nullptr || plan_dev == nullptr) return CN_ERR_ARG;
   if ((bdist == nullptr) != (bdist_out == nullptr)) return CN_ERR_ARG;
   if (xdtype < 0 || xdtype > 3 || (bdist != nullptr && (bdtype < 0 || bdtype > 3)) || ydtype < 1 || ydtype > 4) return CN_ERR_ARG;
   if ((long)C * T > 65535 || B > 65535) return CN_ERR_ARG;
+  if (nrows < 0 || nrows > B) return CN_ERR_ARG;
+  if (nrows > 0) {
+    if (series_host == nullptr || series_dev == nullptr || rows_host == nullptr || rows_dev == nullptr || labels_dev == nullptr) return CN_ERR_ARG;
+    if (T < 2 || T > CN_AUG_TMAX) return CN_ERR_ARG;
+    const long per_row = (long)CN_AUG_PARCELS * ((long)T + (long)C * T + 1);
+    for (int r = 0; r < nrows; ++r) {
+      const int b = rows_host[r];
+      if (b < 0 || b >= B || (r > 0 && b <= rows_host[r - 1])) return CN_ERR_ARG;
+      const int op = plan_host[(long)b * CN_AUG_PLAN_WORDS];
+      if (op < CN_AUG_TSWARP || op > CN_AUG_TSPEAKS) return CN_ERR_ARG;
+      const float* pos = series_host + r * per_row;
+      const float* drift = pos + CN_AUG_PARCELS * T;
+      const float* nscale = drift + (long)CN_AUG_PARCELS * C * T;
+      for (long i = 0; i < (long)CN_AUG_PARCELS * T; ++i)
+        if (!(pos[i] >= 0.f && pos[i] <= (float)(T - 1))) return CN_ERR_ARG;  // refuses NaN too
+      for (long i = 0; i < (long)CN_AUG_PARCELS * C * T; ++i)
+        if (!(fabsf(drift[i]) <= 3.4028234663852886e38f)) return CN_ERR_ARG;
+      for (int k = 0; k < CN_AUG_PARCELS; ++k)
+        if (!(nscale[k] >= 0.f && nscale[k] <= 3.4028234663852886e38f)) return CN_ERR_ARG;
+      for (int t = 0; t < T; ++t)  // slot 0: background, and parcels 256, 512, ...
+        if (pos[t] != (float)t) return CN_ERR_ARG;
+      for (int i = 0; i < C * T; ++i)
+        if (drift[i] != 0.f) return CN_ERR_ARG;
+      if (nscale[0] != 0.f) return CN_ERR_ARG;
+    }
+  }
   bool blur = false;
+  int nseries = 0;
   for (int b = 0; b < B; ++b) {
     const int* row = plan_host + (long)b * CN_AUG_PLAN_WORDS;
     switch (row[0]) {
+      case CN_AUG_TSWARP: case CN_AUG_TSNOISE: case CN_AUG_TSDRIFT: case CN_AUG_TSPEAKS:
+        ++nseries;  // every one of them must own a row of the tables: the rows are distinct series samples, so count
+        break;
       case CN_AUG_NONE: case CN_AUG_ROT180: case CN_AUG_FLIPLR: case CN_AUG_FLIPUD: case CN_AUG_SALTPEPPER: break;
       case CN_AUG_ROT90: case CN_AUG_ROT270:
         if (H != W) return CN_ERR_ARG;
@@ -395,6 +534,7 @@ extern "C" int cn_augment_parcels_f32(const void* x, int xdtype, const void* bdi
       default: return CN_ERR_ARG;
     }
   }
+  if (nseries != nrows) return CN_ERR_ARG;
   size_t lds = CN_AUG_TILE * sizeof(float);  // covers the perlin gradients (2 * 11 * 11 * 3 floats) and the parcel shifts too
   if (blur) {
     const size_t band = (size_t)(CN_AUG_BR + 2) * (W + 2) * sizeof(float);
@@ -411,9 +551,49 @@ extern "C" int cn_augment_parcels_f32(const void* x, int xdtype, const void* bdi
   }
   int rc = cn_check_launch();
   if (rc != CN_OK) return rc;
+  if (nrows > 0) {
+    // two columns of T floats per pixel: 256 pixels up to T = 32, 128 beyond
+    const int nt = 2 * T * CN_AUG_SERIES_NT * (int)sizeof(float) <= CN_AUG_MAX_LDS ? CN_AUG_SERIES_NT : CN_AUG_SERIES_NT / 2;
+    const size_t slds = (size_t)2 * T * nt * sizeof(float);
+    const dim3 sgrid(cn_cdiv((long)H * W, nt), C, nrows), sblock(nt);
+    switch (xdtype) {
+      case 0: CN_LAUNCH(cn_augment_series_kernel<float>, sgrid, sblock, slds, stream, (const float*)x, x_out, plan_dev, labels_dev, series_dev, rows_dev, mean, stdv, B, T, H, W, scale, lo, hi); break;
+      case 1: CN_LAUNCH(cn_augment_series_kernel<int>, sgrid, sblock, slds, stream, (const int*)x, x_out, plan_dev, labels_dev, series_dev, rows_dev, mean, stdv, B, T, H, W, scale, lo, hi); break;
+      case 2: CN_LAUNCH(cn_augment_series_kernel<short>, sgrid, sblock, slds, stream, (const short*)x, x_out, plan_dev, labels_dev, series_dev, rows_dev, mean, stdv, B, T, H, W, scale, lo, hi); break;
+      default: CN_LAUNCH(cn_augment_series_kernel<unsigned short>, sgrid, sblock, slds, stream, (const unsigned short*)x, x_out, plan_dev, labels_dev, series_dev, rows_dev, mean, stdv, B, T, H, W, scale, lo, hi); break;
+    }
+    rc = cn_check_launch();
+    if (rc != CN_OK) return rc;
+  }
   CN_LAUNCH(cn_augment_target_kernel, dim3(bands, 2, B), block, 0, stream, bdist, bdtype, y, ydtype, bdist_out, y_out,
             plan_dev, H, W, scale, lo, hi);
   return cn_check_launch();
+}
+
+// The ten ops of the plane kernel: a series row is CN_ERR_ARG here, as every unknown op.
+extern "C" int cn_augment_parcels_f32(const void* x, int xdtype, const void* bdist, int bdtype, const void* y, int ydtype,
+                                      float* x_out, float* bdist_out, long long* y_out, const int* plan_host,
+                                      const int* plan_dev, const float* perlin_dev, const int* labels_dev,
+                                      const int* parcel_host, const int* parcel_dev, const float* mean, const float* stdv,
+                                      int B, int C, int T, int H, int W, float scale, float lo, float hi, void* stream_) {
+  return cn_augment_run(x, xdtype, bdist, bdtype, y, ydtype, x_out, bdist_out, y_out, plan_host, plan_dev, perlin_dev,
+                        labels_dev, parcel_host, parcel_dev, nullptr, nullptr, nullptr, nullptr, 0, mean, stdv, B, C, T, H, W,
+                        scale, lo, hi, stream_);
+}
+
+// cn_augment_parcels_f32 plus the four series ops (11 tswarp, 12 tsnoise, 13 tsdrift, 14 tspeaks). CN_ERR_ARG with
+// nothing launched: T outside [2, 64]; a source time that is not in [0, T-1]; a drift or noise scale that is not finite,
+// a negative noise scale; slot 0 not the identity; a series row without labels or without its row of the tables.
+extern "C" int cn_augment_series_f32(const void* x, int xdtype, const void* bdist, int bdtype, const void* y, int ydtype,
+                                     float* x_out, float* bdist_out, long long* y_out, const int* plan_host,
+                                     const int* plan_dev, const float* perlin_dev, const int* labels_dev,
+                                     const int* parcel_host, const int* parcel_dev, const float* series_host,
+                                     const float* series_dev, const int* rows_host, const int* rows_dev, int nrows,
+                                     const float* mean, const float* stdv, int B, int C, int T, int H, int W, float scale,
+                                     float lo, float hi, void* stream_) {
+  return cn_augment_run(x, xdtype, bdist, bdtype, y, ydtype, x_out, bdist_out, y_out, plan_host, plan_dev, perlin_dev,
+                        labels_dev, parcel_host, parcel_dev, series_host, series_dev, rows_host, rows_dev, nrows, mean, stdv,
+                        B, C, T, H, W, scale, lo, hi, stream_);
 }
 
 // The nine ops that need no parcel labelling: a `roll` row is CN_ERR_ARG here, as every unknown op.

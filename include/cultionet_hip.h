@@ -382,6 +382,28 @@ int cn_augment_parcels_f32(const void* x, int xdtype, const void* bdist, int bdt
                            const float* perlin_dev, const int* labels_dev, const int* parcel_host, const int* parcel_dev,
                            const float* mean, const float* stdv, int B, int C, int T, int H, int W, float scale, float lo,
                            float hi, void* stream);
+/* cn_augment_parcels_f32 plus ops 11 tswarp, 12 tsnoise, 13 tsdrift, 14 tspeaks (AugmentTimeWarp / AugmentAddTimeNoise /
+ * AugmentTimeDrift, augment/augmenters.py:51-151; augment_time and insert_parcel, augment/augmenter_utils.py:88-165): every
+ * pixel's series of every channel is resampled at the source times of its parcel slot k = labels & 255, drifted and given
+ * noise, all in fp32, with v[t] the prologue's load:
+ *   u = tspeaks and k != 0 ? concat(resize(v, T / 2), resize(v, T - T / 2)) : v     (linear, align_corners = False)
+ *   w[t] = u[j] + (p - j)(u[j1] - u[j]), p = pos[k][t], j = min(floor p, T-1), j1 = min(j+1, T-1)   (tswarp, tspeaks)
+ *   d[t] = w[t] + drift[k][c][t] (max w - min w)                                                    (tsdrift)
+ *   e[t] = d[t] + n nscale[k] (max d - min d), n the normal of saltpepper at the element's index    (where nscale[k] > 0)
+ *   x_out = zscore(clip(clip(e, 0, 1), lo, hi));   bdist and y pass as under `none`.
+ * series_host and series_dev: the same packed tables in host memory (validated before any launch) and in device memory,
+ * one row per series sample: pos [256][T], drift [256][C][T], nscale [256] floats; rows_host and rows_dev: the same [nrows]
+ * sample indices, increasing, row r belongs to sample rows[r]. Slot 0 is the identity (pos = 0..T-1, drift 0, nscale 0):
+ * background pixels and parcels 256, 512, ... come out as cn_prepare_chips_f32 writes them. With nrows = 0 this is
+ * cn_augment_parcels_f32. Three launches with a series sample. CN_ERR_ARG, besides those of cn_augment_parcels_f32:
+ * T outside [2, 64], a pos outside [0, T-1] or not finite, a drift not finite, an nscale negative or not finite, slot 0 not
+ * the identity, a series sample without labels or without a row, a row whose sample is not a series sample. */
+int cn_augment_series_f32(const void* x, int xdtype, const void* bdist, int bdtype, const void* y, int ydtype, float* x_out,
+                          float* bdist_out, long long* y_out, const int* plan_host, const int* plan_dev,
+                          const float* perlin_dev, const int* labels_dev, const int* parcel_host, const int* parcel_dev,
+                          const float* series_host, const float* series_dev, const int* rows_host, const int* rows_dev,
+                          int nrows, const float* mean, const float* stdv, int B, int C, int T, int H, int W, float scale,
+                          float lo, float hi, void* stream);
 /* sliding-window predict (BASELINE configs[4]; data/create.py:176-212, data/store.py:69-100, callbacks.py:176-227):
  * window_chips: window n = crop [r0-pad, r0-pad+S) x [c0-pad, c0-pad+S) of the zero-extended scene [C*T][H][W]
  *   (stored dtype as prepare), scaled / clipped / z-scored into fp32 [nwin][C*T][S][S]; win_rc: DEVICE int [nwin][2].

@@ -3,12 +3,17 @@
 [32, 3, 12, 100, 100], bdist int16, y int64).
 
     python tools/parcel_time.py [--out FILE] [--iters 200] [--repeats 7] [--batches 8 32] [--labels random blocks]
-                                 [--variants fliplr roll label]
+                                 [--variants fliplr roll label tswarp tsdrift tspeaks tsnoise]
 
 Variants, alternated inside every repeat so that they see the same machine state:
   fliplr       DeviceAugmenter.apply with every sample `fliplr` (two launches; the figure the parent commit has too)
   roll         apply with every sample `roll` (three launches: label, x, targets)
   label        label_parcels alone (one launch and its two output allocations)
+  tswarp, tsdrift, tspeaks, tsnoise
+               apply with every sample that series op, its curves drawn once beforehand as DeviceAugmenter.draw draws them
+               (four launches: label, x planes, x series, targets; the call packs and copies the tables of all B samples)
+  draw_tswarp, draw_tsdrift
+               DeviceAugmenter.draw alone for a batch of that op: host time only, nothing runs on the device
 for two kinds of label plane: `random` (each pixel crop with probability 0.5: many small parcels) and `blocks` (rectangular
 fields 8 to 24 pixels on a side between one-pixel edges: few large parcels, as training chips have them).
 Each figure is the time between two HIP events around `iters` back-to-back calls on one stream, divided by `iters`,
@@ -47,7 +52,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[8, 32])
     ap.add_argument("--labels", nargs="+", default=["random", "blocks"], choices=["random", "blocks"])
-    ap.add_argument("--variants", nargs="+", default=["fliplr", "roll", "label"], choices=["fliplr", "roll", "label"])
+    series = ["tswarp", "tsdrift", "tspeaks", "tsnoise"]
+    ap.add_argument("--variants", nargs="+", default=["fliplr", "roll", "label", "tswarp", "tsdrift", "tspeaks"],
+                    choices=["fliplr", "roll", "label", "draw_tswarp", "draw_tsdrift"] + series)
     ap.add_argument("--chip", type=int, nargs=4, default=[3, 12, 100, 100], help="C T H W")
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=7)
@@ -76,6 +83,8 @@ def main():
             shifts = np.zeros(256, dtype=np.int32)
             shifts[1:] = rng.integers(-q, q + 1, 255)
             roll.set(b, "roll", shifts=shifts)
+        drawers = {v: DeviceAugmenter(augment_prob=1.0, augmentations=(), series_augmentations=(v,), seed=2) for v in series}
+        plans = {v: drawers[v].draw(B, T, H, W, C) for v in series if v in args.variants}
         for kind in args.labels:
             y = blocks(B, H, W, rng) if kind == "blocks" else (rng.random((B, H, W)) < 0.5).astype(np.int64)
             yd = torch.from_numpy(y).cuda()
@@ -84,6 +93,8 @@ def main():
             fns = {"fliplr": lambda batch=batch, m=mean, s=std, p=flip: aug.apply(batch, m, s, plan=p),
                    "roll": lambda batch=batch, m=mean, s=std, p=roll: aug.apply(batch, m, s, plan=p),
                    "label": lambda yd=yd: label_parcels(yd)}
+            fns.update({v: lambda batch=batch, m=mean, s=std, p=p: aug.apply(batch, m, s, plan=p) for v, p in plans.items()})
+            fns.update({f"draw_{v}": lambda d=drawers[v], B=B: d.draw(B, T, H, W, C) for v in ("tswarp", "tsdrift")})
             variants.update({f"{v}/{kind}/{B}": fns[v] for v in args.variants})
 
     def window(fn):
