@@ -86,6 +86,9 @@ SIGNATURES = {
     "cn_label_parcels_i32": [P, I, L, P, P, I, I, I, P],  # crop_value: long long, as wide as long here
     "cn_augment_parcels_f32": [P, I, P, I, P, I, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, F, F, P],
     "cn_augment_series_f32": [P, I, P, I, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, P, P, I, I, I, I, I, F, F, F, P],
+    "cn_chip_hist_u32": [P, I, P, I, I, L, I, P],
+    "cn_hist_batch_reduce": [P, P, P, P, I, I, I, I, P],
+    "cn_label_counts_i64": [P, I, L, P, I, P],
     # ---- bf16 NHWC mixed-precision path ----
     "cn_bconv_packed_elems": [I, I, I],
     "cn_pack_weights_bf16": [P, P, I, I, I, L, L, L, P],

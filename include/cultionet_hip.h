@@ -415,6 +415,27 @@ int cn_stitch_predictions_u16(const float* dist, const float* edge, const float*
                               const int* win_rc, int nwin, int S, int pad, int ws, int H, int W, float scale,
                               void* stream);
 
+/* ---- dataset normalization statistics -----------------------------------------------------------------------------
+ * NormValues.from_dataset (utils/normalize.py:118-213) over integers: stored reflectances pass through
+ * (x / 10000).clip(1e-9, 1) (data/datasets.py:443), so a per-channel histogram over bin = clamp(v, 0, nbins - 1) holds
+ * all that Variance(method='median') (utils/stats.py:642-683) and Quantile (utils/stats.py:309-352, 519-575) are fed.
+ * Every output is an integer and independent of arrival order; the caller owns and zero-fills every buffer once; no
+ * allocation, no synchronisation, one launch each.
+ * chip_hist: the rearrange + stat.add of normalize.py:173-177. x [B][C][L] (dtype 1 i32, 2 i16, 3 u16 as
+ *   cn_prepare_chips_f32; 0 f32 is CN_ERR_ARG) -> hist [C][nbins] uint32, ADDED into. CN_ERR_ARG: nbins outside
+ *   [2, 16384], B * L >= 2^32, x not aligned to its element.
+ * batch_reduce: what Variance.add takes from one batch (stats.py:646-658). records[batch_index][c] = 7 int64 words
+ *   {n, count of bin 0, median bin, S1 low, S1 high, S2 low, S2 high}: the median bin holds the element of sorted rank
+ *   (n - 1) / 2 (a.median(dim=0)[0], torch's lower median; -1 when n = 0); S1 = sum h_k w_k and S2 = sum h_k w_k^2 are
+ *   128-bit sums over the caller's weights [nbins], 0 <= w_k < 2^40. Then dataset_hist [C][nbins] uint64 += batch_hist
+ *   and batch_hist = 0. CN_ERR_ARG: batch_index outside [0, capacity), nbins outside [2, 16384].
+ * label_counts: the tallies of normalize.py:180-191. y [N] (ydtype as cn_label_parcels_i32) -> counts [nlab + 2] int64,
+ *   ADDED into: [0] v < 0, [1 + v] 0 <= v < nlab, [nlab + 1] v >= nlab. CN_ERR_ARG: nlab outside [1, 1022]. */
+int cn_chip_hist_u32(const void* x, int dtype, unsigned int* hist, int B, int C, long L, int nbins, void* stream);
+int cn_hist_batch_reduce(unsigned int* batch_hist, unsigned long long* dataset_hist, const long long* weights,
+                         long long* records, int batch_index, int capacity, int C, int nbins, void* stream);
+int cn_label_counts_i64(const void* y, int ydtype, long N, long long* counts, int nlab, void* stream);
+
 
 /* ================================================================================================================
  * bf16 mixed-precision path (BASELINE configs[2]; the reference's default precision="16-mixed", model.py:168-186).
