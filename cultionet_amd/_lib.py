@@ -78,6 +78,8 @@ SIGNATURES = {
     "cn_adamw_step_seg_f32": [P, P, P, P, L, P, I, I, I, F, F, F, F, F, F, P, F, P],
     "cn_optim_step_f32": [I, I, P, P, P, P, L, F, F, F, F, F, I, F, P, F, P],
     "cn_optim_step_seg_f32": [I, I, P, P, P, P, L, P, I, I, I, F, F, F, F, F, F, P, F, P],
+    "cn_optim_step_amp_f32": [I, I, P, P, P, P, L, P, I, I, I, F, F, F, F, F, F, P, P, P, P, F, P],
+    "cn_amp_count_skip": [P, P, P],
     "cn_pack_timeconv_f32": [P, P, I, I, I, I, I, P],
     "cn_fold_timeconv_grad_f32": [P, P, I, I, I, I, P],
     "cn_prepare_chips_f32": [P, I, P, P, P, I, I, L, F, F, F, P],

@@ -309,12 +309,25 @@ __global__ __launch_bounds__(256) void cn_optim_kernel(float* __restrict__ p, co
                          clip);
 }
 
+// Loss scaling (torch.amp.GradScaler, the reference's default precision "16-mixed") without a host synchronisation: the
+// scaler leaves three device words and the kernel reads them at block start, one wave-uniform load each.
+//   found_inf   != 0: this step is skipped -- every block returns before its first store, p / m / v keep their bits
+//   loss_scale  the gradient still carries it: an element sees g * grad_scale / *loss_scale, and the norm of
+//               CN_CLIP_NORM is sqrt(*sumsq) * grad_scale / *loss_scale (sumsq taken over the scaled gradient)
+//   skipped     steps skipped so far, which the host's step counts include: the coefficients use step - *skipped
+// Null means 1, 0 and 0: cn_optim_step_seg_f32 is this kernel with the three of them null.
 template <int KIND, int CLIP>
 __global__ __launch_bounds__(256) void cn_optim_seg_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                           float* __restrict__ m, float* __restrict__ v, long n,
                                                           const CnSeg* __restrict__ segs, int nseg, int nchunks,
                                                           int step_add, float lr, float b1, float b2, float eps, float wd,
-                                                          float grad_scale, const double* sumsq, float clip, int vec) {
+                                                          float grad_scale, const float* __restrict__ loss_scale,
+                                                          const float* __restrict__ found_inf,
+                                                          const int* __restrict__ skipped, const double* sumsq,
+                                                          float clip, int vec) {
+  if (found_inf != nullptr && *found_inf != 0.f) return;
+  if (loss_scale != nullptr) grad_scale *= 1.f / *loss_scale;
+  if (skipped != nullptr) step_add -= *skipped;
   const float gs = cn_clip_scale(CLIP, grad_scale, sumsq, clip);
   for (int ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
     const CnSeg sg = segs[cn_seg_find(segs, nseg, ch)];
@@ -325,6 +338,11 @@ __global__ __launch_bounds__(256) void cn_optim_seg_kernel(float* __restrict__ p
     const CnOptCoef c = cn_opt_coef(KIND, lr, b1, b2, eps, wd, (double)sg.step + step_add);
     cn_opt_run<KIND, CLIP>(p, g, m, v, lo, hi, threadIdx.x, 256, vec != 0, c, gs, clip);
   }
+}
+
+// ++*skipped when the scaler found an inf / NaN (after the step that read both words, on the same stream)
+__global__ void cn_amp_count_skip_kernel(const float* __restrict__ found_inf, int* __restrict__ skipped) {
+  if (*found_inf != 0.f) *skipped = *skipped + 1;
 }
 
 static bool cn_opt_args_ok(int kind, int clip_mode, const void* v, const double* sumsq) {
@@ -375,8 +393,30 @@ extern "C" int cn_optim_step_seg_f32(int kind, int clip_mode, float* p, const fl
   if (nseg == 0 || nchunks == 0) return CN_OK;
   CN_OPT_DISPATCH(cn_optim_seg_kernel, kind, clip_mode, dim3((unsigned)cn_seg_grid(nchunks, 2048)), dim3(256), 0,
                   (hipStream_t)stream, p, g, m, v, n, (const CnSeg*)segs, nseg, nchunks, step_add, lr, beta1, beta2, eps,
-                  weight_decay, grad_scale, sumsq, clip, cn_opt_vec(p, g, m, v));
+                  weight_decay, grad_scale, (const float*)nullptr, (const float*)nullptr, (const int*)nullptr, sumsq, clip,
+                  cn_opt_vec(p, g, m, v));
   return cn_check_launch();
 }
 
-extern "C" int cn_version() { return 102; }
+// The segmented step under a loss scaler: loss_scale / found_inf / skipped are DEVICE words (each may be null), see
+// cn_optim_seg_kernel. A whole, unfrozen model is a table of one segment.
+extern "C" int cn_optim_step_amp_f32(int kind, int clip_mode, float* p, const float* g, float* m, float* v, long n,
+                                     const void* segs, int nseg, int nchunks, int step_add, float lr, float beta1,
+                                     float beta2, float eps, float weight_decay, float grad_scale,
+                                     const float* loss_scale, const float* found_inf, const int* skipped,
+                                     const double* sumsq, float clip, void* stream) {
+  if (nseg < 0 || nchunks < 0 || n < 0 || !cn_opt_args_ok(kind, clip_mode, v, sumsq)) return CN_ERR_ARG;
+  if (nseg == 0 || nchunks == 0) return CN_OK;
+  CN_OPT_DISPATCH(cn_optim_seg_kernel, kind, clip_mode, dim3((unsigned)cn_seg_grid(nchunks, 2048)), dim3(256), 0,
+                  (hipStream_t)stream, p, g, m, v, n, (const CnSeg*)segs, nseg, nchunks, step_add, lr, beta1, beta2, eps,
+                  weight_decay, grad_scale, loss_scale, found_inf, skipped, sumsq, clip, cn_opt_vec(p, g, m, v));
+  return cn_check_launch();
+}
+
+extern "C" int cn_amp_count_skip(const float* found_inf, int* skipped, void* stream) {
+  if (found_inf == nullptr || skipped == nullptr) return CN_ERR_ARG;
+  CN_LAUNCH(cn_amp_count_skip_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, found_inf, skipped);
+  return cn_check_launch();
+}
+
+extern "C" int cn_version() { return 103; }

@@ -48,6 +48,19 @@ except Exception:  # pragma: no cover - exercised in the build image
             av = inspect.getargvalues(frame)
             self.hparams = {k: av.locals[k] for k in av.args if k != "self"}
 
+        def clip_gradients(self, optimizer, gradient_clip_val=None, gradient_clip_algorithm=None):
+            if gradient_clip_val is None or gradient_clip_val <= 0:
+                return
+            params = [p for g in optimizer.param_groups for p in g["params"]]
+            if str(getattr(gradient_clip_algorithm, "value", gradient_clip_algorithm)) == "value":
+                torch.nn.utils.clip_grad_value_(params, clip_value=gradient_clip_val)
+            else:
+                torch.nn.utils.clip_grad_norm_(params, gradient_clip_val)
+
+        def configure_gradient_clipping(self, optimizer, gradient_clip_val=None, gradient_clip_algorithm=None):
+            self.clip_gradients(optimizer, gradient_clip_val=gradient_clip_val,
+                                gradient_clip_algorithm=gradient_clip_algorithm)
+
         def log(self, *args, **kwargs):
             pass
 
@@ -347,21 +360,45 @@ class LightningModuleMixin(_Base):
             raise NameError("The learning rate scheduler is not implemented in Cultionet.")
         return per_epoch[name](), "epoch"
 
+    #: True: ``configure_optimizers`` returns a cultionet_amd.optim.NativeOptimizer (clip + optimizer as one or two HIP
+    #: launches over the flat parameter buffer, GradScaler without a host synchronisation) instead of the torch object
+    native_optimizer = False
+
     def configure_optimizers(self):
         """Lightning hook, same choices and error behaviour as the reference (lightning.py:611-683): a torch optimizer over
-        the model's parameters + one scheduler monitored on ``val_score``. (The native path -- HipTrainer -- builds no torch
-        object: it reads the same recipe table and runs clip + optimizer in cn_optim.hip, the schedule on the host.)"""
+        the model's parameters + one scheduler monitored on ``val_score``. With ``native_optimizer`` set the optimizer is
+        the NativeOptimizer of the same kind and hyper-parameters; the scheduler entry is the same. (The native path --
+        HipTrainer -- reads the same recipe table and runs clip + optimizer in cn_optim.hip, the schedule on the host.)"""
         recipe = self._OPTIMIZERS.get(str(self.optimizer))
         if recipe is None:
             raise NameError("Choose either 'AdamW' or 'SGD'.")
         cls_name, takes, fixed = recipe
         hyper = {"lr": self.learning_rate, "weight_decay": self.weight_decay, "eps": self.eps}
-        optimizer = getattr(torch.optim, cls_name)(list(self.cultionet_model.parameters()),
-                                                   **{k: hyper[k] for k in takes}, **fixed)
+        params = list(self.cultionet_model.parameters())
+        if self.native_optimizer:
+            from .optim import NativeOptimizer
+
+            if params[0].device.type != "cuda" or torch.version.hip is None:
+                raise RuntimeError("native_optimizer needs the model on a ROCm device (its step is a HIP kernel)")
+            optimizer = NativeOptimizer(params, self.cultionet_model.mask_model.param_store(), cls_name,
+                                        **{k: hyper[k] for k in takes}, **fixed)
+        else:
+            optimizer = getattr(torch.optim, cls_name)(params, **{k: hyper[k] for k in takes}, **fixed)
         scheduler, interval = self._make_scheduler(optimizer)
         return {"optimizer": optimizer,
                 "lr_scheduler": {"scheduler": scheduler, "name": "lr_sch", "monitor": "val_score", "interval": interval,
                                  "frequency": 1}}
+
+    def configure_gradient_clipping(self, optimizer, gradient_clip_val=None, gradient_clip_algorithm=None):
+        """Lightning hook. A NativeOptimizer clips inside its step (and under "16-mixed" it unscales there too, which is
+        why Lightning's AMP plugin would refuse ``clip_gradients`` for it): the values are handed over and no gradient is
+        touched. Any other optimizer: the base class's behaviour."""
+        from .optim import NativeOptimizer
+
+        if isinstance(optimizer, NativeOptimizer):
+            optimizer.set_clip(gradient_clip_val, gradient_clip_algorithm)
+            return
+        super().configure_gradient_clipping(optimizer, gradient_clip_val, gradient_clip_algorithm)
 
 
 class CultionetLitTransferModel(LightningModuleMixin):
@@ -566,16 +603,21 @@ class HipTrainer:
     update and no gradient is read for them (fused backward kernels may still write their slices), as torch optimizers skip parameters without ``.grad``; clipping sees the trainable
     gradients only, and every parameter keeps its own step count (bias corrections, RAdam's rectification). The
     trainable set is read at every step; it must not change inside a group of accumulated micro-batches.
+
+    The optimizer state and the launches of a step are a cultionet_amd.optim.NativeOptimizer (``trainer.opt``):
+    ``state_dict()`` / ``load_state_dict()`` stop and resume a run, or continue one from the optimizer state of a Lightning
+    checkpoint and hand it back.
     """
 
     _KINDS = {"Adam": 0, "AdamW": 0, "SGD": 1, "RAdam": 2}  # CN_OPT_* of csrc/cn_optim.hip
-    _CLIP_NONE, _CLIP_NORM, _CLIP_VALUE = 0, 1, 2          # CN_CLIP_*
 
     def __init__(self, lit: CultionetLitModel, gradient_clip_val: T.Optional[float] = 1.0,
                  lr_fn: T.Optional[T.Callable[[int], T.Union[float, T.Tuple[float, float]]]] = None, comm=None,
                  total_steps: T.Optional[int] = None, precision: str = "32-true", replay: bool = False,
                  gradient_clip_algorithm: str = "norm", accumulate_grad_batches: int = 1,
                  steps_per_epoch: T.Optional[int] = None):
+        from .optim import NativeOptimizer
+
         self.lit = lit
         # replay=True: forward + loss + backward run from a recorded launch plan after the first steps
         # (cultionet_amd/replay.py): the Python of a step drops from ~8-10 ms to ~1.5 ms, which is what bounds the step at
@@ -606,15 +648,16 @@ class HipTrainer:
         self.model = lit.cultionet_model.mask_model
         self.store = self.model.param_store()
         dev = self.store.flat.device
-        self.exp_avg = torch.zeros_like(self.store.flat)  # (SGD: the momentum buffer, its only state)
-        self.exp_avg_sq = torch.zeros_like(self.store.flat) if cls_name != "SGD" else None
-        self.sumsq = torch.zeros(1, dtype=torch.float64, device=dev)
+        # the optimizer state (exp_avg, exp_avg_sq, every parameter's step count, the segment table of the trainable set)
+        # and the launches of a step live in the NativeOptimizer, in torch's optimizer-state format: state_dict()
+        hyper = {"lr": lit.learning_rate, "weight_decay": lit.weight_decay, "eps": lit.eps}
+        self.opt = NativeOptimizer(list(lit.cultionet_model.parameters()), self.store, cls_name,
+                                   **{k: hyper[k] for k in takes}, **fixed)
         self.total = torch.zeros(1, dtype=torch.float32, device=dev)
         self.clip = gradient_clip_val
         if lr_fn is None:
             lr_fn = self._schedule(lit, total_steps, steps_per_epoch)
         self.lr_fn = lr_fn
-        self.step_count = 0
         self.comm = comm
         # lightning.Trainer(precision=...) of the reference (model.py:168-186; default "16-mixed"): on MI355X the
         # mixed mode is bf16 activations + fp32 master weights / statistics / accumulation (no loss scaling needed)
@@ -631,9 +674,7 @@ class HipTrainer:
         # gradient for them and the optimizer step skips them, as torch optimizers do for parameters without .grad.
         # Every parameter keeps its own step count: ``_psteps`` (per parameter, store order) once a step has run
         # with frozen parameters; until then all share ``step_count`` and the step is the unsegmented one.
-        self._psteps: T.Optional[T.List[int]] = None
         self._mask = self._trainable_mask()
-        self._segs = None  # (mask, steps at build, [(offset, length, step)], device table, chunks, (lo, hi))
         if comm is not None:
             # torch DDP (the reference's strategy="ddp", model.py:101,184) broadcasts rank 0's parameters and buffers
             # at construction; dropout masks must differ per rank (each rank draws its own torch RNG stream upstream)
@@ -690,26 +731,40 @@ class HipTrainer:
             raise ValueError("every parameter of the model is frozen (requires_grad=False): nothing to train")
         return mask
 
+    # the optimizer state under the names it had while it lived here
+    @property
+    def exp_avg(self) -> torch.Tensor:
+        return self.opt.exp_avg
+
+    @property
+    def exp_avg_sq(self) -> T.Optional[torch.Tensor]:
+        return self.opt.exp_avg_sq
+
+    @property
+    def sumsq(self) -> torch.Tensor:
+        return self.opt.sumsq
+
+    @property
+    def step_count(self) -> int:
+        """Optimizer steps taken (the schedule's clock; every parameter's step count until one is frozen)."""
+        return self.opt.step_count
+
+    @step_count.setter
+    def step_count(self, value: int) -> None:
+        self.opt.step_count = int(value)
+
+    @property
+    def _psteps(self) -> T.Optional[T.List[int]]:
+        return self.opt._psteps
+
     @property
     def param_steps(self) -> T.List[int]:
         """Optimizer step count of every parameter (store order)."""
-        return list(self._psteps) if self._psteps is not None else [self.step_count] * len(self.store.params)
+        return self.opt.param_steps
 
     def _segments(self):
         """Segment table of the current trainable set (rebuilt when that set changes)."""
-        steps = self.param_steps
-        sg = self._segs
-        if sg is None or sg[0] != self._mask:
-            store = self.store
-            segs = E.trainable_segments(store.offsets, [p.numel() for p in store.params], self._mask, steps)
-            raw, chunks = E.segment_table(segs)
-            table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(store.flat.device)
-            span = (segs[0][0], segs[-1][0] + segs[-1][1])
-            # the step counts of a table's parameters advance together while the set is unchanged: the kernel adds
-            # the steps taken since the build (step_add)
-            anchor = next(i for i, t in enumerate(self._mask) if t)
-            sg = self._segs = (self._mask, steps[anchor], segs, table, chunks, span)
-        return sg
+        return self.opt.segments(self._mask)
 
     def forward_backward(self, batch: Data, last: bool = False) -> torch.Tensor:
         """Forward + loss + backward; adds d(loss)/d(params) of this micro-batch to store.flat_grad (the trainable slices
@@ -780,23 +835,9 @@ class HipTrainer:
                 tape.backward()
         return self.total
 
-    def _clip_args(self, sumsq_entry: str, *seg_args) -> T.Tuple[int, T.Optional[int], float]:
-        """(clip mode, sumsq pointer, clip value) of this step; launches the sum of squares that norm clipping needs."""
-        from . import _lib
-
-        if self.clip is None:
-            return self._CLIP_NONE, None, 0.0
-        if self.clip_algorithm == "value":
-            return self._CLIP_VALUE, None, float(self.clip)
-        store = self.store
-        _lib.call(sumsq_entry, store.flat_grad.data_ptr(), store.numel, *seg_args, self.sumsq.data_ptr(), E._stream())
-        return self._CLIP_NORM, self.sumsq.data_ptr(), float(self.clip)
-
     def optimizer_step(self) -> None:
         """Clip + optimizer over what flat_grad holds: the sum of the micro-batches since the last step, divided by
         ``accumulate_grad_batches`` (and by the world size)."""
-        from . import _lib
-
         store = self.store
         if self.accumulate > 1 and self._micro == 0:
             raise RuntimeError("optimizer_step without a micro-batch since the last step: nothing accumulated")
@@ -804,53 +845,36 @@ class HipTrainer:
             self.comm.reduce(store)  # a trailing group flushed without a ``last=True`` micro-batch
             self._reduced = True
         self._micro = 0
-        self.step_count += 1
-        s = E._stream()
         scale = 1.0 / ((self.comm.world_size if self.comm is not None else 1) * self.accumulate)
-        mask = self._mask
-        if self._psteps is not None or not all(mask):
-            if self._psteps is None:
-                self._psteps = [self.step_count - 1] * len(mask)
-            for i, t in enumerate(mask):
-                if t:
-                    self._psteps[i] += 1
-            self._segmented_step(scale, s)
-            return
-        mode, sumsq, clip = self._clip_args("cn_grad_sumsq_f32")
-        sched = self.lr_fn(self.step_count)
+        sched = self.lr_fn(self.opt.step_count + 1)
         lr, beta1 = sched if isinstance(sched, tuple) else (sched, self._beta1)
-        v = self.exp_avg_sq.data_ptr() if self.exp_avg_sq is not None else None
-        if self.opt_kind == 0 and mode != self._CLIP_VALUE:  # AdamW / Adam, norm clipping or none: the original pair
-            _lib.call("cn_adamw_step_f32", store.flat.data_ptr(), store.flat_grad.data_ptr(), self.exp_avg.data_ptr(),
-                      v, store.numel, float(lr), float(beta1), self._beta2, self._eps, self._wd, self.step_count, scale,
-                      sumsq, clip, s)
-        else:
-            _lib.call("cn_optim_step_f32", self.opt_kind, mode, store.flat.data_ptr(), store.flat_grad.data_ptr(),
-                      self.exp_avg.data_ptr(), v, store.numel, float(lr), float(beta1), self._beta2, self._eps, self._wd,
-                      self.step_count, scale, sumsq, clip, s)
-        store.bump()
+        # unsegmented while no parameter has ever been frozen, else over the trainable runs only, each with its own
+        # step count (cultionet_amd.optim.launch_step)
+        self.opt.step_flat(store.flat_grad.data_ptr(), self._mask, lr, beta1, self._beta2, self._eps, self._wd, scale,
+                           self.clip, self.clip_algorithm)
 
-    def _segmented_step(self, scale: float, s: int) -> None:
-        """Clip + optimizer over the trainable runs only, each with its own step count (cn_*_seg_f32)."""
-        from . import _lib
+    def state_dict(self) -> T.Dict[str, T.Any]:
+        """What a resumed run needs besides the module's own state_dict: ``optimizer`` in torch's optimizer-state format
+        (what ``torch.optim.<kind>.state_dict()`` holds after the same steps: it can go into ``optimizer_states[0]`` of a
+        Lightning checkpoint), the schedule's clock and the accumulation phase. A copy: later steps do not change it."""
+        import copy
 
-        store = self.store
-        mask, step0, segs, table, chunks, _span = self._segments()
-        anchor = next(i for i, t in enumerate(mask) if t)
-        step_add = self._psteps[anchor] - step0
-        mode, sumsq, clip = self._clip_args("cn_grad_sumsq_seg_f32", table.data_ptr(), len(segs), chunks)
-        sched = self.lr_fn(self.step_count)
-        lr, beta1 = sched if isinstance(sched, tuple) else (sched, self._beta1)
-        v = self.exp_avg_sq.data_ptr() if self.exp_avg_sq is not None else None
-        if self.opt_kind == 0 and mode != self._CLIP_VALUE:
-            _lib.call("cn_adamw_step_seg_f32", store.flat.data_ptr(), store.flat_grad.data_ptr(), self.exp_avg.data_ptr(),
-                      v, store.numel, table.data_ptr(), len(segs), chunks, step_add, float(lr), float(beta1), self._beta2,
-                      self._eps, self._wd, scale, sumsq, clip, s)
-        else:
-            _lib.call("cn_optim_step_seg_f32", self.opt_kind, mode, store.flat.data_ptr(), store.flat_grad.data_ptr(),
-                      self.exp_avg.data_ptr(), v, store.numel, table.data_ptr(), len(segs), chunks, step_add, float(lr),
-                      float(beta1), self._beta2, self._eps, self._wd, scale, sumsq, clip, s)
-        store.bump(mask)  # only the trainable weights changed: only their packed copies are refreshed
+        return {"optimizer": copy.deepcopy(self.opt.state_dict()), "step_count": self.step_count, "micro": self._micro,
+                "param_steps": self.param_steps}
+
+    def load_state_dict(self, d: T.Mapping[str, T.Any]) -> None:
+        """Resume from ``state_dict()``. ``d["optimizer"]`` may equally be ``optimizer_states[0]`` of a Lightning
+        checkpoint written with the torch optimizer or the NativeOptimizer; without ``step_count`` the schedule resumes
+        from the largest step count in it. The state buffers are written in place: recorded replay plans stay valid."""
+        if self._micro != 0 or int(d.get("micro", 0)) != 0:
+            raise RuntimeError("load_state_dict inside a group of accumulated micro-batches: the gradients summed so far "
+                               "belong to another state (load after an optimizer step, save after one)")
+        self.opt.load_state_dict(d["optimizer"])
+        steps = d.get("param_steps")
+        if steps is not None and len(set(steps)) > 1:
+            self.opt._psteps = [int(t) for t in steps]
+        if "step_count" in d:
+            self.opt.step_count = int(d["step_count"])
 
     def training_step(self, batch: Data, last: bool = False) -> torch.Tensor:
         """One micro-batch; the optimizer steps once ``accumulate_grad_batches`` of them are summed, or at once with

@@ -33,7 +33,8 @@ extern "C" {
 #define CN_ERR_LDS (-3)
 
 /* cn_version(): 100 initial ABI; 101 adds cn_grad_sumsq_seg_f32 / cn_adamw_step_seg_f32 (frozen parameters);
- * 102 adds cn_optim_step_f32 / cn_optim_step_seg_f32 (Adam, SGD, RAdam; value clipping). */
+ * 102 adds cn_optim_step_f32 / cn_optim_step_seg_f32 (Adam, SGD, RAdam; value clipping);
+ * 103 adds cn_optim_step_amp_f32 / cn_amp_count_skip (the segmented step under a device-side loss scaler). */
 int cn_version(void);
 
 /* ---- packed weights for the implicit-GEMM kernels -------------------------------------------
@@ -336,6 +337,18 @@ int cn_optim_step_f32(int kind, int clip_mode, float* p, const float* g, float* 
 int cn_optim_step_seg_f32(int kind, int clip_mode, float* p, const float* g, float* m, float* v, long n, const void* segs,
                           int nseg, int nchunks, int step_add, float lr, float beta1, float beta2, float eps,
                           float weight_decay, float grad_scale, const double* sumsq, float clip, void* stream);
+/* The segmented step under torch.amp.GradScaler (v103), without a host synchronisation. Three DEVICE words, each may be
+ * null (= 1, 0, 0):
+ *   loss_scale  the gradient still carries it: an element sees g * grad_scale / *loss_scale; the norm of clip_mode 1 is
+ *               sqrt(*sumsq) * grad_scale / *loss_scale, sumsq taken over the scaled gradient (cn_grad_sumsq_seg_f32)
+ *   found_inf   != 0: the step is skipped, p / m / v keep their bits
+ *   skipped     number of skipped steps the host's counts include: the coefficients use step + step_add - *skipped
+ * cn_amp_count_skip: ++*skipped if *found_inf != 0 (launch it after the step, on the same stream). */
+int cn_optim_step_amp_f32(int kind, int clip_mode, float* p, const float* g, float* m, float* v, long n, const void* segs,
+                          int nseg, int nchunks, int step_add, float lr, float beta1, float beta2, float eps,
+                          float weight_decay, float grad_scale, const float* loss_scale, const float* found_inf,
+                          const int* skipped, const double* sumsq, float clip, void* stream);
+int cn_amp_count_skip(const float* found_inf, int* skipped, void* stream);
 
 /* ---- input / output edges ------------------------------------------------
  * prepare: EdgeDataset.get scale + clip (data/datasets.py:443-446) + NormValues z-score
