@@ -13,1288 +13,55 @@ Design (MI355X-first, not torch.autograd):
     slices): no separate add/copy kernels.
   * parameters live in ONE flat fp32 buffer and so do their gradients (``ParamStore``): the optimizer
     is one fused launch and data-parallel all-reduce buckets are plain slices of the flat gradient.
+
+This module holds the ops of both precisions. What they stand on lives in four modules, each importing only from those
+before it: ``runtime`` (thread state, streams, allocator), ``params`` (ParamStore, weight packs), ``scratch`` (deferred
+slice sums, scratch pools), ``tape`` (Var, Tape, spawn / join). Their names are re-bound here: ``engine`` is the name
+the rest of the package uses.
 """
 from __future__ import annotations
 
-import bisect
-import struct
-import threading
 import contextlib
-import os
+import ctypes
+import struct
 import typing as T
 
 import torch
 
-from . import _lib
-
-_state = threading.local()
-
-
-# ---- launch-plan recording (cultionet_amd/replay.py) ----------------------------------------------------------------
-# While a plan is being recorded, every stream / event operation and every host-side torch call that launches work is
-# routed through _py_op so that the plan can repeat it; C-ABI calls are captured by a recording _lib.call.
-_recorder: T.Optional[T.List] = None
-
-
-def _py_op(fn: T.Callable, *args) -> None:
-    """Run ``fn(*args)`` now and, while a launch plan is being recorded, append it to the plan."""
-    fn(*args)
-    if _recorder is not None:
-        _recorder.append((1, fn, args))
-
-
-def _main_stream() -> "torch.cuda.Stream":
-    """torch's current stream, looked up once per ``using_store`` scope (a forward, a backward or a whole native step:
-    the stream cannot change inside one) -- ``torch.cuda.current_stream()`` costs ~11 us, and at ~420 launches per step
-    that was a third of the host's enqueue time."""
-    ms = getattr(_state, "main_stream", None)
-    return ms if ms is not None else torch.cuda.current_stream()
-
-
-def _stream() -> int:
-    """HIP stream handle the next launch goes to: the side stream inside a ``side_stream`` block, else torch's
-    current stream."""
-    ov = getattr(_state, "stream_override", None)
-    if ov is not None:
-        return ov
-    h = getattr(_state, "main_handle", None)
-    return h if h is not None else torch.cuda.current_stream().cuda_stream
-
-
-def _check(t: torch.Tensor) -> torch.Tensor:
-    if not t.is_cuda:
-        raise RuntimeError("cultionet_amd ops need device tensors (MI355X); there is no CPU fallback")
-    if t.dtype == torch.bfloat16:
-        # mixed-precision path: bf16 activations are NHWC (logical shape [B,C,H,W], channel stride 1)
-        if t.dim() != 4 or (t.shape[1] > 1 and t.stride(1) != 1) or t.stride(3) % 8 or t.data_ptr() % 16:
-            raise RuntimeError("bf16 activations must be NHWC views (channels innermost, 16-byte aligned slices)")
-        return t
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"fp32 (or bf16 NHWC) tensor expected, got {t.dtype}")
-    return t
-
-
-def is16(t: torch.Tensor) -> bool:
-    return t.dtype == torch.bfloat16
-
-
-def ld(t: torch.Tensor) -> int:
-    """Pixel stride (elements) of a bf16 NHWC activation held as a logical [B,C,H,W] view."""
-    return t.stride(3)
-
-
-def _dense16(t: torch.Tensor) -> bool:
-    """Pixels of all images form ONE run of rows with stride ld (kernels take P = B*H*W rows)."""
-    B, _, H, W = t.shape
-    l = t.stride(3)
-    return (W == 1 or True) and (H == 1 or t.stride(2) == W * l) and (B == 1 or t.stride(0) == H * W * l)
-
-
-class mixed_precision:
-    """Context manager: run the TowerUNet body (encoder .. tower heads) in bf16 NHWC with fp32 accumulation,
-    statistics and parameters -- the reference's precision="16-mixed" (model.py:168-186) on MI355X MFMA."""
-
-    def __init__(self, enabled: bool = True):
-        self.enabled = bool(enabled)
-
-    def __enter__(self):
-        self.prev = getattr(_state, "bf16", False)
-        _state.bf16 = self.enabled
-        return self
-
-    def __exit__(self, *exc):
-        _state.bf16 = self.prev
-        return False
-
-
-def bf16_enabled() -> bool:
-    return bool(getattr(_state, "bf16", False))
-
-
-def bstride(t: torch.Tensor) -> int:
-    """Batch stride of an NCHW(-like) buffer whose inner dims are dense."""
-    return t.stride(0) if t.shape[0] > 1 else int(t[0].numel())
-
-
-def _dense_inner(t: torch.Tensor) -> bool:
-    exp = 1
-    for d in range(t.dim() - 1, 0, -1):
-        if t.shape[d] != 1 and t.stride(d) != exp:
-            return False
-        exp *= t.shape[d]
-    return True
-
-
-class Var:
-    """A device buffer and (during training) its gradient buffer."""
-
-    __slots__ = ("t", "grad", "req", "parent", "stats", "bnfin")
-
-    def __init__(self, t: torch.Tensor, req: bool = False):
-        self.t = t
-        self.grad: T.Optional[torch.Tensor] = None
-        self.req = req
-        self.parent: T.Optional[T.Tuple["Var", int, int]] = None  # channel slice [c0, c1) of another Var
-        self.stats: T.Optional[torch.Tensor] = None  # bf16 conv outputs: per-channel {sum, sumsq} from the epilogue
-        self.bnfin = None  # (bn module, mean, rstd): BatchNorm statistics already finished by the producing conv launch
-
-    @property
-    def shape(self):
-        return self.t.shape
-
-
-def _tr(p: T.Optional[torch.Tensor]) -> bool:
-    """Does parameter ``p`` get a gradient (exists and ``requires_grad``)? Frozen parameters get none."""
-    return p is not None and p.requires_grad
-
-
-def _req(tape: "Tape", vs: T.Sequence[T.Optional[Var]] = (), params: T.Sequence[T.Optional[torch.Tensor]] = ()) -> bool:
-    """Does an op's output need a gradient: the tape is on and an input or one of the op's own parameters needs one.
-    An op whose output needs none records no tape node."""
-    if not tape.enabled:
-        return False
-    return any(v is not None and v.req for v in vs) or any(p is not None and p.requires_grad for p in params)
-
-
-class Tape:
-    def __init__(self, enabled: bool):
-        self.enabled = enabled
-        self.nodes: T.List[T.Callable[[], None]] = []
-        self.marks: T.Dict[int, int] = {}  # flat offset of a parameter -> index of the node that uses it
-
-    def add(self, fn: T.Callable[[], None], params: T.Sequence[T.Optional[torch.Tensor]] = ()) -> None:
-        if self.enabled:
-            br = getattr(_state, "branch", None)
-            if br is not None:  # recorded inside spawn(): its backward runs on the branch's stream
-                fn = br.wrap(fn)
-            self.nodes.append(fn)
-            if params:
-                base = current_store()._base
-                idx = len(self.nodes) - 1
-                for p in params:
-                    # frozen parameters get no gradient: only trainable offsets are marked (the bucket plan relies on it)
-                    if p is not None and p.requires_grad:  # a gradient is final once backward has passed the FIRST node that used it
-                        k = (p.data_ptr() - base) // 4
-                        self.marks[k] = min(self.marks.get(k, idx), idx)
-
-    def backward(self) -> None:
-        nodes, self.nodes = self.nodes, []
-        hold = begin_branch_backward(self)
-        store = getattr(_state, "store", None)
-        try:
-            with deferring_slice_sums(store) if store is not None else contextlib.nullcontext():
-                while nodes:
-                    fn = nodes.pop()
-                    fn()
-                    if hold is not None:
-                        hold.append(fn)
-        finally:
-            release_branches()
-        join_side_stream()
-
-
-# ---------------------------------------------------------------------------
-# weight gradients on a side stream
-# ---------------------------------------------------------------------------
-# In backward only dx feeds the next node; dW (and bias gradients) are needed by the optimizer alone. Their launches
-# go to a second HIP stream that waits for the node's dy, so the launch-shaped layers of the coarse levels (25x25,
-# 13x13: a fraction of the 256 CUs each) run beside the dx chain instead of in front of it. The main stream joins
-# the side stream once, before the gradient exchange / optimizer. CN_OVERLAP_WGRAD=0 keeps everything on one stream.
-_OVERLAP_WGRAD = os.environ.get("CN_OVERLAP_WGRAD", "1") == "1"
-_side_streams: T.Dict[T.Any, T.Dict[str, T.Any]] = {}
-
-
-def overlap_wgrad(enabled: bool) -> bool:
-    """Switch the weight-gradient side stream on / off at run time (bench.py's isolated per-kernel pass); returns the
-    previous setting. Pending side-stream work is joined first."""
-    global _OVERLAP_WGRAD
-    prev = _OVERLAP_WGRAD
-    join_side_stream()
-    _OVERLAP_WGRAD = bool(enabled)
-    return prev
-
-
-def _make_side_stream(dev) -> "torch.cuda.Stream":
-    """The weight-gradient stream. Its kernels (one wave per SIMD, hundreds of microseconds each) must not take CUs
-    from the data-gradient chain on the compute stream, which is the critical path: it is created with the LOWEST
-    priority the device offers through the C ABI (torch.cuda.Stream can only ask for normal or higher) and wrapped as
-    a torch ExternalStream for events / record_stream. (A normal-priority stream and a CU-masked one were measured
-    against it and removed: DESIGN.md section 2.)"""
-    import ctypes
-
-    handle = ctypes.c_void_p()
-    rng = (ctypes.c_int * 2)()
-    with torch.cuda.device(dev):
-        _lib.call("cn_stream_priority_range", rng)
-        _lib.call("cn_stream_create", int(rng[0]), None, 0, ctypes.byref(handle))
-    return torch.cuda.ExternalStream(handle.value, device=dev)
-
-
-def _side_state(dev) -> T.Dict[str, T.Any]:
-    st = _side_streams.get(dev)
-    if st is None:
-        st = {"stream": _make_side_stream(dev), "event": torch.cuda.Event(), "dirty": False}
-        _side_streams[dev] = st
-    return st
-
-
-class side_stream:
-    """Context manager: enqueue the enclosed launches on the side stream, ordered after everything enqueued so far on
-    the current stream. ``tensors`` are the buffers those launches read (kept from being recycled by the caching
-    allocator until the side stream has passed them)."""
-
-    def __init__(self, *tensors: torch.Tensor):
-        self.tensors = tensors
-        self.ctx = None
-
-    def __enter__(self):
-        if not _OVERLAP_WGRAD:
-            return self
-        main = _main_stream()
-        st = _side_state(main.device)
-        cur = getattr(_state, "stream_obj_override", None) or main  # (inside spawn(): the branch's stream)
-        if cur is main:
-            _py_op(st["event"].record, main)
-            _py_op(st["stream"].wait_event, st["event"])
-        else:  # a fresh event: st["event"] may still be pending on the compute stream's behalf
-            ev = torch.cuda.Event()
-            _py_op(ev.record, cur)
-            _py_op(st["stream"].wait_event, ev)
-        st["dirty"] = True
-        self.st = st
-        self.prev = (getattr(_state, "stream_override", None), getattr(_state, "stream_obj_override", None))
-        # launches go through the C ABI with an explicit stream handle: redirect _stream() instead of switching torch's
-        # current stream (a torch.cuda.stream() context costs ~15 us of host time per layer). torch allocations made
-        # inside the block still belong to the main stream: nothing inside may rely on a torch op (fills go through
-        # cn_fill_f32 on the side stream).
-        self.ctx = True
-        _state.stream_override = st["stream"].cuda_stream
-        _state.stream_obj_override = st["stream"]
-        return self
-
-    def __exit__(self, *exc):
-        if self.ctx is not None:
-            _state.stream_override, _state.stream_obj_override = self.prev
-            for t in self.tensors:
-                if t is not None:
-                    t.record_stream(self.st["stream"])
-        return False
-
-
-def join_side_stream() -> None:
-    """Make the current stream wait for every weight-gradient launch issued so far."""
-    if not torch.cuda.is_available():
-        return
-    main = _main_stream()
-    st = _side_streams.get(main.device)
-    if st is not None and st["dirty"]:
-        _py_op(main.wait_stream, st["stream"])
-        st["dirty"] = False
-
-
-# ---------------------------------------------------------------------------
-# small sub-graphs beside the big kernels: spawn() / join()
-# ---------------------------------------------------------------------------
-# final_c and final_b (TowerUNetFinal, nunet.py:197-202 of the reference) are chains of ~15 small launches forward and
-# ~25 backward on 9- / 3- / 1-channel tensors. They depend only on x_tower_c / x_tower_b, which exist long before the
-# forward reaches the heads, and in backward nothing needs their result until tower_b / tower_c run. spawn() puts such
-# a chain on an auxiliary stream the moment its input exists, so that it executes BESIDE the MFMA-bound tower
-# convolutions of the compute stream (the regime in which overlap pays on this chip: a bandwidth- / latency-bound kernel
-# next to a matrix-pipe-bound one); its tape nodes run on the same stream in backward. ``branch_streams(False)``: off.
-_aux_streams: T.Dict[T.Any, T.List["torch.cuda.Stream"]] = {}
-
-
-# Hardware queues of one process (round 6, profiles/r06_hw_queues.txt). The HIP runtime keeps a pool of up to
-# GPU_MAX_HW_QUEUES hardware queues PER STREAM PRIORITY, and this chip runs a process's queues concurrently
-# only while there are at most SEVEN of them: with an eighth the queues are time-sliced and the whole step runs 1.5-1.9x
-# slower (that is the "auxiliary streams + bucket collectives" slowdown of rounds 4-5: a torch.distributed process group
-# brings six normal-priority streams with it -- 6 + the weight-gradient stream's lowest-priority queue + two
-# highest-priority auxiliary queues = 9). The engine therefore owns exactly one queue per extra priority -- the
-# weight-gradient stream (lowest) and ONE auxiliary stream for every spawn() (highest) -- and the process is expected to
-# cap the normal pool at 5 (cultionet_amd.configure_runtime): 5 + 1 + 1 = 7 whatever the process group creates.
-_HW_QUEUE_BUDGET = 7
-
-
-def _hw_queue_cap() -> int:
-    try:
-        return int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))  # (unset: the runtime's default of 4)
-    except ValueError:
-        return 4
-
-
-def branch_streams_allowed() -> bool:
-    """spawn() runs its sub-graph on the auxiliary stream unless that could push the process over the hardware-queue
-    budget: with a torch.distributed process group alive (six normal-priority streams of its own) the auxiliary stream
-    needs GPU_MAX_HW_QUEUES <= 5 (cap + weight-gradient queue + auxiliary queue <= 7). Checked LIVE at every spawn()
-    (ADVICE r4), so it follows the group's lifetime and covers the drop-in mode under Lightning's own DDP;
-    ``engine.branch_streams(False)`` switches spawn() off for a scope. One-rank RCCL group, same box: bf16 2249 chips/s
-    with the auxiliary stream at 5 queues against 2162 without it at 8 (single process 2279-2285); at 6 queues 1396."""
-    if getattr(_state, "no_branches", False):
-        return False
-    import torch.distributed as dist
-
-    if dist.is_available() and dist.is_initialized():
-        return _hw_queue_cap() + 2 <= _HW_QUEUE_BUDGET
-    return True
-
-
-class branch_streams:
-    """Context manager: allow (default) / forbid spawn() to use auxiliary streams on this thread for a scope."""
-
-    def __init__(self, enabled: bool):
-        self.enabled = bool(enabled)
-
-    def __enter__(self):
-        self.prev = getattr(_state, "no_branches", False)
-        _state.no_branches = not self.enabled
-        return self
-
-    def __exit__(self, *exc):
-        _state.no_branches = self.prev
-        return False
-
-
-def _aux_stream(dev, k: int = 0) -> "torch.cuda.Stream":
-    """THE auxiliary stream of ``dev`` (``k`` names the sub-graph for the reader: every spawn() shares one stream since
-    round 6 -- a second highest-priority stream is a second hardware queue, see _HW_QUEUE_BUDGET; same box, single
-    process: bf16 2279 / fp32 387.5 chips/s with one stream against 2285 / 385.8 with two)."""
-    if _OVERLAP_WGRAD:
-        _side_state(dev)  # HIP deals streams to hardware queues in creation order: the weight-gradient stream first
-    lst = _aux_streams.setdefault(dev, [])
-    if not lst:
-        # HIGHEST priority, through the C ABI like the weight-gradient stream: a priority is a property of the hardware
-        # queue, so this stream can never be dealt the queue of the compute stream, of the (lowest-priority)
-        # weight-gradient stream or of RCCL's streams -- with torch.cuda.Stream() (normal priority) a live process group
-        # put an auxiliary stream on a queue shared with the compute stream: 2115 -> 1255 chips/s (bf16), 377 -> 241 (fp32).
-        import ctypes
-
-        handle = ctypes.c_void_p()
-        rng = (ctypes.c_int * 2)()
-        with torch.cuda.device(dev):
-            _lib.call("cn_stream_priority_range", rng)
-            _lib.call("cn_stream_create", int(rng[1]), None, 0, ctypes.byref(handle))
-        lst.append(torch.cuda.ExternalStream(handle.value, device=dev))
-    return lst[0]
-
-
-# ---- the engine's allocator -----------------------------------------------------------------------------------------
-# Every per-step buffer of the engine (activations, gradients, statistics rows, masks, scratch) comes from _alloc().
-# torch's caching allocator only knows the compute stream, while launches carry explicit stream handles: whoever needs
-# buffers to outlive a host-side free -- the branches of spawn() until they are joined, a launch plan while it is being
-# recorded -- registers a list as an allocation SINK of the calling thread (``holding_allocations``), and _alloc() files
-# every tensor it hands out there. Nothing in ``torch``'s namespace is touched (VERDICT r5 item 8: rounds 3-5 wrapped
-# torch.empty / zeros / full process-wide instead).
-def _alloc(shape, dtype: torch.dtype, device) -> torch.Tensor:
-    t = torch.empty(shape, dtype=dtype, device=device)
-    sinks = getattr(_state, "alloc_sinks", None)
-    if sinks:
-        for sink in sinks:
-            sink.append(t)
-    return t
-
-
-def _alloc_like(t: torch.Tensor) -> torch.Tensor:
-    return _alloc(tuple(t.shape), t.dtype, t.device)
-
-
-def alloc(shape, dtype: torch.dtype, device) -> torch.Tensor:
-    """Public form of the engine allocator for the host mirror (unet_parts / lightning): a buffer whose lifetime follows
-    the calling thread's open branches / plan recording."""
-    return _alloc(shape, dtype, device)
-
-
-class holding_allocations:
-    """Context manager: every buffer _alloc() hands out on this thread is also appended to ``sink`` (kept alive by it)."""
-
-    def __init__(self, sink: T.List[T.Any]):
-        self.sink = sink
-
-    def __enter__(self):
-        sinks = getattr(_state, "alloc_sinks", None)
-        if sinks is None:
-            sinks = _state.alloc_sinks = []
-        sinks.append(self.sink)
-        return self.sink
-
-    def __exit__(self, *exc):
-        sinks = _state.alloc_sinks
-        for i in range(len(sinks) - 1, -1, -1):
-            if sinks[i] is self.sink:
-                del sinks[i]
-                break
-        return False
-
-
-class _KeepAlive:
-    """Frees are deferred while any branch is open. torch's caching allocator only knows the compute stream (launches
-    go through the C ABI with explicit stream handles): a block freed on the host while an auxiliary stream's kernel
-    still uses it could be handed to a compute-stream allocation at once. Reference-counted per thread: buffers the
-    engine allocates (``keep`` is an allocation sink of _alloc while depth > 0), finished backward closures and incoming
-    gradients are held until the thread's last open branch has been joined."""
-
-    def __init__(self):
-        self.depth = 0
-        self.keep: T.List[T.Any] = []
-        self._hold: T.Optional[holding_allocations] = None
-
-    def acquire(self) -> None:
-        self.depth += 1
-        if self.depth == 1:
-            self._hold = holding_allocations(self.keep)
-            self._hold.__enter__()
-
-    def release(self, force: bool = False) -> None:
-        if self.depth == 0:
-            return
-        self.depth = 0 if force else self.depth - 1
-        if self.depth == 0:
-            if self._hold is not None:
-                self._hold.__exit__(None, None, None)
-                self._hold = None
-            self.keep = []
-
-
-def _keepalive() -> _KeepAlive:
-    ka = getattr(_state, "keepalive", None)
-    if ka is None:
-        ka = _state.keepalive = _KeepAlive()
-    return ka
-
-
-def begin_branch_backward(tape) -> T.Optional[T.List[T.Any]]:
-    """A tape with spawned branches: NOTHING is freed during its backward (returns the list that holds the finished
-    nodes' closures; the engine's allocations are filed there by _alloc). Between a branch's start and its fork the compute stream
-    runs arbitrary nodes of its own; a block one of them frees on the host while its kernel is still queued must not be
-    handed to an allocation whose kernel runs on an auxiliary stream."""
-    if not getattr(tape, "has_branches", False):
-        return None
-    ka = _keepalive()
-    ka.acquire()
-    return ka.keep
-
-
-def release_branches() -> None:
-    """After a backward pass (also one that raised): nothing may be left holding tensors or torch wrappers."""
-    _keepalive().release(force=True)
-    _state.open_branches = []
-
-
-def aux_stream_events() -> T.List["torch.cuda.Event"]:
-    """Events recorded now on the auxiliary streams with backward work of open branches (for the RCCL bucket stream,
-    like side_stream_event())."""
-    out = []
-    for br in getattr(_state, "open_branches", ()):
-        ev = torch.cuda.Event()
-        ev.record(br.stream)
-        out.append(ev)
-    return out
-
-
-class _Branch:
-    def __init__(self, stream: "torch.cuda.Stream", main: "torch.cuda.Stream", inputs, aliases):
-        self.stream, self.main = stream, main
-        self.inputs, self.aliases = inputs, aliases
-        self.fork_ev, self.done_ev = torch.cuda.Event(), torch.cuda.Event()
-        self.left = 0
-        self.result = None
-
-    def enter(self):
-        prev = (getattr(_state, "stream_override", None), getattr(_state, "stream_obj_override", None))
-        _state.stream_override, _state.stream_obj_override = self.stream.cuda_stream, self.stream
-        _bind_conv_workspace(self.main.device)
-        return prev
-
-    @staticmethod
-    def leave(prev) -> None:
-        _state.stream_override, _state.stream_obj_override = prev
-
-    def wrap(self, fn: T.Callable[[], None]) -> T.Callable[[], None]:
-        self.left += 1
-
-        def node():
-            prev = self.enter()
-            try:
-                fn()
-            finally:
-                self.leave(prev)
-            _keepalive().keep.append(fn)  # its closure (saved activations) lives until the branches are joined
-            self.left -= 1
-            if self.left == 0:
-                _py_op(self.done_ev.record, self.stream)
-
-        return node
-
-    def bwd_fork(self) -> None:
-        """In backward this runs AFTER the branch's nodes (it was recorded before them): the compute stream waits for
-        the branch, takes over the gradients of its inputs, and the deferred frees of this branch are released."""
-        _py_op(self.main.wait_event, self.done_ev)
-        for x, xa in zip(self.inputs, self.aliases):
-            if xa.grad is not None:
-                give_grad(x, xa.grad)
-                xa.grad = None
-        ob = getattr(_state, "open_branches", None)
-        if ob and self in ob:
-            ob.remove(self)
-        _keepalive().release()
-
-
-def spawn(fn: T.Callable[..., T.Any], inputs: T.Sequence[Var], k: int) -> T.Tuple[T.Optional[_Branch], T.Any]:
-    """Run ``fn(*aliases of inputs)`` -- engine ops that read nothing but ``inputs`` and the parameters -- on auxiliary
-    stream k, concurrently with whatever the compute stream does next. Returns (branch, result); join([branch, ...])
-    must be called before the result is used. The branch sees ALIASES of its inputs (same tensors, own gradient slots):
-    two streams never accumulate into one gradient buffer; the compute stream adds the alias gradients in bwd_fork."""
-    tape = current_tape()
-    if (not _OVERLAP_WGRAD or not torch.cuda.is_available() or getattr(_state, "stream_override", None) is not None
-            or getattr(_state, "branch", None) is not None or not branch_streams_allowed()):
-        return None, fn(*inputs)
-    main = _main_stream()
-    aliases = [Var(x.t, x.req) for x in inputs]
-    br = _Branch(_aux_stream(main.device, k), main, list(inputs), aliases)
-    if tape.enabled:
-        tape.has_branches = True
-        tape.add(br.bwd_fork)
-    _keepalive().acquire()
-    _py_op(br.fork_ev.record, main)
-    _py_op(br.stream.wait_event, br.fork_ev)
-    prev = br.enter()
-    _state.branch = br
-    try:
-        br.result = fn(*aliases)
-    finally:
-        _state.branch = None
-        br.leave(prev)
-    _py_op(br.done_ev.record, br.stream)
-    return br, br.result
-
-
-def join(branches: T.Sequence[T.Optional[_Branch]]) -> None:
-    """The compute stream waits for the spawned branches (forward); in backward this is where they may start."""
-    brs = [b for b in branches if b is not None]
-    if not brs:
-        return
-    tape = current_tape()
-    for br in brs:
-        _py_op(br.main.wait_event, br.done_ev)
-        _keepalive().release()
-    if not tape.enabled:
-        return
-
-    def bwd_join():
-        ka = _keepalive()
-        ob = getattr(_state, "open_branches", None)
-        if ob is None:
-            ob = _state.open_branches = []
-        ev = torch.cuda.Event()
-        for br in brs:
-            ka.acquire()
-            ob.append(br)
-            r = br.result
-            for v in (r if isinstance(r, (tuple, list)) else (r,)):
-                if isinstance(v, Var) and v.grad is not None:
-                    ka.keep.append(v.grad)  # allocated before the deferral began, freed inside the branch
-        _py_op(ev.record, brs[0].main)
-        for br in brs:
-            _py_op(br.stream.wait_event, ev)
-            if br.left == 0:  # no backward nodes: nothing to wait for at the fork
-                _py_op(br.done_ev.record, br.stream)
-
-    tape.add(bwd_join)
-
-
-def side_stream_event() -> T.Optional["torch.cuda.Event"]:
-    """An event recorded on the weight-gradient side stream now (None when nothing is pending there): lets another
-    stream -- the RCCL bucket stream -- wait for the gradients issued so far without stalling the compute stream."""
-    if not torch.cuda.is_available():
-        return None
-    st = _side_streams.get(_main_stream().device)
-    if st is None or not st["dirty"]:
-        return None
-    ev = torch.cuda.Event()
-    ev.record(st["stream"])
-    return ev
-
-
-def current_tape() -> Tape:
-    tp = getattr(_state, "tape", None)
-    if tp is None:
-        tp = Tape(False)
-        _state.tape = tp
-    return tp
-
-
-class recording:
-    """Context manager: run forward ops under a fresh tape (enabled or not)."""
-
-    def __init__(self, enabled: bool = True):
-        self.tape = Tape(enabled)
-
-    def __enter__(self) -> Tape:
-        self.prev = getattr(_state, "tape", None)
-        _state.tape = self.tape
-        return self.tape
-
-    def __exit__(self, *exc):
-        _state.tape = self.prev
-        return False
-
-
-# ---------------------------------------------------------------------------
-# gradient plumbing
-# ---------------------------------------------------------------------------
-
-def grad_buffer(v: Var) -> T.Tuple[torch.Tensor, int]:
-    """(buffer, accumulate flag) to write/accumulate v's gradient into."""
-    if v.grad is None:
-        if v.parent is not None:
-            # a channel slice writes straight into its parent's gradient (zero-filled once, then accumulated)
-            pv, c0, c1 = v.parent
-            if pv.grad is None:
-                pv.grad = _new(tuple(pv.t.shape), pv.t)
-                if is16(pv.t):
-                    _lib.call("cn_zero_bf16", pv.grad.data_ptr(), ld(pv.grad), _rows(pv.grad), pv.grad.shape[1], _stream())
-                else:
-                    _lib.call("cn_fill_f32", pv.grad.data_ptr(), pv.grad.numel(), 0.0, _stream())
-            v.grad = pv.grad[:, c0:c1]
-            return v.grad, 1
-        v.grad = _new(tuple(v.t.shape), v.t)
-        return v.grad, 0
-    return v.grad, 1
-
-
-def give_grad(v: Var, g: torch.Tensor) -> None:
-    """v.grad (+)= g where the op is the identity on the gradient: alias when first, else add in place."""
-    if not v.req:
-        return
-    if v.grad is None and v.parent is None:
-        v.grad = g
-        return
-    if v.grad is None:
-        grad_buffer(v)
-    if is16(g):
-        _lib.call("cn_copy_bf16", g.data_ptr(), ld(g), v.grad.data_ptr(), ld(v.grad), _rows(g), g.shape[1], 1, _stream())
-        return
-    B = g.shape[0]
-    n = g[0].numel()
-    _lib.call("cn_copy_f32", g.data_ptr(), bstride(g), v.grad.data_ptr(), bstride(v.grad), B, n, 1, _stream())
-
-
-# ---------------------------------------------------------------------------
-# flat parameter store
-# ---------------------------------------------------------------------------
-
-class PackFormat(T.NamedTuple):
-    """One layout of the implicit-GEMM weight copies: the single-pack and the batched entry point, the element count
-    of a copy of (T, K, N), its element type, and (wptr, dst ptr, T, K, N, sk, sn, st) -> the bytes of one record of
-    the batched entry point's descriptor table."""
-    pack: str
-    batched: str
-    elems: T.Callable[[int, int, int], int]
-    dtype: torch.dtype
-    record: T.Callable[..., bytes]
-
-
-def _pack_record_f32(wptr: int, dst: int, T_: int, K: int, N: int, sk: int, sn: int, st: int) -> bytes:
-    """CnPackDesc (csrc/cn_conv.hip), 64 bytes."""
-    kp, np_ = _lib.query("cn_conv_kpad", K), _lib.query("cn_conv_npad", N)
-    return struct.pack("<QQiiiiiiqqq", wptr, dst, T_, K, N, kp, np_, 0, sk, sn, st)
-
-
-def _pack_record_bf16(wptr: int, dst: int, T_: int, K: int, N: int, sk: int, sn: int, st: int) -> bytes:
-    """CnBPackDesc (csrc/cn_bconv.hip), 72 bytes (nscale = NULL)."""
-    return struct.pack("<QQiiiiiiqqqQ", wptr, dst, T_, K, N, (K + 15) // 16, (N + 31) // 32, 0, sk, sn, st, 0)
-
-
-PACK_F32 = PackFormat(  # [tap][Kpad][Npad] fp32
-    "cn_pack_weights_f32", "cn_pack_weights_batched_f32",
-    lambda T_, K, N: T_ * _lib.query("cn_conv_kpad", K) * _lib.query("cn_conv_npad", N),
-    torch.float32, _pack_record_f32)
-PACK_BF16 = PackFormat(  # bf16 MFMA fragments (mixed-precision path)
-    "cn_pack_weights_bf16", "cn_pack_weights_batched_bf16",
-    lambda T_, K, N: _lib.query("cn_bconv_packed_elems", T_, K, N),
-    torch.bfloat16, _pack_record_bf16)
-
-
-def select_packs(offsets: T.Sequence[int], spans: T.Sequence[T.Tuple[int, int]],
-                 dirty: T.Optional[T.AbstractSet[int]]) -> T.List[int]:
-    """Indices of the pack records to refresh: all of them (``dirty`` None), else those whose source -- elements
-    [lo, hi) of the flat buffer: a dense weight tensor, or adjacent ones (a declared group) -- overlaps a parameter in
-    ``dirty`` (parameter i starts at ``offsets[i]``, ascending)."""
-    if dirty is None:
-        return list(range(len(spans)))
-    out = []
-    for r, (lo, hi) in enumerate(spans):
-        i = max(bisect.bisect_right(offsets, lo) - 1, 0)
-        while i < len(offsets) and offsets[i] < hi:
-            if i in dirty:
-                out.append(r)
-                break
-            i += 1
-    return out
-
-
-_SUB_TABLES_KEPT = 8  # pack tables (ParamStore.repack_all) cached per set of changed parameters ("any" is one of them)
-
-
-class ParamStore:
-    """All parameters of a module in one flat fp32 buffer; gradients likewise.
-
-    ``param.data`` becomes a view of ``flat`` (checkpoints / state_dict keep working); gradients are
-    accumulated by the kernels into ``flat_grad``, on which the fused AdamW step and the RCCL
-    all-reduce operate directly (``attach_grads`` exposes them as ``param.grad`` views).
-    """
-
-    _serial = __import__("itertools").count(1)
-
-    def __init__(self, module: torch.nn.Module):
-        params = [p for p in module.parameters()]
-        if not params:
-            raise ValueError("module has no parameters")
-        params = self._with_contiguous_groups(module, params)
-        dev = params[0].device
-        if dev.type != "cuda":
-            raise RuntimeError("ParamStore needs the module on the GPU (call .to('cuda') first)")
-        self.params = params
-        offs, n = [], 0
-        for p in params:
-            offs.append(n)
-            n += (p.numel() + 3) // 4 * 4  # 16-byte aligned slices
-        self.numel = n
-        self.offsets = offs
-        self.flat = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.flat_grad = torch.zeros(n, dtype=torch.float32, device=dev)
-        with torch.no_grad():
-            for p, o in zip(params, offs):
-                view = self.flat[o:o + p.numel()].view(p.shape)
-                view.copy_(p.data)
-                p.data = view
-        self.version = 0  # bumped whenever parameter values change (invalidates packed weights)
-        # process-unique serial: caches key their validity on it (CPython may hand a rebuilt store the id() of a dead one,
-        # and a cached VIEW of the old flat buffer would then be used silently -- ADVICE r4)
-        self.uid = next(ParamStore._serial)
-        self._sig = self._signature()
-        self._base = self.flat.data_ptr()
-        self._packs: T.List[T.Tuple] = []  # (PackFormat, dst tensor, w ptr, T, K, N, sk, sn, st): every registered copy
-        self.packed_version = self.version  # the parameter values the registered copies hold (repack_all)
-        # parameters written since the last repack: None = any of them (a full repack), else a set of indices (the
-        # optimizer step of a model with frozen parameters writes the trainable ones only)
-        self._dirty: T.Optional[T.FrozenSet[int]] = None
-        # dirty set -> [(batched entry point, device table, records)] of its repack, most recently used last
-        self._tables: T.Dict[T.Optional[T.FrozenSet[int]], T.List[T.Tuple[str, torch.Tensor, int]]] = {}
-
-    @staticmethod
-    def _with_contiguous_groups(module: torch.nn.Module, params: T.List[torch.nn.Parameter]) -> T.List[torch.nn.Parameter]:
-        """Registration order with the members of every declared group made adjacent (at the place of the group's first
-        member). A submodule declares groups through ``cn_contiguous_params()`` -> lists of parameters that one kernel
-        reads / writes as ONE tensor (the three 128 -> 3 head convolutions of a tower: one 128 -> 9 convolution on the
-        views, no concatenated copies of weights or gradients). Members must be multiples of 4 elements (the store pads
-        every slice to 16 bytes: a padded member would break adjacency)."""
-        first_of, member = {}, set()
-        for m in module.modules():
-            fn = getattr(m, "cn_contiguous_params", None)
-            if fn is None:
-                continue
-            for grp in fn():
-                grp = list(grp)
-                if len(grp) < 2 or any(q.numel() % 4 for q in grp) or any(id(q) in member for q in grp):
-                    continue
-                first_of[id(grp[0])] = grp
-                member.update(id(q) for q in grp)
-        if not first_of:
-            return params
-        out = []
-        for q in params:
-            if id(q) in first_of:
-                out.extend(first_of[id(q)])
-            elif id(q) not in member:
-                out.append(q)
-        assert len(out) == len(params)
-        return out
-
-    def owns(self, module: torch.nn.Module) -> bool:
-        lo, hi = self._base, self._base + self.numel * 4
-        first, last = self.params[0], self.params[-1]
-        return lo <= first.data_ptr() < hi and lo <= last.data_ptr() < hi
-
-    def grad_of(self, p: torch.Tensor) -> torch.Tensor:
-        """Gradient slice matching a parameter (or any dense view of one) inside the flat buffer."""
-        o = (p.data_ptr() - self._base) // 4
-        if o < 0 or o + p.numel() > self.numel:
-            raise RuntimeError("tensor is not part of this ParamStore (was the module moved or re-created?)")
-        return self.flat_grad[o:o + p.numel()].view(p.shape)
-
-    def attach_grads(self) -> None:
-        """Point every ``param.grad`` at its slice of the flat gradient (for torch optimizers driving the NATIVE step).
-        Not for drop-in mode: autograd_bridge hands the flat buffer itself to autograd at every backward (p.grad then
-        IS a view of that step's buffer) and gives the store a fresh one, so views attached here would go stale."""
-        for p, o in zip(self.params, self.offsets):
-            p.grad = self.flat_grad[o:o + p.numel()].view(p.shape)
-
-    def zero_grad(self) -> None:
-        _lib.call("cn_fill_f32", self.flat_grad.data_ptr(), self.numel, 0.0, _stream())
-
-    def bump(self, changed: T.Optional[T.Sequence[bool]] = None) -> None:
-        """The parameter values changed. ``changed``: mask (one flag per parameter, store order) of the parameters
-        that did; None = any may have. Packed copies of the others are not refreshed."""
-        self.version += 1
-        if changed is None:
-            self._dirty = None
-        elif self._dirty is not None:
-            self._dirty = self._dirty | frozenset(i for i, c in enumerate(changed) if c)
-
-    def trainable_mask(self) -> T.Tuple[bool, ...]:
-        """``requires_grad`` of every parameter in store order: the trainable set (frozen parameters get no gradient)."""
-        return tuple(p.requires_grad for p in self.params)
-
-    def _signature(self) -> int:
-        """Sum of the parameters' torch version counters: moves whenever anything outside the engine writes a
-        parameter in place (torch optimizers in drop-in mode, ``load_state_dict`` / ``load_from_checkpoint`` through
-        nn.Module's recursion, ``param.data.copy_``). The engine's own kernels (fused AdamW) do not touch it and call
-        ``bump()`` themselves."""
-        return sum(p._version for p in self.params)
-
-    def refresh(self) -> None:
-        """Invalidate the packed weight copies if the parameters were modified behind the engine's back."""
-        sig = self._signature()
-        if sig != self._sig:
-            self._sig = sig
-            self.bump()
-
-    def register_pack(self, fmt: PackFormat, dst: torch.Tensor, w: torch.Tensor, T_: int, K: int, N: int, sk: int,
-                      sn: int, st: int) -> None:
-        self._packs.append((fmt, dst, w.data_ptr(), T_, K, N, sk, sn, st))
-        self._tables.clear()  # (they list the copies registered so far)
-
-    def _build_tables(self, dirty: T.Optional[T.FrozenSet[int]]) -> T.List[T.Tuple[str, torch.Tensor, int]]:
-        """The descriptor tables that refresh the copies of the parameters in ``dirty``: bf16 first, then fp32 (the
-        order recorded plans hold), none for a precision without records."""
-        spans = []
-        for (_fmt, _dst, wptr, T_, K, N, *_strides) in self._packs:
-            lo = (wptr - self._base) // 4
-            spans.append((lo, lo + T_ * K * N))
-        chosen = [self._packs[i] for i in select_packs(self.offsets, spans, dirty)]
-        tables = []
-        for fmt in (PACK_BF16, PACK_F32):
-            recs = [fmt.record(wptr, dst.data_ptr(), *dims) for (f, dst, wptr, *dims) in chosen if f is fmt]
-            if recs:
-                table = torch.frombuffer(bytearray(b"".join(recs)), dtype=torch.uint8).clone().to(self.flat.device)
-                tables.append((fmt.batched, table, len(recs)))
-        return tables
-
-    def repack_all(self) -> None:
-        """Refresh the registered packed weight copies with ONE launch per precision (after the parameters changed):
-        every copy, or -- when only known parameters changed (bump with a mask) -- the copies of those."""
-        dirty = self._dirty
-        self._dirty = frozenset()
-        self.packed_version = self.version
-        tables = self._tables.pop(dirty, None)
-        if tables is None:
-            tables = self._build_tables(dirty)
-        self._tables[dirty] = tables  # most recently used last; a few trainable sets are kept (gradual unfreezing)
-        while len(self._tables) > _SUB_TABLES_KEPT:
-            self._tables.pop(next(iter(self._tables)))
-        for sink in getattr(_state, "alloc_sinks", None) or ():  # a plan being recorded bakes the table pointers in:
-            sink.extend(t for (_name, t, _n) in tables)          # it keeps the tables alive past their eviction
-        for (name, t, n) in tables:
-            _lib.call(name, t.data_ptr(), n, _stream())
-
-
-SEG_CHUNK = 4096  # elements per chunk of the segmented optimizer kernels (CN_SEG_CHUNK in csrc/cn_optim.hip)
-
-
-def trainable_segments(offsets: T.Sequence[int], sizes: T.Sequence[int], trainable: T.Sequence[bool],
-                       steps: T.Sequence[int]) -> T.List[T.Tuple[int, int, int]]:
-    """The runs of trainable parameters in the flat buffer as [(offset, length, step)]: adjacent trainable parameters
-    with equal AdamW step counts merge (across the 16-byte padding between their slices, which is zero in every
-    buffer); a frozen parameter or a different step count starts a new run."""
-    segs: T.List[T.List[int]] = []
-    end = None  # padded end of the previous parameter, when it is trainable
-    for i in sorted(range(len(offsets)), key=lambda k: offsets[k]):
-        o, n = int(offsets[i]), int(sizes[i])
-        if not trainable[i] or n <= 0:
-            end = None
-            continue
-        if end is not None and end == o and segs[-1][2] == int(steps[i]):
-            segs[-1][1] = o + n - segs[-1][0]
-        else:
-            segs.append([o, n, int(steps[i])])
-        end = o + (n + 3) // 4 * 4
-    return [tuple(x) for x in segs]
-
-
-def segment_table(segs: T.Sequence[T.Tuple[int, int, int]]) -> T.Tuple[bytes, int]:
-    """The 24-byte CnSeg records of ``segs`` for cn_*_seg_f32 and the total chunk count."""
-    import struct
-
-    buf, chunk = bytearray(), 0
-    for o, n, st in segs:
-        buf += struct.pack("<qqii", o, n, st, chunk)
-        chunk += (n + SEG_CHUNK - 1) // SEG_CHUNK
-    return bytes(buf), chunk
-
-
-# Launch plans (cultionet_amd/replay.py) bake the raw pointers of the process-wide scratch buffers below into their
-# recorded arguments. Every (re)allocation of one of them bumps this epoch; the plans' keys hold it, so a plan recorded
-# against an older buffer is never replayed (it is re-recorded against the current one).
-_ws_epoch = 0
-
-
-def workspace_epoch() -> int:
-    return _ws_epoch
-
-
-def _bump_ws_epoch() -> None:
-    global _ws_epoch
-    _ws_epoch += 1
-
-
-_CONV_WS_FLOATS = 16 << 20  # split-K partial slices of the implicit-GEMM launches (64 MB, one per process)
-_conv_ws: T.Dict[T.Tuple[str, int], torch.Tensor] = {}
-
-
-def _bind_conv_workspace(dev: torch.device) -> None:
-    """Register a split-K scratch buffer for the CURRENT stream (the library keys its scratch by stream, so model
-    instances running on different streams / autograd worker threads never share one)."""
-    s = _stream()
-    key = (str(dev), s)
-    if key in _conv_ws:
-        return
-    ws = torch.empty(_CONV_WS_FLOATS, dtype=torch.float32, device=dev)
-    _conv_ws[key] = ws
-    _bump_ws_epoch()
-    _lib.call("cn_conv_set_workspace", s, ws.data_ptr(), ws.numel())
-    # CN_AUTOTUNE=1: measure the (tile, K split) candidates per conv shape during the first steps instead of
-    # trusting the launch-cost model (+0.5 % at batch 8; off by default so that runs are reproducible)
-    _lib.call("cn_conv_set_autotune", 1 if os.environ.get("CN_AUTOTUNE", "0") == "1" else 0)
-
-
-def current_store() -> ParamStore:
-    st = getattr(_state, "store", None)
-    if st is None:
-        raise RuntimeError("no active ParamStore (ops on parameters must run inside a model forward)")
-    return st
-
-
-class using_store:
-    def __init__(self, store: ParamStore):
-        self.store = store
-
-    def __enter__(self):
-        self.prev = getattr(_state, "store", None)
-        _state.store = self.store
-        self.prev_stream = (getattr(_state, "main_stream", None), getattr(_state, "main_handle", None))
-        if self.store.flat.is_cuda:
-            ms = torch.cuda.current_stream()
-            _state.main_stream, _state.main_handle = ms, ms.cuda_stream
-        _bind_conv_workspace(self.store.flat.device)
-        return self.store
-
-    def __exit__(self, *exc):
-        _state.store = self.prev
-        _state.main_stream, _state.main_handle = self.prev_stream
-        return False
-
-
-def pgrad(p: torch.nn.Parameter) -> torch.Tensor:
-    return current_store().grad_of(p)
-
-
-# ---------------------------------------------------------------------------
-# packed weights cache (re-packed when the store version changes)
-# ---------------------------------------------------------------------------
-
-class PackedWeight:
-    """Packed copies of one weight tensor for the implicit-GEMM kernels (forward / bwd-data)."""
-
-    __slots__ = ("fwd", "bwd", "fwd16", "bwd16", "version", "store_id")
-
-    def __init__(self):
-        self.fwd = None
-        self.bwd = None
-        self.fwd16 = None  # bf16 MFMA-fragment copies (mixed-precision path)
-        self.bwd16 = None
-        self.version = -1
-        self.store_id = 0
-
-
-def _pack(fmt: PackFormat, w: torch.Tensor, T_: int, K: int, N: int, sk: int, sn: int, st: int) -> torch.Tensor:
-    """Pack now (first use) into a persistent buffer and register it for the batched per-step repack."""
-    out = _alloc(fmt.elems(T_, K, N), fmt.dtype, w.device)
-    _lib.call(fmt.pack, w.data_ptr(), out.data_ptr(), T_, K, N, sk, sn, st, _stream())
-    current_store().register_pack(fmt, out, w, T_, K, N, sk, sn, st)
-    return out
-
-
-def _bwd_data_dims(T_: int, K: int, N: int, sk: int, sn: int, st: int) -> T.Tuple[int, int, int, int, int, int]:
-    """The backward-data copy of a weight is the forward copy (T, K, N, sk, sn, st) with K and N exchanged."""
-    return (T_, N, K, sn, sk, st)
-
-
-def _pack_copies(fmt: PackFormat, w: torch.Tensor, fwd: T.Optional[torch.Tensor], bwd: T.Optional[torch.Tensor],
-                 need_bwd: bool, *dims: int) -> T.Tuple[torch.Tensor, T.Optional[torch.Tensor]]:
-    """(forward, backward-data) copies of ``w`` in one format: those given, the missing ones packed from the forward
-    ``dims`` (the backward-data copy only when asked for)."""
-    if fwd is None:
-        fwd = _pack(fmt, w, *dims)
-    if need_bwd and bwd is None:
-        bwd = _pack(fmt, w, *_bwd_data_dims(*dims))
-    return fwd, bwd
-
-
-def _sync_packs(pw: "PackedWeight") -> None:
-    """Bring all registered packed weights up to date if the parameters changed since the last pack."""
-    st = current_store()
-    if pw.store_id != st.uid:  # parameters were re-flattened into a new store: drop copies of the old one
-        pw.fwd = pw.bwd = pw.fwd16 = pw.bwd16 = None
-        pw.store_id = st.uid
-    if st.packed_version != st.version:
-        st.repack_all()
-
-
-def _holder(mod) -> PackedWeight:
-    """The module's PackedWeight (created at first use), its registered copies current."""
-    pw = mod.__dict__.get("_cn_packed")
-    if pw is None:
-        pw = PackedWeight()
-        mod.__dict__["_cn_packed"] = pw
-    _sync_packs(pw)
-    return pw
-
-
-def _fill(pw: PackedWeight, w: torch.Tensor, need_bwd: bool, bf16: bool, *dims: int) -> PackedWeight:
-    """The holder with the copies of one precision that a caller needs (forward ``dims``)."""
-    if bf16:
-        pw.fwd16, pw.bwd16 = _pack_copies(PACK_BF16, w, pw.fwd16, pw.bwd16, need_bwd, *dims)
-    else:
-        pw.fwd, pw.bwd = _pack_copies(PACK_F32, w, pw.fwd, pw.bwd, need_bwd, *dims)
-    return pw
-
-
-def packed_conv(mod, need_bwd: bool, bf16: bool = False) -> PackedWeight:
-    """Packed weights of an nn.Conv2d / nn.Linear-like module (weight [Cout][Cin][KH][KW])."""
-    w = mod.weight
-    cout, cin = w.shape[0], w.shape[1]
-    taps = int(w[0, 0].numel()) if w.dim() > 2 else 1
-    return _fill(_holder(mod), w, need_bwd, bf16, taps, cin, cout, taps, cin * taps, 1)
-
-
-def packed_convT(mod, need_bwd: bool, bf16: bool = False, taps_as_channels: bool = False) -> PackedWeight:
-    """Packed weights of an nn.ConvTranspose2d (weight [Cin][Cout][KH][KW]). ``taps_as_channels`` (fp32, stride >=
-    kernel size, _conv_transpose2d_taps): the tensor as the [Cin][Cout*KH*KW] matrix of a 1x1 transposed convolution."""
-    w = mod.weight
-    cin, cout = w.shape[0], w.shape[1]
-    taps = int(w[0, 0].numel())
-    if taps_as_channels and not bf16:
-        n = cout * taps
-        return _fill(_holder(mod), w, need_bwd, False, 1, cin, n, n, 1, 0)
-    return _fill(_holder(mod), w, need_bwd, bf16, taps, cin, cout, cout * taps, taps, 1)
+from . import _lib, runtime
+# The infrastructure the ops stand on, bottom layer first; each module imports only from those above it. Their names are
+# re-bound here so that ``engine.<name>`` keeps resolving for the rest of the package, the tools and the tests.
+from .runtime import (  # noqa: F401
+    _alloc, alloc, _alloc_like, _aux_stream, _aux_streams, bf16_enabled, branch_streams, branch_streams_allowed,
+    bstride, _check, _dense16, _dense_inner, holding_allocations, _HW_QUEUE_BUDGET, _hw_queue_cap, is16,
+    join_side_stream, _KeepAlive, _keepalive, ld, _main_stream, mixed_precision, _new, new_buffer,
+    overlap_wgrad, _priority_stream, _py_op, _rows, _side_state, side_stream, side_stream_event, _side_streams,
+    _state, _stream)
+from .params import (  # noqa: F401
+    _bind_conv_workspace, _bump_ws_epoch, _bwd_data_dims, _conv_ws, _CONV_WS_FLOATS, current_store, _fill,
+    _holder, _pack, PACK_BF16, _pack_copies, PACK_F32, _pack_record_bf16, _pack_record_f32, packed_conv,
+    packed_convT, PackedWeight, PackFormat, ParamStore, pgrad, SEG_CHUNK, segment_table, select_packs,
+    _SUB_TABLES_KEPT, _sync_packs, trainable_segments, using_store, workspace_epoch)
+from .scratch import (  # noqa: F401
+    _bn_group_ws16, _bn_ws16, _bng_ws, deferring_slice_sums, flush_slice_sums, _grown, _pad_ws, _pretime_ws,
+    _pt_ws, _SliceSums, _SS_BLOCK, _SS_CAP, _SS_FLUSH_FLOATS, _ss_state, _sum_stream, _ws16, _WS16_MAX_FLOATS,
+    _WS_FLOATS, _zeroed_scratch)
+from .tape import (  # noqa: F401
+    aux_stream_events, begin_branch_backward, _Branch, current_tape, give_grad, grad_buffer, join, recording,
+    release_branches, _req, spawn, Tape, _tr, Var)
+
+
+def __getattr__(name: str):
+    """``_OVERLAP_WGRAD`` and ``_recorder`` are rebound at run time and live in ``runtime``: a copy bound here at import
+    would go stale, so reads of ``engine.<flag>`` are forwarded (PEP 562)."""
+    if name in ("_OVERLAP_WGRAD", "_recorder"):
+        return getattr(runtime, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 # ---------------------------------------------------------------------------
 # ops
 # ---------------------------------------------------------------------------
-
-def _new(shape, like: torch.Tensor) -> torch.Tensor:
-    if like.dtype == torch.bfloat16 and len(shape) == 4:
-        B, C, H, W = shape
-        return _alloc((B, H, W, C), torch.bfloat16, like.device).permute(0, 3, 1, 2)
-    return _alloc(shape, torch.float32, like.device)
-
-
-def new_buffer(shape, like: torch.Tensor) -> torch.Tensor:
-    """An activation buffer of logical shape [B,C,H,W] in ``like``'s precision / layout (fp32 NCHW or bf16 NHWC)."""
-    return _new(tuple(shape), like)
-
-
-def _rows(t: torch.Tensor) -> int:
-    return t.shape[0] * t.shape[2] * t.shape[3]
-
-
-_WS_FLOATS = 16 << 20  # persistent weight-gradient scratch (64 MB): aligned operand copies + partial dW slices
-
-
-# ---------------------------------------------------------------------------
-# deferred weight-gradient slice sums (csrc/cn_slicesum.h)
-# ---------------------------------------------------------------------------
-# A many-split weight gradient leaves partial dW slices in scratch; `dW += sum(slices)` is needed by the optimizer (or by
-# the gradient bucket's all-reduce), not by the next backward node. During a backward pass the library appends those
-# sums to a table instead of launching them (34 fp32 / 68 bf16 dependent launches per step), and ONE batched launch per
-# flush -- per ready bucket under data parallelism, else one per step -- adds them all. Since the slices must survive
-# until then, every weight-gradient call of the pass takes its scratch from an arena that only moves forward.
-# CN_DEFER_SUMS=0: the sums run right behind their contraction as in rounds 1-4.
-_DEFER_SUMS = os.environ.get("CN_DEFER_SUMS", "1") != "0"
-_SS_CAP = 512            # records per backward pass (64 bytes each)
-_SS_BLOCK = 64 << 20     # floats per arena block (256 MB)
-# Pending slices are summed as soon as this many floats are waiting (CN_SUM_FLUSH_MB, default 128 MB): they are then
-# still in the 256 MB Infinity Cache, and the pass does not end with ONE 0.6 GB reduction behind the last weight gradient
-# on the stream that finishes last (fp32, same box: all-at-the-end 386.4 chips/s against 387.5 with the 34 immediate
-# sums). 0 = only the final flush.
-_SS_FLUSH_FLOATS = int(float(os.environ.get("CN_SUM_FLUSH_MB", "128")) * (1 << 20) / 4)
-
-
-class _SliceSums:
-    """Per-device state of the deferred sums: pinned host table the library writes, its device copy, the arena."""
-
-    def __init__(self, dev: torch.device):
-        self.dev = dev
-        self.host = torch.zeros(_SS_CAP * 64, dtype=torch.uint8).pin_memory()
-        self.table = torch.zeros(_SS_CAP * 64, dtype=torch.uint8, device=dev)
-        self.uploaded: T.Dict[T.Tuple[int, int], bytes] = {}  # record range -> bytes the device copy holds for it
-        self.upload_ev = torch.cuda.Event()                    # (re-)recorded behind every table upload
-        self.writer: T.Any = None    # the launch plan that rewrote the host table last (None: an eager pass)
-        self.blocks: T.List[torch.Tensor] = []
-        self.active = False
-        self.reset()
-
-    def reset(self) -> None:
-        self.cur, self.off, self.seen, self.flushed, self.pending = 0, 0, 0, 0, 0
-
-    def _commit(self) -> None:
-        """Move the arena past the slices of the records appended since the last call (a call whose sum was not
-        deferred leaves nothing behind: its scratch is reused by the next call, as stream order allows)."""
-        n = _lib.query("cn_slice_sums_count")
-        if n <= self.seen or not self.blocks:
-            return
-        import struct
-
-        raw = bytes(self.host[self.seen * 64:n * 64].numpy())
-        base = self.blocks[self.cur].data_ptr()
-        for i in range(n - self.seen):
-            part, _dw, stride, _n, nslices = struct.unpack_from("<QQqqi", raw, i * 64)
-            end = (part - base) // 4 + stride * nslices
-            if 0 <= end <= self.blocks[self.cur].numel():
-                self.off = max(self.off, (end + 63) // 64 * 64)
-            self.pending += stride * nslices
-        self.seen = n
-
-    def take(self, need: int) -> T.Tuple[int, int]:
-        self._commit()
-        if 0 < _SS_FLUSH_FLOATS <= self.pending:
-            flush_slice_sums()
-        need = int(need)
-        while True:
-            if self.cur >= len(self.blocks):
-                # (no workspace-epoch bump: a block that is ADDED moves nothing a recorded plan points at)
-                self.blocks.append(torch.empty(max(_SS_BLOCK, need), dtype=torch.float32, device=self.dev))
-            blk = self.blocks[self.cur]
-            if blk.numel() - self.off >= need:
-                return blk.data_ptr() + 4 * self.off, need
-            if self.off == 0:  # an oversized request in front of a standard block
-                torch.cuda.synchronize(self.dev)
-                self.blocks[self.cur] = torch.empty(need, dtype=torch.float32, device=self.dev)
-                _bump_ws_epoch()
-                continue
-            self.cur, self.off = self.cur + 1, 0
-
-
-def _ss_state() -> T.Optional[_SliceSums]:
-    """The active deferral state of this thread (None: sums run immediately)."""
-    return getattr(_state, "slice_sums", None)
-
-
-def _sum_stream() -> int:
-    """Handle of the stream every weight gradient of the pass runs on (the side stream, or the compute stream when the
-    overlap is off): the batched sums are stream-ordered behind the contractions that wrote their slices."""
-    if _OVERLAP_WGRAD:
-        return _side_state(_main_stream().device)["stream"].cuda_stream
-    return _stream()
-
-
-class deferring_slice_sums:
-    """Context manager around one backward pass: weight-gradient slice sums into ``store.flat_grad`` are collected and
-    run by flush_slice_sums() (called on exit, and by the data-parallel bucket logic before a bucket is reduced)."""
-
-    def __init__(self, store: "ParamStore"):
-        self.store = store
-        self.on = False
-
-    def __enter__(self):
-        if not _DEFER_SUMS or _ss_state() is not None or not self.store.flat_grad.is_cuda:
-            return self
-        # One state PER STORE (tables, arena): a launch plan recorded for one trainer bakes these addresses in, and a
-        # second trainer of the process (tests run an eager and a replayed one side by side) must not rewrite them.
-        st = getattr(self.store, "_slice_sums", None)
-        if st is None:
-            st = self.store._slice_sums = _SliceSums(self.store.flat_grad.device)
-        if st.active:  # a pass over this store is already collecting (another thread): that one keeps the arena
-            return self
-        st.reset()
-        st.active = True
-        # the library is about to rewrite the host table: an upload still in flight (enqueued by the previous eager pass,
-        # or by a replayed plan, which re-records the event) must have read it first
-        if not st.upload_ev.query():
-            st.upload_ev.synchronize()
-        if _recorder is None:
-            st.writer = None
-        _state.slice_sums = st
-        _lib.call("cn_slice_sums_begin", st.host.data_ptr(), _SS_CAP, self.store.flat_grad.data_ptr(),
-                  self.store.numel)
-        self.on = True
-        return self
-
-    def __exit__(self, *exc):
-        if self.on:
-            try:
-                if exc[0] is None:
-                    flush_slice_sums()
-            finally:
-                _lib.call("cn_slice_sums_end")
-                _state.slice_sums.active = False
-                _state.slice_sums = None
-        return False
-
-
-def flush_slice_sums() -> None:
-    """ONE launch adding every pending slice sum into the flat gradient, on the weight gradients' stream."""
-    st = _ss_state()
-    if st is None:
-        return
-    st._commit()
-    n = _lib.query("cn_slice_sums_count")
-    first = st.flushed
-    if n <= first:
-        return
-    now = st.host.numpy().reshape(-1, 64)[first:n, :60].tobytes()  # (without the block dealing the run call writes)
-    # a recorded plan always refreshes the device copy: eager steps in between (other shapes) may have changed it
-    upload = 0 if (st.uploaded.get((first, n)) == now and _recorder is None) else 1
-    sobj = _side_state(st.dev)["stream"] if _OVERLAP_WGRAD else _main_stream()
-    stream = _sum_stream()
-    _lib.call("cn_slice_sums_run", st.host.data_ptr(), st.table.data_ptr(), first, n - first, upload, stream)
-    if upload:  # the device copy of every overlapping range is no longer what `uploaded` says
-        for k in [k for k in st.uploaded if k[0] < n and first < k[1]]:
-            del st.uploaded[k]
-        st.uploaded[(first, n)] = now
-        _py_op(st.upload_ev.record, sobj)  # (a plan entry too: the next eager pass waits for a replay's upload)
-    st.pending = 0
-    st.flushed = n
-    # every slice handed out so far has been consumed by a launch that is now enqueued on the weight gradients' stream,
-    # and whatever takes scratch next runs behind it on the same stream: the arena starts over (ADVICE r5: it used to
-    # grow to the whole pass's slices, ~0.6 GB per fp32 step, and never shrank)
-    st.cur, st.off = 0, 0
-
-
-def _pad_ws(*tensors: torch.Tensor) -> T.Tuple[T.Optional[int], int]:
-    """(pointer, floats) of the weight-gradient scratch: room for aligned copies of odd-sized operands plus the
-    partial-dW slices of many-split launches. One persistent buffer per device (launches are stream-ordered)."""
-    need = _WS_FLOATS
-    for t in tensors:
-        H, W = t.shape[-2], t.shape[-1]
-        if (H * W) % 4 or (W & 1):
-            need += t.shape[0] * t.shape[1] * (H * (W + 1) + 3)
-    dev = tensors[0].device
-    ss = _ss_state()
-    if ss is not None:  # deferred slice sums: this call's slices must outlive the next call
-        return ss.take(need)
-    pool = getattr(_state, "ws_pool", None)
-    if pool is None:
-        pool = _state.ws_pool = {}
-    ws = pool.get(dev)
-    if ws is None or ws.numel() < need:
-        if ws is not None:  # growing: the old buffer may still be read by launches in flight on the side stream
-            torch.cuda.synchronize(dev)
-        ws = pool[dev] = torch.empty(need, dtype=torch.float32, device=dev)
-        _bump_ws_epoch()
-    return ws.data_ptr(), ws.numel()
-
 
 def conv2d(x: Var, mod, stride: int = 1, padding: int = 0, dilation: int = 1, out: T.Optional[torch.Tensor] = None,
            want_stats: bool = False, bn=None) -> Var:
@@ -1351,8 +118,6 @@ def conv2d_group(xs: T.Sequence[Var], mods: T.Sequence, paddings: T.Sequence[int
     """G (<= 4) nn.Conv2d of identical shapes (per-conv padding / dilation) in ONE implicit-GEMM launch -- the
     dilation branches of ResidualAConv. ``xs`` may repeat one Var (branches sharing their input: backward sums the
     G input gradients in the same launch). Weight gradients stay one launch per conv."""
-    import ctypes
-
     tape = current_tape()
     G = len(mods)
     xts = [_check(x.t) for x in xs]
@@ -1635,7 +400,7 @@ def time_conv(x: Var, mod, tin: int) -> Var:
                               dwexp.data_ptr(), B, CT, H, W, Cout * tout, 1, 1, 1, 0, 1, None, 0, s)
                     _lib.call("cn_fold_timeconv_grad_f32", dwexp.data_ptr(), store.grad_of(w).data_ptr(), Cout, Cin,
                               tin, k, s)
-                    if _OVERLAP_WGRAD:
+                    if runtime._OVERLAP_WGRAD:
                         dwexp.record_stream(_side_state(xt.device)["stream"])
             s = _stream()
             if x.req:
@@ -1648,34 +413,9 @@ def time_conv(x: Var, mod, tin: int) -> Var:
     return yv
 
 
-_pt_ws: T.Dict[T.Tuple, torch.Tensor] = {}
 # The fused PreTimeReduction family (csrc/cn_pretime.hip) serves training and inference (forward 3
 # launches / 1 in eval mode instead of ~20, backward 3 instead of ~20; same-box A/B in round 4 against the op-by-op
 # path: bf16 batch 32 at parity, fp32 batch 8 +1 %, 32 / 29 launches fewer per step).
-
-
-def _zeroed_scratch(n: int, dev: torch.device) -> torch.Tensor:
-    """A scratch buffer whose ticket-counter head must be zero before its first launch, zeroed ON THE STREAM THAT WILL
-    USE IT. ``torch.zeros`` fills on torch's current (compute) stream, but these buffers are keyed to the
-    weight-gradient side stream or an auxiliary stream, which had only waited for an event recorded BEFORE the
-    allocation: the fill raced the first ticketed kernel. ``cn_fill_f32`` on ``_stream()`` is ordered by construction;
-    a recycled block is safe because that stream already waits for everything the compute stream enqueued earlier."""
-    ws = torch.empty(n, dtype=torch.float32, device=dev)
-    _lib.call("cn_fill_f32", ws.data_ptr(), n, 0.0, _stream())
-    return ws
-
-
-def _pretime_ws(need: int, dev: torch.device) -> torch.Tensor:
-    """Scratch of the fused PreTimeReduction calls, one per (device, stream): zero-filled once (ticket counters at its
-    head; every launch leaves them zero)."""
-    key = (dev, _stream())
-    ws = _pt_ws.get(key)
-    if ws is None or ws.numel() < need:
-        if ws is not None:
-            torch.cuda.synchronize(dev)
-        ws = _pt_ws[key] = _zeroed_scratch(need, dev)
-        _bump_ws_epoch()
-    return ws
 
 
 def pretime_reduction(x: Var, pre, in_channels: int, in_time: int) -> T.Optional[Var]:
@@ -1684,8 +424,6 @@ def pretime_reduction(x: Var, pre, in_channels: int, in_time: int) -> T.Optional
     training, 1 in inference, 3 backward on the compute stream: the stage has parameter gradients only).
     Writes fp32 NCHW, or bf16 NHWC directly when the mixed-precision region is on. Returns None for shapes / settings the
     fused kernels do not cover (the caller keeps the generic op-by-op path)."""
-    import ctypes
-
     tape = current_tape()
     xt = _check(x.t)
     if is16(xt) or x.req or not xt.is_contiguous():
@@ -1860,8 +598,6 @@ def bn_act_group(xs: T.Sequence[Var], bns: T.Sequence, act: int, residual: T.Opt
     """G BatchNorm2d(+act) over G same-shaped tensors in one launch pair. ``sum_outputs``: returns the single Var
     ``residual + sum_g act(bn_g(x_g))`` (the ResUNet-a sum, accumulated in the order of the sequential form);
     otherwise the list of G activations."""
-    import ctypes
-
     tape = current_tape()
     G = len(xs)
     xts = [_check(x.t) for x in xs]
@@ -2027,17 +763,13 @@ def na2d(qkv: Var, heads: int, kernel_size: int, dilation: int, attn_drop: float
             if do is None:
                 return
             dattn = _alloc_like(attn)
+            dq = _new(qt.shape, qt)
+            _lib.call("cn_na2d_bwd_f32", qt.data_ptr(), bstride(qt), do.data_ptr(), bstride(do), attn.data_ptr(),
+                      dattn.data_ptr(), dq.data_ptr(), bstride(dq), B, C, heads, H, W, kernel_size, dilation,
+                      float(attn_drop), _bwd_seed(seed, step_fwd), stepw, _stream())
             if qkv.grad is None:
-                dq = _new(qt.shape, qt)
-                _lib.call("cn_na2d_bwd_f32", qt.data_ptr(), bstride(qt), do.data_ptr(), bstride(do), attn.data_ptr(),
-                          dattn.data_ptr(), dq.data_ptr(), bstride(dq), B, C, heads, H, W, kernel_size, dilation,
-                          float(attn_drop), _bwd_seed(seed, step_fwd), stepw, _stream())
                 qkv.grad = dq
             else:  # pragma: no cover - qkv has a single consumer in TowerUNet
-                dq = _new(qt.shape, qt)
-                _lib.call("cn_na2d_bwd_f32", qt.data_ptr(), bstride(qt), do.data_ptr(), bstride(do), attn.data_ptr(),
-                          dattn.data_ptr(), dq.data_ptr(), bstride(dq), B, C, heads, H, W, kernel_size, dilation,
-                          float(attn_drop), _bwd_seed(seed, step_fwd), stepw, _stream())
                 give_grad(qkv, dq)
             ov.grad = None
 
@@ -2351,8 +1083,6 @@ def add(a: Var, b: Var) -> Var:
 
 
 def _ptr_table(ptrs: T.Sequence[int]):
-    import ctypes
-
     return (ctypes.c_void_p * len(ptrs))(*ptrs)
 
 
@@ -2491,8 +1221,6 @@ def tanimoto_loss_multi(preds: T.Sequence[Var], terms: T.Sequence[T.Dict[str, T.
     tanimoto_loss()'s keyword arguments for head h (target_f / labels / mask / target_mode / mask_mode / klass). Returns
     the n per-head batch means (device tensor); ``total`` (1 element) is WRITTEN with sum_h weights[h] * loss_h. The one
     tape node writes weights[h] * dL_h/dpred_h into every head's gradient."""
-    import struct
-
     tape = current_tape()
     n = len(preds)
     if not 1 <= n <= 4:
@@ -2662,35 +1390,6 @@ def adaptive_max_pool2d(x: Var, size: T.Tuple[int, int]) -> Var:
 # ---------------------------------------------------------------------------
 # mixed-precision (bf16 NHWC) op bodies: activations / activation gradients bf16, parameters + statistics fp32
 # ---------------------------------------------------------------------------
-_WS16_MAX_FLOATS = 96 << 20  # cap of the weight-gradient scratch (384 MB); the pixel split shrinks to fit
-
-
-def _ws16(need: int, dev: torch.device, pool_name: str = "wgrad") -> T.Tuple[int, int]:
-    """(pointer, floats) of a persistent fp32 scratch of the bf16 kernels. One buffer per (device, purpose): the
-    weight-gradient slices live on the side stream, BatchNorm partial sums on the main stream."""
-    need = int(min(max(need, 1 << 20), _WS16_MAX_FLOATS))
-    if pool_name == "wgrad":
-        ss = _ss_state()
-        if ss is not None:  # deferred slice sums: this call's slices must outlive the next call
-            return ss.take(need)
-    pool = getattr(_state, "ws16_pool", None)
-    if pool is None:
-        pool = _state.ws16_pool = {}
-    # ("wgrad" / "side" live on the ONE weight-gradient stream; every other pool belongs to the stream that launches)
-    key = (dev, pool_name) if pool_name in ("wgrad", "side") else (dev, pool_name, getattr(_state, "stream_override", None))
-    ws = pool.get(key)
-    if ws is None or ws.numel() < need:
-        if ws is not None:  # growing: the old buffer may still be in use by launches in flight on either stream
-            torch.cuda.synchronize(dev)
-        # zero-filled: the single-launch reductions keep their ticket counters in the first words of these buffers
-        # (zero on entry, left zero on exit)
-        ws = pool[key] = _zeroed_scratch(need, dev)
-        _bump_ws_epoch()
-    return ws.data_ptr(), ws.numel()
-
-
-def _bn_ws16(C: int, dev: torch.device, pool_name: str = "bn") -> int:
-    return _ws16(_lib.query("cn_bn_workspace_floats_bf16", C), dev, pool_name)[0]
 
 
 def to_bf16(x: Var) -> Var:
@@ -2764,8 +1463,6 @@ def _bnstats_launch(xts, pws, ys, B, Cin, H, W, Cout, KH, KW, stride, paddings, 
     tiles, finishes them (mean / rstd / running statistics) by a last-block ticket -- the dependent finalize launch between
     the convolution and the BatchNorm apply disappears. Returns per-output (bn, mean, rstd) or None when the launch only
     wrote the rows."""
-    import ctypes
-
     G = len(xts)
     dev = xts[0].device
     tab = lambda ptrs: (ctypes.c_void_p * G)(*ptrs)
@@ -2861,8 +1558,6 @@ def _conv2d_group_bf16(xs: T.Sequence[Var], mods: T.Sequence, paddings: T.Sequen
     Backward: weight gradients conv by conv on the side stream; data gradients in one grouped launch when the G inputs
     are distinct tensors (second level), conv by conv when they share their input (first level: the second launch
     accumulates -- a grouped launch would race on the shared dx)."""
-    import ctypes
-
     tape = current_tape()
     G = len(mods)
     xts = [x.t for x in xs]
@@ -3077,28 +1772,9 @@ def _bn_act_bf16(x: Var, bn, act: int, residual: T.Optional[Var], training: bool
     return _bn_act_group_bf16([x], [bn], act, residual, True, training, [out] if out is not None else None)
 
 
-_bng_ws: T.Dict[T.Tuple, torch.Tensor] = {}
-
-
-def _bn_group_ws16(G: int, C: int, dev: torch.device) -> int:
-    """Scratch of the grouped BatchNorm calls on the COMPUTE stream (launches are stream-ordered): ticket counters
-    (zeroed ONCE here; every launch leaves them zero), finalize slices, backward coefficients, partial rows."""
-    need = int(_lib.query("cn_bn_group_workspace_floats_bf16", G, C))
-    key = (dev, _stream())
-    ws = _bng_ws.get(key)
-    if ws is None or ws.numel() < need:
-        if ws is not None:
-            torch.cuda.synchronize(dev)
-        ws = _bng_ws[key] = _zeroed_scratch(max(need, 1 << 20), dev)
-        _bump_ws_epoch()
-    return ws.data_ptr()
-
-
 def _bn_act_group_bf16(xs: T.Sequence[Var], bns: T.Sequence, act: int, residual: T.Optional[Var], sum_outputs: bool,
                        training: bool, outs: T.Optional[T.Sequence[torch.Tensor]]) -> T.Union[Var, T.List[Var]]:
     """bn_act_group in bf16, for layers one grouped launch serves (checked by the callers: bn_act_group, _bn_act_bf16)."""
-    import ctypes
-
     tape = current_tape()
     G = len(xs)
     xts = [x.t for x in xs]

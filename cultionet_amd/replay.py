@@ -25,7 +25,7 @@ import typing as T
 
 import torch
 
-from . import _lib
+from . import _lib, runtime
 from . import engine as E
 
 
@@ -126,13 +126,13 @@ def forward(model, x: torch.Tensor, bf16: bool, run: T.Callable[[torch.Tensor], 
         plan.x = torch.empty_like(x)
         plan.x.copy_(x)
         _lib.call = recording
-        prev_rec = E._recorder
-        E._recorder = plan.calls  # engine._py_op appends (1, fn, args): stream operations in program order
+        prev_rec = runtime._recorder
+        runtime._recorder = plan.calls  # runtime._py_op appends (1, fn, args): stream operations in program order
         try:
             outs = run(plan.x)
         finally:
             _lib.call = orig
-            E._recorder = prev_rec
+            runtime._recorder = prev_rec
         plan.outputs = dict(outs)
     if E.workspace_epoch() != epoch0:  # a scratch buffer moved while recording: stale pointers, do not keep the plan
         return plan.outputs
@@ -153,7 +153,7 @@ def forward(model, x: torch.Tensor, bf16: bool, run: T.Callable[[torch.Tensor], 
 # is ~2.5-4 ms of GPU work behind ~9.8 ms of Python (the tape, ~470 C-ABI calls, ~2400 small torch calls): host-bound.
 # The same recording trick as above, with what a training step adds:
 #   * two streams: the weight-gradient side stream's event record / wait calls and the final join are part of the plan
-#     (engine._py_op), in program order;
+#     (runtime._py_op), in program order;
 #   * NO buffer is reused inside a recorded step. The caching allocator makes cross-stream reuse safe EAGERLY by looking
 #     at events when a block is freed; a replay has no such check, so a block that held a weight gradient's operand and
 #     was later handed to the compute stream would be a race. While recording, every tensor torch hands out is kept alive
@@ -179,7 +179,7 @@ class StepPlan:
         self.outputs: T.Optional[T.Dict[str, torch.Tensor]] = None
         self.key = None
         self.n_calls = 0
-        self.sums = None  # the store's deferred-slice-sum state (engine._SliceSums) whose host table this plan rewrites
+        self.sums = None  # the store's deferred-slice-sum state (scratch._SliceSums) whose host table this plan rewrites
         # the phase the plan was recorded for (gradient accumulation): a micro-step that continues a group adds to the
         # gradients already there, and its plan holds neither a zero-fill of the flat gradient nor a weight repack
         self.accumulates = False
@@ -197,7 +197,7 @@ def step_key(trainer, batch) -> tuple:
     if mask is None:
         mask = trainer.store.trainable_mask()
     return (tuple(x.shape), x.dtype, tuple(y.shape), y.dtype, tuple(bd.shape), bd.dtype, trainer.bf16, trainer.store.uid,
-            str(trainer.lit.loss_name), torch.cuda.current_stream(x.device).cuda_stream, E._OVERLAP_WGRAD,
+            str(trainer.lit.loss_name), torch.cuda.current_stream(x.device).cuda_stream, runtime._OVERLAP_WGRAD,
             E.workspace_epoch(), E.branch_streams_allowed(), mask, bool(getattr(trainer, "_accumulating", False)))
 
 
@@ -253,12 +253,12 @@ def record_step(trainer, batch, eager: T.Callable) -> StepPlan:
         if not plan.accumulates:
             trainer.store.bump(mask if partial else None)
         _lib.call = recording
-        E._recorder = ops
+        runtime._recorder = ops
         try:
             with E.holding_allocations(plan.keep):  # every buffer the engine hands out lives as long as the plan
                 eager(pb)
         finally:
-            E._recorder = None
+            runtime._recorder = None
             _lib.call = orig_call
     plan.outputs = dict(trainer.last_outputs)
     plan.sums = getattr(trainer.store, "_slice_sums", None)

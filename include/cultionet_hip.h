@@ -705,7 +705,7 @@ int cn_slice_sums_end(void);
 int cn_slice_sums_run(void* host_table, void* dev_table, int first, int n, int upload, void* stream);
 
 /* ---- runtime plumbing: streams torch cannot create ---------------------------------------------------
- * The training step issues weight gradients on a second stream (engine.py side_stream; the reference has no
+ * The training step issues weight gradients on a second stream (runtime.py side_stream; the reference has no
  * counterpart: torch.autograd runs one stream). That stream must not starve the data-gradient chain:
  * cn_stream_create(priority) = hipStreamCreateWithPriority (out[0] = least, out[1] = greatest of
  * cn_stream_priority_range), or with cu_mask != NULL hipExtStreamCreateWithCUMask (bit i = CU i). */

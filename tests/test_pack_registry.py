@@ -78,11 +78,11 @@ def test_backward_data_exchange(monkeypatch):
     tuple derived from it, against the tuples written out per layer kind."""
     import torch
 
-    from cultionet_amd import engine as E
+    from cultionet_amd import engine as E, params
 
-    calls = []
-    monkeypatch.setattr(E, "_pack", lambda fmt, w, *dims: calls.append((fmt, dims)) or torch.empty(0))
-    monkeypatch.setattr(E, "_holder", lambda mod: E.PackedWeight())  # (no store: nothing is registered)
+    calls = []  # (packed_conv / packed_convT look _pack and _holder up where they live: cultionet_amd/params.py)
+    monkeypatch.setattr(params, "_pack", lambda fmt, w, *dims: calls.append((fmt, dims)) or torch.empty(0))
+    monkeypatch.setattr(params, "_holder", lambda mod: E.PackedWeight())  # (no store: nothing is registered)
 
     def packed(fn, mod, **kw):
         del calls[:]

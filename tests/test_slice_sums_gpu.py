@@ -91,8 +91,7 @@ def test_step_gradients_with_and_without_deferral(precision, monkeypatch):
     """The whole training step on the same weights and batch, sums deferred (default) vs immediate: the flat gradient
     identical up to the float atomics of the few-split launches (1e-5 of the gradient's scale), and the reduction
     launches really gone."""
-    from cultionet_amd import _lib
-    from cultionet_amd import engine as E
+    from cultionet_amd import _lib, scratch
     from cultionet_amd.data import Data
     from cultionet_amd.lightning import HipTrainer
     from oracle import towerunet_oracle as O
@@ -106,7 +105,7 @@ def test_step_gradients_with_and_without_deferral(precision, monkeypatch):
     trainer = HipTrainer(lit, precision=precision)
     out = {}
     for mode in (False, True, False, True):  # (twice each: the second pass of a mode reuses its arena / table)
-        monkeypatch.setattr(E, "_DEFER_SUMS", mode)
+        monkeypatch.setattr(scratch, "_DEFER_SUMS", mode)  # (read where it lives: cultionet_amd/scratch.py)
         _lib.query("cn_launch_count", 1)
         loss = trainer.forward_backward(batch)
         torch.cuda.synchronize()
