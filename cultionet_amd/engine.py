@@ -1065,7 +1065,9 @@ def add(a: Var, b: Var) -> Var:
                 return
             give_grad(a, dy)
             if b.req:
-                if b.grad is None:  # never let two Vars alias one gradient buffer
+                # never let two Vars alias one gradient buffer; a channel slice has no buffer of its own: give_grad
+                # adds dy into its parent's gradient
+                if b.grad is None and b.parent is None:
                     cp = _new(dy.shape, dy)
                     if is16(dy):
                         _lib.call("cn_copy_bf16", dy.data_ptr(), ld(dy), cp.data_ptr(), ld(cp), _rows(dy), dy.shape[1],
