@@ -21,7 +21,8 @@ _DTYPES = {torch.float32: 0, torch.int32: 1, torch.int16: 2, torch.uint16: 3}
 
 def prepare_chips(x_raw: torch.Tensor, mean: T.Optional[torch.Tensor] = None, std: T.Optional[torch.Tensor] = None,
                   scale: float = 1.0 / SCALE_FACTOR, lo: float = 1e-9, hi: float = 1.0) -> torch.Tensor:
-    """x_raw: [B, C, T, H, W] on the GPU (f32 / i32 / i16 / u16); mean/std: per-channel [C] (or broadcastable)."""
+    """x_raw: [B, C, T, H, W] on the GPU (f32 / i32 / i16 / u16); mean / std: exactly C values each (any shape), each
+    optional on its own: the kernel indexes both by channel."""
     if not x_raw.is_cuda:
         raise RuntimeError("prepare_chips needs a device tensor")
     if x_raw.dtype not in _DTYPES:
@@ -34,6 +35,8 @@ def prepare_chips(x_raw: torch.Tensor, mean: T.Optional[torch.Tensor] = None, st
     s = std.to(device=x_raw.device, dtype=torch.float32).reshape(-1).contiguous() if std is not None else None
     if m is not None and m.numel() != C:
         raise ValueError("mean must hold one value per channel")
+    if s is not None and s.numel() != C:
+        raise ValueError("std must hold one value per channel")
     _lib.call("cn_prepare_chips_f32", x_raw.data_ptr(), _DTYPES[x_raw.dtype], out.data_ptr(),
               m.data_ptr() if m is not None else None, s.data_ptr() if s is not None else None, B, C, L, float(scale),
               float(lo), float(hi), _stream())
@@ -42,10 +45,25 @@ def prepare_chips(x_raw: torch.Tensor, mean: T.Optional[torch.Tensor] = None, st
 
 def predictions_to_uint16(prediction: T.Dict[str, torch.Tensor], padding: int, height: int, width: int,
                           scale: float = SCALE_FACTOR) -> torch.Tensor:
-    """{distance, edge, crop}: [B,1,H,W] -> uint16 [B,3,height,width] with the window padding removed."""
-    d, e, c = (prediction[k].contiguous() for k in ("distance", "edge", "crop"))
-    B, _, H, W = d.shape
+    """{distance, edge, crop}: [B,1,H,W] device maps of one shape, fp32 or a narrower float type (the bf16-mixed forward
+    returns bf16 maps; they are widened to fp32 first) -> uint16 [B,3,height,width] with the window padding removed."""
+    maps = [prediction[k] for k in ("distance", "edge", "crop")]
+    for k, t in zip(("distance", "edge", "crop"), maps):
+        if not t.is_cuda:
+            raise ValueError(f"predictions_to_uint16 needs device tensors, {k} is on {t.device}")
+        if not t.is_floating_point():
+            raise ValueError(f"{k} must be a floating-point map, got {t.dtype}")
+        if t.dim() != 4 or t.shape[1] != 1:
+            raise ValueError(f"{k} must be [B, 1, H, W], got {tuple(t.shape)}")
+        if t.shape != maps[0].shape or t.device != maps[0].device:
+            raise ValueError(f"{k} is {tuple(t.shape)} on {t.device}, distance is {tuple(maps[0].shape)} on "
+                             f"{maps[0].device}")
+    B, _, H, W = maps[0].shape
+    padding, height, width = int(padding), int(height), int(width)
+    if padding < 0 or height < 0 or width < 0 or padding + height > H or padding + width > W:
+        raise ValueError(f"padding {padding} + window {height} x {width} does not fit the {H} x {W} maps")
+    d, e, c = (t.float().contiguous() for t in maps)
     out = torch.empty((B, 3, height, width), dtype=torch.uint16, device=d.device)
-    _lib.call("cn_predictions_to_u16", d.data_ptr(), e.data_ptr(), c.data_ptr(), out.data_ptr(), B, H, W, int(padding),
-              int(padding), int(height), int(width), float(scale), _stream())
+    _lib.call("cn_predictions_to_u16", d.data_ptr(), e.data_ptr(), c.data_ptr(), out.data_ptr(), B, H, W, padding,
+              padding, height, width, float(scale), _stream())
     return out

@@ -8,8 +8,9 @@ on the CPU by tests/test_pointwise_ref.py. Plain torch / numpy: no GPU, no impor
   maximum; torch.amax for the channel maximum: gradient split evenly among ties).
 * final_combine_ref: TowerUNetFinalCombine + SigmoidCrisp from the formula in the header of
   cn_final_combine_fwd_kernel.
-* window_chips_ref / stitch_ref: numpy restatements of cn_window_chips_f32 / cn_stitch_predictions_u16. Every step is
-  one IEEE fp32 operation with one rounding, so these are bit-exact, not approximate.
+* window_chips_ref / stitch_ref / prepare_chips_ref / predictions_u16_ref: numpy restatements of cn_window_chips_f32 /
+  cn_stitch_predictions_u16 / cn_prepare_chips_f32 / cn_predictions_to_u16. Every step is one IEEE fp32 operation with
+  one rounding, so these are bit-exact, not approximate.
 """
 from __future__ import annotations
 
@@ -298,6 +299,52 @@ def window_chips_ref(scene, win_rc, T, S, pad, mean, std, scale, lo, hi):
         v = np.fmin(np.fmax(v, f(lo)), f(hi))
         out[n] = ((v - m[:, None, None]).astype(np.float32) * inv[:, None, None]).astype(np.float32)
     return out
+
+
+def prepare_chips_ref(x, mean, std, scale, lo, hi):
+    """x: numpy [B][C][...] of float32 / int32 / int16 / uint16; mean / std: float32 [C] or None, each on its own.
+    cn_prepare_chips_f32 step by step, every step one IEEE fp32 operation with one rounding: x.astype(f32) * f32(scale),
+    fmin(fmax(v, lo), hi) (a NaN clips to lo, as fmaxf), (v - mean[c]) * (f32(1) / std[c]). float32, the shape of x.
+
+    Bit-exact against the kernel, NOT against the reference's (x / 10000).clip(1e-9, 1), (. - mean) / std: the rounded
+    constant 1e-4 and the reciprocal-multiply move about a quarter of all values in their last bits.
+    tests/test_pointwise_ref.py bounds that distance."""
+    f = np.float32
+    x = np.asarray(x)
+    per_c = (1, x.shape[1]) + (1,) * (x.ndim - 2)
+    v = (x.astype(np.float32) * f(scale)).astype(np.float32)
+    v = np.fmin(np.fmax(v, f(lo)), f(hi))
+    if mean is not None:
+        v = (v - np.asarray(mean, dtype=np.float32).reshape(per_c)).astype(np.float32)
+    if std is not None:
+        v = (v * (f(1) / np.asarray(std, dtype=np.float32).reshape(per_c)).astype(np.float32)).astype(np.float32)
+    return v
+
+
+def predictions_u16_ref(dist, edge, crop, pad_top, pad_left, h, w, scale):
+    """dist / edge / crop: float32 [B][1][H][W] (or [B][H][W]). cn_predictions_to_u16: the arithmetic of stitch_ref for
+    one window per sample -- drop the padding, * scale in float32, clip to [0, scale] (a NaN clips to 0), truncate.
+    uint16 [B][3][h][w]."""
+    f = np.float32
+    B = np.asarray(dist).shape[0]
+    out = np.zeros((B, 3, h, w), dtype=np.uint16)
+    for k, src in enumerate((dist, edge, crop)):
+        s = np.asarray(src, dtype=np.float32)
+        s = s.reshape(B, s.shape[-2], s.shape[-1])
+        v = (s[:, pad_top:pad_top + h, pad_left:pad_left + w] * f(scale)).astype(np.float32)
+        v = np.fmin(np.fmax(v, f(0)), f(scale))
+        out[:, k] = v.astype(np.uint16)
+    return out
+
+
+def count_neighbours(n, seed, scale=10000.0):
+    """n float32 probabilities on and next to integer counts: k / scale for random k in 0..scale, a third of them moved
+    to the fp32 neighbour below and a third to the one above (the values of test_stitch_predictions_u16_bit_exact)."""
+    rng = np.random.default_rng(seed)
+    v = (rng.integers(0, int(scale) + 1, n) / scale).astype(np.float32)
+    step = rng.integers(-1, 2, n)
+    v = np.where(step < 0, np.nextafter(v, np.float32(-1)), np.where(step > 0, np.nextafter(v, np.float32(2)), v))
+    return v.astype(np.float32)
 
 
 def stitch_ref(dist, edge, crop, win_rc, S, pad, ws, H, W, scale):

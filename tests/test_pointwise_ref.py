@@ -201,6 +201,99 @@ def test_stitch_ref_matches_scalar_loops():
     assert got[1, 4 + 1, 0 + 1] == 0  # the NaN
 
 
+@pytest.mark.parametrize("zscore", [True, False])
+def test_prepare_chips_ref_distance_from_the_reference_arithmetic(zscore):
+    """prepare_chips_ref (the kernel's arithmetic) against the reference's literal torch lines,
+    (x / 10000).clip(1e-9, 1) and (. - mean) / std, over the full int16 range under 256 (mean, std) pairs.
+
+    Bit equality with the reference is NOT the contract: the kernel multiplies by the rounded constant 1e-4 and by the
+    rounded reciprocal of std, and about a quarter of all values differ from the reference in their last bits. The
+    contract is the distance: with u = 2^-24 and v, m, s the clipped value, mean and std in float64,
+        |kernel - reference| <= u (3 |v| + 6 |v - m|) / s        (3 u |v| without the z-score),
+    from: the rounded 1e-4 and one product against one division (3 u |v| into v, carried through the subtraction),
+    one subtraction on each side (2 u |v - m|), the rounded reciprocal and one product against one division
+    (3 u |v - m|), and one more u |v - m| for the second-order terms."""
+    C = 256
+    x = np.broadcast_to(np.arange(-32768, 32768, dtype=np.int16), (1, C, 65536)).copy()
+    rng = np.random.default_rng(12)
+    mean = (rng.random(C) * 0.5).astype(np.float32) if zscore else None
+    std = (rng.random(C) * 0.3 + 0.02).astype(np.float32) if zscore else None
+    got = R.prepare_chips_ref(x, mean, std, 1.0 / 10000.0, 1e-9, 1.0)
+    xt = torch.from_numpy(x)
+    ref = (xt / 10_000.0).clip(1e-9, 1)
+    assert ref.dtype == torch.float32
+    v = np.clip(x.astype(np.float64) / 10000.0, 1e-9, 1.0)
+    if zscore:
+        ref = (ref - torch.from_numpy(mean).view(1, C, 1)) / torch.from_numpy(std).view(1, C, 1)
+        m, s = mean.astype(np.float64).reshape(1, C, 1), std.astype(np.float64).reshape(1, C, 1)
+        bound = U * (3 * np.abs(v) + 6 * np.abs(v - m)) / s
+    else:
+        bound = 3 * U * np.abs(v)
+    ref = ref.numpy()
+    err = np.abs(got.astype(np.float64) - ref.astype(np.float64))
+    ratio = float((err / bound).max())
+    differ = float((got.view(np.uint32) != ref.view(np.uint32)).mean())
+    print(f"BOUND prepare_chips_ref vs reference arithmetic zscore={zscore}: worst err/bound {ratio:.3f} over {got.size} "
+          f"values, {100 * differ:.1f} % differ in their bits")
+    assert ratio <= 1.0
+    if zscore:
+        assert differ > 0.0  # the restatement is the kernel's arithmetic, not the reference's
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.int32, np.int16, np.uint16])
+def test_prepare_chips_ref_matches_scalar_loops(dtype):
+    """Against a scalar loop of the kernel's statements, mean and std each on its own; NaN clips to lo."""
+    f = np.float32
+    rng = np.random.default_rng(13)
+    if dtype == np.float32:
+        x = rng.normal(2000, 6000, (2, 3, 7)).astype(dtype)
+        x[0, 1, :5] = [np.nan, np.inf, -np.inf, 0.0, -0.0]
+    elif dtype == np.uint16:
+        x = rng.integers(0, 65536, (2, 3, 7)).astype(dtype)
+    else:
+        x = rng.integers(-32768, 32768, (2, 3, 7)).astype(dtype)
+    mean, std = np.array([0.21, 0.3, 0.0], dtype=np.float32), np.array([0.11, 0.07, 3.0], dtype=np.float32)
+    for m, s in ((mean, std), (mean, None), (None, std), (None, None)):
+        got = R.prepare_chips_ref(x, m, s, 1e-4, 1e-9, 1.0)
+        want = np.zeros(x.shape, dtype=np.float32)
+        for b, c, l in np.ndindex(*x.shape):
+            v = f(f(x[b, c, l]) * f(1e-4))
+            v = f(1e-9) if np.isnan(v) else min(max(v, f(1e-9)), f(1.0))
+            want[b, c, l] = f(f(v - (f(0) if m is None else m[c])) * (f(1) if s is None else f(f(1) / s[c])))
+        assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    if dtype == np.float32:
+        assert R.prepare_chips_ref(x, None, None, 1e-4, 1e-9, 1.0)[0, 1, 0] == f(1e-9)
+
+
+def _writer_line(stack, scale=10_000.0):
+    """callbacks.py:220 on the float32 numpy stack, then the cast of the uint16 raster it is written to."""
+    return (stack * scale).clip(0, scale).astype(np.uint16)
+
+
+def test_predictions_u16_ref_equals_the_reference_writer():
+    """array_equal to the reference writer's numpy line on random probabilities around [0, 1], on every k / 10000 and
+    on both fp32 neighbours of each; then the slicing: unequal pads, three different maps, three samples."""
+    rng = np.random.default_rng(14)
+    k = (np.arange(10001) / 10000.0).astype(np.float32)
+    values = np.concatenate([rng.uniform(-0.1, 1.1, 1 << 20).astype(np.float32), k, np.nextafter(k, np.float32(-1)),
+                             np.nextafter(k, np.float32(2)), np.array([-0.25, 1.5, 7.0, -0.0], dtype=np.float32)])
+    n = values.size
+    maps = [np.roll(values, s).reshape(1, 1, 1, n) for s in (0, 1, 2)]
+    got = R.predictions_u16_ref(maps[0], maps[1], maps[2], 0, 0, 1, n, 10000.0)
+    want = np.stack([_writer_line(m.reshape(1, 1, n)) for m in maps], 1)
+    assert got.dtype == np.uint16 and got.shape == (1, 3, 1, n) and np.array_equal(got, want)
+    assert (got == 10000).any() and (got == 0).any()
+    B, H, W, pt, pl, h, w = 3, 17, 19, 3, 5, 12, 14
+    maps = [R.count_neighbours(B * H * W, 15 + i).reshape(B, 1, H, W) for i in range(3)]
+    got = R.predictions_u16_ref(maps[0], maps[1], maps[2], pt, pl, h, w, 10000.0)
+    want = np.stack([_writer_line(m[:, 0, pt:pt + h, pl:pl + w]) for m in maps], 1)
+    assert np.array_equal(got, want)
+    assert not np.array_equal(got, R.predictions_u16_ref(maps[0], maps[1], maps[2], pl, pt, h, w, 10000.0))
+    nan = maps[1].copy()
+    nan[2, 0, pt, pl] = np.nan
+    assert R.predictions_u16_ref(maps[0], nan, maps[2], pt, pl, h, w, 10000.0)[2, 1, 0, 0] == 0  # as fmaxf
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # bf16 spatial-channel attention / max pool: the per-element bounds can fail
 # ---------------------------------------------------------------------------------------------------------------------

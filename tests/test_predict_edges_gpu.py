@@ -87,6 +87,14 @@ def test_sliding_window_predict_bf16_mixed_vs_restatement(pack):
         assert d.mean() <= 60, d.mean()
 
 
+def _prologue_ref(raw, mean, std):
+    """tests/pointwise_ref.prepare_chips_ref at the prologue's constants, as a CPU tensor."""
+    import pointwise_ref as R
+
+    as_np = lambda t: None if t is None else t.cpu().numpy()
+    return torch.from_numpy(R.prepare_chips_ref(as_np(raw), as_np(mean), as_np(std), 1.0 / 10_000.0, 1e-9, 1.0))
+
+
 def test_collate_and_device_prologue():
     from cultionet_amd.data import Data, collate_fn
     from cultionet_amd.lightning import CultionetLitModel
@@ -110,6 +118,9 @@ def test_collate_and_device_prologue():
     assert (out.x.cpu() - want).abs().max() <= 1e-6
     wb = (batch.bdist.float() / 10000.0).clip(1e-9, 1)
     assert (out.bdist.cpu() - wb).abs().max() <= 1e-7
+    # and bit for bit the kernel's own arithmetic (tests/pointwise_ref.py), which every augmenter test builds on
+    assert torch.equal(out.x.cpu(), _prologue_ref(batch.x, mean, std))
+    assert torch.equal(out.bdist.cpu(), _prologue_ref(batch.bdist.unsqueeze(1), None, None).squeeze(1))
     pred = lit.eval()(out)  # the prepared batch feeds the forward
     assert pred["distance"].shape == (3, 1, 20, 20)
 
@@ -146,6 +157,8 @@ def test_device_feeder_double_buffers_raw_batches():
         assert (b.x.cpu() - ref).abs().max() <= 1e-5
         assert torch.equal(b.y.cpu(), h.y)
         assert (b.bdist.cpu() - (h.bdist.float() / 10_000.0).clip(1e-9, 1)).abs().max() <= 1e-6
+        assert torch.equal(b.x.cpu(), _prologue_ref(h.x, mean, std))
+        assert torch.equal(b.bdist.cpu(), _prologue_ref(h.bdist.unsqueeze(1), None, None).squeeze(1))
         seen += 1
     assert seen == len(hosts)
     assert list(feeder.iterate([])) == []
