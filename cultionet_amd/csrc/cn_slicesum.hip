@@ -14,9 +14,10 @@ bool cn_ss_push(const CnSliceSum* js, int n) {
   for (int k = 0; k < n; ++k) {
     if (js[k].nslices <= 0 || js[k].n <= 0) return false;
     if (js[k].dw < cn_ss_lo || js[k].dw + js[k].n > cn_ss_hi) return false;  // a temporary dW is consumed at once
-    // two pending records must never accumulate into the same dW from different blocks of one launch
+    // two pending records must never accumulate into the same floats from different blocks of one launch: neither
+    // into the same dW nor into ranges that only overlap
     for (int i = 0; i < cn_ss_count; ++i)
-      if (cn_ss_sink[i].dw == js[k].dw) return false;
+      if (js[k].dw < cn_ss_sink[i].dw + cn_ss_sink[i].n && cn_ss_sink[i].dw < js[k].dw + js[k].n) return false;
   }
   for (int k = 0; k < n; ++k) {
     // chunk0 (the record's last word) belongs to cn_slice_sums_run. A table upload of the previous step may still be

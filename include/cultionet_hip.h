@@ -698,7 +698,7 @@ long cn_launch_count(int reset);
  * cn_slice_sums_run: ONE launch summing records [first, first+n) (its blocks are dealt to the records on the
  * host; that is written into host_table); dev_table = device copy of the table, refreshed from host_table for
  * that range when upload != 0 (async on `stream`; upload == 0 asserts it already holds this range, dealt alike). Deterministic summation order; a record whose
- * dW already has a pending record is refused by the sink (that call reduces immediately, as without a sink). */
+ * dW is, or overlaps, the dW of a pending record is refused by the sink (that call reduces immediately, as without a sink). */
 int cn_slice_sums_begin(void* host_table, int capacity, const float* dw_lo, long dw_floats);
 int cn_slice_sums_count(void);
 int cn_slice_sums_end(void);
