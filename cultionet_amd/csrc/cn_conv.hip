@@ -7,7 +7,8 @@
 //   * Conv2d backward-data      (autograd of the above; stride>1 handled as s*s parity classes)
 //   * ConvTranspose2d forward   (convolution.py:45-68; s*s parity classes, no zero-stuffing)
 //   * ConvTranspose2d backward-data
-//   * 1x1 convs / the NA qkv+proj Linear layers (convolution.py:341-350) as T=1 taps.
+//   * grouped 1x1 convs as T=1 taps (single 1x1 convs and the NA qkv+proj Linear layers, convolution.py:341-350, run
+//     on the plain-GEMM family cn_gemm1x1_kernel further down).
 //
 // Mapping (im2col-free): a block owns MT consecutive flattened grid pixels of one
 // image and NT output channels. Per K-chunk of 8 input channels it stages the
@@ -977,82 +978,173 @@ static int cn_launch_dword_cfg(const float* x, const float* wp, const float* bia
 }
 
 // --------------------------------------------------------------------------
-// 1x1 convolutions of large pixel counts (skip convs of the tower blocks, qkv / proj of the 100x100 attention) as a
-// plain GEMM  y[co][p] = sum_ci wp[ci][co] x[ci][p]: no halo, so a K-chunk of 32 channels is staged densely
-// ([32][NT] weights + [32][MT] pixels = 36 KB) and there are 4x fewer barriers per MFMA than the 8-channel chunks
-// of the tap kernels give a single-tap layer.
+// 1x1 convolutions (skip convs of the tower blocks, qkv / proj of the attention, the taps-as-channels GEMM of the
+// stride-4 ConvTranspose2d) as a plain GEMM  y[co][p] = sum_ci wp[ci][co] x[ci][p],  forward and data gradient, for
+// every plane size: no halo, so both operands are k-major rows of contiguous floats and a K-chunk of KCH channels is
+// staged densely -- [KCH][NT] weights and [KCH][MT] pixels -- by LDS-DMA into a ring of LDS buffers. The next chunks' loads
+// are in flight while the MFMAs of the current one run, and there is one barrier per chunk. Outputs are finished by the
+// launch itself: parallelism comes from the M x N tiling alone (tiles down to 32 x 32 on one wave), never from a K
+// split, so there are no slices and no reduce launch.
+//   WN x WM waves of TM 32x32 accumulators each: the tile is NT = 32*WN couts x MT = 32*WM*TM pixels.
+//   STG: how the pixel operand is staged.
+//     CN_G1_ALIGNED  16-byte pieces; needs 16-byte aligned channel rows (HW % 4 == 0, batch stride % 4 == 0, aligned base)
+//     CN_G1_ODD      16-byte pieces over ODD planes (HW % 4 == 1: 25x25, 13x13; Cin % 4 == 0, aligned images): row c of a
+//                    tile starts (c % 4) floats past a 16-byte boundary, so it is fetched from its address rounded DOWN
+//                    into an LDS row of pitch MT + 4 and read back at the shift c % 4 -- a chunk starts at a multiple of
+//                    four channels, so the shift of every unrolled k is a constant
+//     CN_G1_DWORD    4-byte pieces: everything else (HW % 4 == 2 or 3, padded batch strides, unaligned bases)
+//   NST: LDS buffers (pipeline stages). Two for the large tiles (two blocks share a CU and hide each other's waits).
+//       The small tiles of the deep-K layers on 25x25 / 13x13 planes live through up to 36 chunks with next to no
+//       MFMA work each, so their time is a chain of load latencies: four buffers keep three chunks in flight. The
+//       barrier is then a counted s_waitcnt vmcnt(N) + s_barrier -- a fence would drain the DMA queue.
+// Rows of wp past Kpad and rows of x past Cin are never read (they stage zeros), nor is anything outside an image.
 // --------------------------------------------------------------------------
 struct CnGemm1x1 {
   int B, Cin, Cout, HW, Kpad, Npad, tiles_per_img, grid_x, grid_y, accumulate;
   long xbs, ybs;
 };
-#define KC1 32
+#define CN_G1_ALIGNED 0
+#define CN_G1_ODD 1
+#define CN_G1_DWORD 2
 
-template <int TM>
-__global__ __launch_bounds__(256) void cn_conv1x1_kernel(const float* __restrict__ x, const float* __restrict__ wp,
-                                                        const float* __restrict__ bias, float* __restrict__ y,
-                                                        const CnGemm1x1 g) {
-  constexpr int MT = TM * 32, NT = 128;
-  constexpr int NA = KC1 * NT / 4 / 256;             // weight float4 per thread per chunk (4)
-  constexpr int NB = (KC1 * MT / 4 + 255) / 256;     // pixel float4 per thread per chunk
-  __shared__ __attribute__((aligned(16))) float a_lds[KC1 * NT];
-  __shared__ __attribute__((aligned(16))) float b_lds[KC1 * MT];
+typedef __attribute__((address_space(3))) void* cn_g1_lds_ptr;
+typedef const __attribute__((address_space(1))) void* cn_g1_gbl_ptr;
+static __device__ float cn_g1_zero[256];  // 1 KiB of zeros: per-lane source of an LDS-DMA piece that must read as zero
+
+// One LDS-DMA wave-instruction: lane l copies BYTES bytes from its own `src` to lds_wave_base + l*BYTES.
+template <int BYTES>
+__device__ __forceinline__ void cn_g1_glds(const float* src, float* lds_wave_base) {
+  if constexpr (BYTES == 16)  // the size must be a literal
+    __builtin_amdgcn_global_load_lds((cn_g1_gbl_ptr)src, (cn_g1_lds_ptr)lds_wave_base, 16, 0, 0);
+  else
+    __builtin_amdgcn_global_load_lds((cn_g1_gbl_ptr)src, (cn_g1_lds_ptr)lds_wave_base, 4, 0, 0);
+}
+
+template <int WN, int WM, int TM, int KCH, int STG, int NST>
+struct CnG1Cfg {
+  static constexpr int NW = WN * WM, NT = WN * 32, MT = WM * TM * 32;
+  static constexpr int VB = STG == CN_G1_DWORD ? 4 : 16;
+  static constexpr int MTP = MT + (STG == CN_G1_ODD ? 4 : 0);  // LDS row pitch of the pixel image
+  static constexpr int BPI = VB == 16 ? 256 : 64;              // floats per DMA wave-instruction of the pixel operand
+  static constexpr int NBI = (KCH * MTP + BPI - 1) / BPI;      // DMA instructions per pixel chunk image
+  static constexpr int BIMG = NBI * BPI;                       // floats per pixel chunk image (whole instructions)
+  static constexpr int AIMG = KCH * NT;
+  static constexpr size_t LDS = sizeof(float) * NST * (AIMG + BIMG);
+};
+
+template <int WN, int WM, int TM, int KCH, int STG, int NST>
+__global__ __launch_bounds__(64 * WN * WM) void cn_gemm1x1_kernel(const float* __restrict__ x,
+                                                                  const float* __restrict__ wp,
+                                                                  const float* __restrict__ bias,
+                                                                  float* __restrict__ y, const CnGemm1x1 g) {
+  using C = CnG1Cfg<WN, WM, TM, KCH, STG, NST>;
+  constexpr int NW = C::NW, NT = C::NT, MT = C::MT, VB = C::VB, MTP = C::MTP, BPI = C::BPI, NBI = C::NBI;
+  constexpr int BIMG = C::BIMG, AIMG = C::AIMG;
+  constexpr int NA = AIMG / 256 / NW;        // weight DMA instructions per wave per chunk (16 bytes per lane)
+  constexpr int NBW = (NBI + NW - 1) / NW;   // pixel DMA instructions per wave per chunk
+  constexpr bool ODD = STG == CN_G1_ODD;
+  static_assert(AIMG % (256 * NW) == 0, "a weight chunk is a whole number of DMA instructions per wave");
+  static_assert(STG != CN_G1_DWORD || (MT & (MT - 1)) == 0, "the dword variant decodes pixels with shifts");
+  // DMA instructions every wave issues per stage at least: what may stay in flight behind the stage being waited for
+  constexpr int INFL = (NST - 2) * (NA + NBI / NW);
+  static_assert(NST >= 2 && INFL < 64, "vmcnt is a 6-bit counter");
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* a_lds = smem;               // [NST][KCH][NT]
+  float* b_lds = smem + NST * AIMG;  // [NST][KCH][MTP]
+
   int bx, by, bz;
   if (!cn_xcd_block(g.grid_x, g.grid_y, g.grid_x * g.grid_y, bx, by, bz)) return;
-  const int tid = threadIdx.x, lane = tid & 63, wn = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int half = lane >> 5, l31 = lane & 31;
+  const int wn = wid % WN, wm = wid / WN;
   const int b = bx / g.tiles_per_img;
   const int p0 = (bx - b * g.tiles_per_img) * MT;
-  const int n0 = by * NT;
   const float* xb = x + (long)b * g.xbs;
+  const float* zero16 = cn_g1_zero + 4 * lane;
+  const float* zerob = cn_g1_zero + (VB == 16 ? 4 : 1) * lane;
+  const int nch = (g.Cin + KCH - 1) / KCH;
+  const long img = (long)g.Cin * g.HW;
+
+  const int n0 = by * NT;
+  // weights: piece p = 16 bytes, row = p / (NT/4) of the chunk, 64 consecutive pieces per instruction
+  auto stage_a = [&](int c0, int buf) {
+    float* dst = a_lds + buf * AIMG;
+#pragma unroll
+    for (int k = 0; k < NA; ++k) {
+      const int inst = wid + NW * k;
+      const int p = inst * 64 + lane;
+      const int row = c0 + p / (NT / 4), c4 = p % (NT / 4);
+      const float* src = row < g.Kpad ? wp + (long)row * g.Npad + n0 + 4 * c4 : zero16;
+      cn_g1_glds<16>(src, dst + inst * 256);
+    }
+  };
+  // pixels: [KCH][MTP]. Aligned / dword pieces lie wholly inside or wholly outside the plane. An ODD row image starts
+  // (row % 4) floats early: its first floats and those past the plane's end are a neighbouring channel's -- never a
+  // valid pixel's operand, and inside the image, whose size is a multiple of four floats.
+  auto stage_b = [&](int c0, int buf) {
+    float* dst = b_lds + buf * BIMG;
+#pragma unroll
+    for (int k = 0; k < NBW; ++k) {
+      const int inst = wid + NW * k;
+      if (NBI % NW == 0 || inst < NBI) {  // wave-uniform
+        const int e = inst * BPI + (VB == 16 ? 4 : 1) * lane;  // float index inside the chunk image
+        const int r = e / MTP, row = c0 + r;
+        const int pix = p0 + e % MTP - (ODD ? (row & 3) : 0);  // plane index of the piece's first float
+        const long f = (long)row * g.HW + pix;
+        bool ok = r < KCH && row < g.Cin && pix < g.HW;
+        if (ODD) ok = ok && f + 3 < img;
+        const float* src = ok ? xb + f : zerob;
+        cn_g1_glds<VB>(src, dst + inst * BPI);
+      }
+    }
+  };
 
   f32x16 acc[TM];
 #pragma unroll
   for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[tm][r] = 0.f;
-
-  f32x4 ra[NA], rb[NB];
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-#define CN_G1_PREFETCH(c0_)                                                                          \
-  {                                                                                                  \
-    const int c0 = (c0_);                                                                            \
-    _Pragma("unroll") for (int k = 0; k < NA; ++k) {                                                 \
-      const int i = tid + k * 256, row = i / (NT / 4), c4 = i - row * (NT / 4);                      \
-      ra[k] = (c0 + row) < g.Kpad                                                                    \
-                  ? *reinterpret_cast<const f32x4*>(wp + (long)(c0 + row) * g.Npad + n0 + c4 * 4)    \
-                  : zero4;                                                                           \
-    }                                                                                                \
-    _Pragma("unroll") for (int k = 0; k < NB; ++k) {                                                 \
-      const int i = tid + k * 256, row = i / (MT / 4), q = i - row * (MT / 4);                       \
-      const int p = p0 + q * 4;                                                                      \
-      rb[k] = (i < KC1 * MT / 4 && (c0 + row) < g.Cin && p < g.HW)                                   \
-                  ? *reinterpret_cast<const f32x4*>(xb + (long)(c0 + row) * g.HW + p)                \
-                  : zero4;                                                                           \
-    }                                                                                                \
-  }
-  const int nchunks = (g.Cin + KC1 - 1) / KC1;
-  CN_G1_PREFETCH(0);
-  for (int ch = 0; ch < nchunks; ++ch) {
-    __syncthreads();
+  // dense k-major rows are what the 32x32x2 fragments want: lanes 0-31 read row 2*k2, lanes 32-63 row 2*k2+1,
+  // 32 consecutive floats each (conflict-free), every offset a DS immediate (ODD: plus the row's shift, (2*k2) % 4 for
+  // the even row and one more for the odd one)
+  auto compute = [&](int buf) {
+    const float* ap = a_lds + buf * AIMG + half * NT + wn * 32 + l31;
+    const float* bp = b_lds + buf * BIMG + half * (MTP + (ODD ? 1 : 0)) + wm * (TM * 32) + l31;
 #pragma unroll
-    for (int k = 0; k < NA; ++k) *reinterpret_cast<f32x4*>(a_lds + (tid + k * 256) * 4) = ra[k];
-#pragma unroll
-    for (int k = 0; k < NB; ++k)
-      if (tid + k * 256 < KC1 * MT / 4) *reinterpret_cast<f32x4*>(b_lds + (tid + k * 256) * 4) = rb[k];
-    __syncthreads();
-    if (ch + 1 < nchunks) CN_G1_PREFETCH((ch + 1) * KC1);
-    const float* ap = a_lds + half * NT + wn * 32 + l31;
-    const float* bp = b_lds + half * MT + l31;
-#pragma unroll
-    for (int k2 = 0; k2 < KC1 / 2; ++k2) {
+    for (int k2 = 0; k2 < KCH / 2; ++k2) {
       const float av = ap[k2 * 2 * NT];
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm)
-        acc[tm] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bp[k2 * 2 * MT + tm * 32], acc[tm], 0, 0, 0);
+        acc[tm] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bp[k2 * 2 * MTP + (ODD ? (2 * k2) & 3 : 0) + tm * 32], acc[tm],
+                                                       0, 0, 0);
     }
+  };
+  // Chunk ch lives in buffer ch % NST. The barrier at the top of step ch -- every wave first waits until at most the
+  // DMA of the NST-2 chunks issued after ch is still in flight, i.e. its own pieces of chunk ch have landed -- says that
+  // all of chunk ch is in LDS AND that every wave is done reading the buffer of step ch-1, which the DMA issued right
+  // after it, for chunk ch+NST-1, overwrites. One asm statement with a memory clobber: no LDS access moves across it.
+#pragma unroll
+  for (int s = 0; s < NST - 1; ++s)
+    if (s < nch) {
+      stage_a(s * KCH, s);
+      stage_b(s * KCH, s);
+    }
+  int buf = 0, nbuf = NST - 1;  // ch % NST, (ch + NST - 1) % NST
+  for (int ch = 0; ch < nch; ++ch) {
+    if (ch + NST - 1 <= nch)  // NST-2 later chunks are in flight (wave-uniform); the tail drains
+      asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(INFL) : "memory");
+    else
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    if (ch + NST - 1 < nch) {
+      stage_a((ch + NST - 1) * KCH, nbuf);
+      stage_b((ch + NST - 1) * KCH, nbuf);
+    }
+    compute(buf);
+    buf = buf + 1 == NST ? 0 : buf + 1;
+    nbuf = nbuf + 1 == NST ? 0 : nbuf + 1;
   }
-#undef CN_G1_PREFETCH
+  // epilogue: bias, accumulate; ragged couts and the pixel tail are masked
   float* yb = y + (long)b * g.ybs;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -1061,7 +1153,7 @@ __global__ __launch_bounds__(256) void cn_conv1x1_kernel(const float* __restrict
       const float bv = bias != nullptr ? bias[co] : 0.f;
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm) {
-        const int p = p0 + tm * 32 + l31;
+        const int p = p0 + wm * (TM * 32) + tm * 32 + l31;
         if (p < g.HW) {
           float* dst = yb + (long)co * g.HW + p;
           const float v = acc[tm][r] + bv;
@@ -1072,33 +1164,80 @@ __global__ __launch_bounds__(256) void cn_conv1x1_kernel(const float* __restrict
   }
 }
 
-// Returns CN_ERR_ARG when the shape is not for this kernel (the caller then takes the tap kernels).
+template <int WN, int WM, int TM, int KCH, int STG, int NST>
+static int cn_gemm1x1_go(const float* x, const float* wp, const float* bias, float* y, CnGemm1x1& g,
+                         hipStream_t stream) {
+  using C = CnG1Cfg<WN, WM, TM, KCH, STG, NST>;
+  g.tiles_per_img = (g.HW + C::MT - 1) / C::MT;
+  g.grid_x = g.B * g.tiles_per_img;
+  g.grid_y = (g.Cout + C::NT - 1) / C::NT;
+  constexpr size_t lds = C::LDS;
+  static_assert(lds <= 160 * 1024, "LDS of one CU");
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)cn_gemm1x1_kernel<WN, WM, TM, KCH, STG, NST>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    attr_set = true;
+  }
+  const double flops = 2.0 * g.B * g.HW * (double)g.Cout * g.Cin;
+  cn_prof_name("cn_gemm1x1_kernel<%d, %d, %d, %d, %d, %d>", WN, WM, TM, KCH, STG, NST);
+  cn_prof_desc("gemm1x1<%dx%d,k%dx%d,%s> B%d %d->%d HW%d grid%dx%d", C::NT, C::MT, KCH, NST,
+               STG == CN_G1_ALIGNED ? "v16" : (STG == CN_G1_ODD ? "odd16" : "v4"), g.B, g.Cin, g.Cout, g.HW, g.grid_x,
+               g.grid_y);
+  cn_prof_before(stream);
+  CN_LAUNCH((cn_gemm1x1_kernel<WN, WM, TM, KCH, STG, NST>), dim3(cn_xcd_grid((long)g.grid_x * g.grid_y)),
+            dim3(64 * WN * WM), lds, stream, x, wp, bias, y, g);
+  cn_prof_after(stream, 0, flops);
+  return cn_check_launch();
+}
+
+// Tile rule (256 CUs; a launch wants at least one block per CU from M x N alone, and the largest tile that gives it):
+//   1. 128 couts x 160 or 128 pixels (four waves, one 32-cout row each), whichever needs fewer rounds x tile at 512
+//      resident blocks; two LDS buffers, two blocks per CU.
+//   2. otherwise 64 x 64 (2 x 2 waves, three buffers), 32 x 64 (two waves) or 32 x 32 (one wave, four buffers each) by
+//      the staging cost below: 50x50 and 25x25 planes take 64 x 64, the 13x13 planes the two small ones; those are
+//      bound by the latency of their few chunks whatever the tile.
+// Odd planes take 128 x 128 instead of 128 x 160 and otherwise the same tiles. The dword staging takes only the tiles of
+// rule 2: sixteen 4-byte DMA instructions per wave and chunk, each with its own uniform LDS address, are more than the
+// 128-wide tile's scalar registers hold without spilling, and such launches (padded batch strides, HW % 4 = 2, 3) are off
+// the training path.
+// Returns CN_ERR_ARG when the shape is not for this family (the caller then takes the tap kernels).
 static int cn_conv1x1_launch(const float* x, long xbs, const float* wp, const float* bias, float* y, long ybs, int B,
                              int Cin, int HW, int Cout, int accumulate, hipStream_t stream) {
-  if ((HW & 3) || (xbs & 3) || (reinterpret_cast<uintptr_t>(x) & 15)) return CN_ERR_ARG;
+  if (B <= 0 || Cin <= 0 || Cout <= 0 || HW <= 0) return CN_ERR_ARG;
+  if (reinterpret_cast<uintptr_t>(wp) & 15) return CN_ERR_ARG;
   CnGemm1x1 g = {};
   g.B = B; g.Cin = Cin; g.Cout = Cout; g.HW = HW; g.xbs = xbs; g.ybs = ybs; g.accumulate = accumulate;
   g.Kpad = cn_conv_kpad(Cin);
   g.Npad = cn_conv_npad(Cout);
-  if (cn_pick_nt(Cout) != 128) return CN_ERR_ARG;
-  g.grid_y = (Cout + 127) / 128;
-  // pixel tile: 160 or 128, whichever needs fewer (rounds x tile) at 512 resident blocks
-  const long t160 = (long)B * ((HW + 159) / 160) * g.grid_y, t128 = (long)B * ((HW + 127) / 128) * g.grid_y;
-  const bool use160 = ((t160 + 511) / 512) * 160 <= ((t128 + 511) / 512) * 128;
-  const long blocks = use160 ? t160 : t128;
-  if (blocks < 256) return CN_ERR_ARG;  // small launches need the K split of the tap kernels
-  g.tiles_per_img = use160 ? (HW + 159) / 160 : (HW + 127) / 128;
-  g.grid_x = B * g.tiles_per_img;
-  const double flops = 2.0 * B * HW * (double)Cout * Cin;
-  cn_prof_name("cn_conv1x1_kernel<%d>", use160 ? 5 : 4);
-  cn_prof_desc("gemm1x1<%d> B%d %d->%d HW%d grid%dx%d", use160 ? 5 : 4, B, Cin, Cout, HW, g.grid_x, g.grid_y);
-  cn_prof_before(stream);
-  if (use160)
-    CN_LAUNCH((cn_conv1x1_kernel<5>), dim3(cn_xcd_grid(blocks)), dim3(256), 0, stream, x, wp, bias, y, g);
-  else
-    CN_LAUNCH((cn_conv1x1_kernel<4>), dim3(cn_xcd_grid(blocks)), dim3(256), 0, stream, x, wp, bias, y, g);
-  cn_prof_after(stream, 0, flops);
-  return cn_check_launch();
+  const bool img16 = !(xbs & 3) && !(reinterpret_cast<uintptr_t>(x) & 15);
+  const int stg = (img16 && (HW & 3) == 0) ? CN_G1_ALIGNED
+                  : (img16 && (HW & 3) == 1 && (Cin & 3) == 0) ? CN_G1_ODD : CN_G1_DWORD;
+  const int nt = cn_pick_nt(Cout);  // Npad is a multiple of it: a cout tile may be this wide or any power of two below
+  auto blocks = [&](int ntile, int mtile) {
+    return (long)B * ((HW + mtile - 1) / mtile) * ((Cout + ntile - 1) / ntile);
+  };
+#define CN_G1_GO(WN_, WM_, TM_, KCH_, NST_)                                                                        \
+  return stg == CN_G1_ALIGNED ? cn_gemm1x1_go<WN_, WM_, TM_, KCH_, CN_G1_ALIGNED, NST_>(x, wp, bias, y, g, stream) \
+         : stg == CN_G1_ODD   ? cn_gemm1x1_go<WN_, WM_, TM_, KCH_, CN_G1_ODD, NST_>(x, wp, bias, y, g, stream)     \
+                              : cn_gemm1x1_go<WN_, WM_, TM_, KCH_, CN_G1_DWORD, NST_>(x, wp, bias, y, g, stream)
+  if (nt == 128 && stg == CN_G1_ALIGNED) {
+    const long t160 = blocks(128, 160), t128 = blocks(128, 128);
+    const bool use160 = ((t160 + 511) / 512) * 160 <= ((t128 + 511) / 512) * 128;
+    if (use160 && t160 >= 256) return cn_gemm1x1_go<4, 1, 5, 32, CN_G1_ALIGNED, 2>(x, wp, bias, y, g, stream);
+    if (!use160 && t128 >= 256) return cn_gemm1x1_go<4, 1, 4, 32, CN_G1_ALIGNED, 2>(x, wp, bias, y, g, stream);
+  }
+  if (nt == 128 && stg == CN_G1_ODD && blocks(128, 128) >= 256)
+    return cn_gemm1x1_go<4, 1, 4, 32, CN_G1_ODD, 2>(x, wp, bias, y, g, stream);
+  // Smaller launches: staging is what such a tile pays for (a block stages NT + MT floats per channel, and every cout
+  // tile stages the pixels again), so the cost of a candidate is rounds on 256 CUs x (NT + MT); ties go to the larger
+  // tile.
+  auto cost = [&](int ntile, int mtile) { return ((blocks(ntile, mtile) + 255) / 256) * (ntile + mtile); };
+  const long c64 = nt >= 64 ? cost(64, 64) : (1L << 60), c32x64 = cost(32, 64), c32 = cost(32, 32);
+  if (c64 <= c32x64 && c64 <= c32) { CN_G1_GO(2, 2, 1, 32, 3); }
+  if (c32x64 <= c32) { CN_G1_GO(1, 2, 1, 32, 4); }
+  CN_G1_GO(1, 1, 1, 32, 4);
+#undef CN_G1_GO
 }
 
 // ---- opt-in autotuning (cn_conv_set_autotune): the first overwriting launch of each distinct shape times the
