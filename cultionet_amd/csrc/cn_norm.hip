@@ -878,13 +878,18 @@ __global__ __launch_bounds__(256) void cn_ln_fwd_reg_kernel(const float* __restr
   const long b = ok ? p / L : 0, l = ok ? p - b * L : 0;
   const int c0 = wid * CPW;
   const float* xp = x + b * xbs + l + (long)c0 * L;
-  float xv[CPW];
+  const float* rp = res ? res + b * rbs + l + (long)c0 * L : nullptr;
+  float xv[CPW], rv[CPW];
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < CPW; ++i) {
     xv[i] = (ok && c0 + i < C) ? xp[(long)i * L] : 0.f;
     s += xv[i];
   }
+  // The residual is fetched here, with x, and held: read next to the stores at the end, each load waited for the store
+  // before it and the launch ran at half the bandwidth of the one without a residual.
+#pragma unroll
+  for (int i = 0; i < CPW; ++i) rv[i] = (rp && ok && c0 + i < C) ? rp[(long)i * L] : 0.f;
   red[0][wid][lane] = s;
   __syncthreads();
   const float m = (red[0][0][lane] + red[0][1][lane] + red[0][2][lane] + red[0][3][lane]) / C;
@@ -903,67 +908,88 @@ __global__ __launch_bounds__(256) void cn_ln_fwd_reg_kernel(const float* __restr
     rstd[p] = rs;
   }
   float* yp = y + b * ybs + l + (long)c0 * L;
-  const float* rp = res ? res + b * rbs + l + (long)c0 * L : nullptr;
 #pragma unroll
   for (int i = 0; i < CPW; ++i) {
     if (c0 + i < C) {
       float o = (xv[i] - m) * rs * w[c0 + i] + bvec[c0 + i];
-      if (rp) o += rp[(long)i * L];
+      if (rp) o += rv[i];
       yp[(long)i * L] = o;
     }
   }
 }
 
-// Backward: tiles of 64 pixels (grid-stride), channels split over the 4 waves and held in registers. The parameter
-// gradients are kept per lane across the block's tiles, reduced once per block and written to the workspace
-// part[block][2][C] (same-address float atomics serialise at ~200 ns each: one per tile and channel was the
-// whole cost of this kernel); cn_ln_param_finalize_kernel sums the partials.
-template <int CPW>
-__global__ __launch_bounds__(256) void cn_ln_bwd_reg_kernel(const float* __restrict__ x, long xbs,
-                                                           const float* __restrict__ dy, long dybs,
-                                                           const float* __restrict__ w, const float* __restrict__ mu,
-                                                           const float* __restrict__ rstd, float* __restrict__ dx,
-                                                           long dxbs, float* __restrict__ part, int B, int C, int L,
-                                                           int accumulate_dx, int ntiles) {
-  __shared__ float red[2][4][64];
+// Backward: tiles of 64 pixels (grid-stride), the channels split over the block's 8 waves (CPW each: 4 / 8 / 16 for
+// C <= 32 / 64 / 128) and held in registers. With 4 waves of 32 channels the kernel held 220 VGPRs, two blocks per
+// CU, and every block ran one tile: load, barrier, store, 64 wave trees, each phase waiting for the one before it with
+// nothing else on the SIMD (1.3 TB/s at 100 x 100). Eight waves of 16 channels hold 128 VGPRs (4 waves per
+// SIMD), and ln_bwd_blocks() gives a block several tiles, so the wave trees run once per block, not once per tile.
+// The old dx of an accumulating launch is fetched with x and dy, not next to the stores (see the forward kernel).
+// The parameter gradients are kept per lane across the block's tiles, reduced once per block and written to the
+// workspace part[block][2][C] (same-address float atomics serialise at ~200 ns each); cn_ln_param_finalize_kernel
+// sums the partials.
+// Lengths of the fp32 chains: per pixel CPW products in a lane, then a tree over the 8 waves (3): CPW + 3. dw / db:
+// ceil(ntiles / nblk) tiles in a lane, the wave tree (6), then the finalize kernel (ceil(nblk / 128) + 8 + 16); at
+// [8, 128, 100, 100] that is 3 + 6 + 4 + 24 = 37.
+#define LN_BWD_WAVES 8
+template <int CPW, bool ACC>  // ACC: dx += the gradient
+__global__ __launch_bounds__(64 * LN_BWD_WAVES) __attribute__((amdgpu_waves_per_eu(4, 8))) void cn_ln_bwd_reg_kernel(
+    const float* __restrict__ x, long xbs, const float* __restrict__ dy, long dybs, const float* __restrict__ w,
+    const float* __restrict__ mu, const float* __restrict__ rstd, float* __restrict__ dx, long dxbs,
+    float* __restrict__ part, int B, int C, int L, int ntiles) {
+  __shared__ float red[2][2][LN_BWD_WAVES][64];  // [tile parity]: one barrier per tile
+  __shared__ float wsh[LN_BWD_WAVES * CPW];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int c0 = wid * CPW;
   float dwacc[CPW], dbacc[CPW];
 #pragma unroll
   for (int i = 0; i < CPW; ++i) dwacc[i] = dbacc[i] = 0.f;
-  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+  if (threadIdx.x < LN_BWD_WAVES * CPW) wsh[threadIdx.x] = threadIdx.x < C ? w[threadIdx.x] : 0.f;
+  __syncthreads();
+  int par = 0;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x, par ^= 1) {
     const long p = tile * 64L + lane;
     const bool ok = p < (long)B * L;
     const long b = ok ? p / L : 0, l = ok ? p - b * L : 0;
-    const float m = ok ? mu[p] : 0.f, rs = ok ? rstd[p] : 0.f;
     const float* xp = x + b * xbs + l + (long)c0 * L;
     const float* dp = dy + b * dybs + l + (long)c0 * L;
-    float xh[CPW], g[CPW];
+    float* dxp = dx + b * dxbs + l + (long)c0 * L;
+    float xh[CPW], g[CPW], old[CPW];
+#pragma unroll
+    for (int i = 0; i < CPW; ++i) {
+      const bool cok = ok && c0 + i < C;
+      g[i] = cok ? dp[(long)i * L] : 0.f;
+      xh[i] = cok ? xp[(long)i * L] : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < CPW; ++i) old[i] = (ACC && ok && c0 + i < C) ? dxp[(long)i * L] : 0.f;
+    const float m = ok ? mu[p] : 0.f, rs = ok ? rstd[p] : 0.f;
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < CPW; ++i) {
       const bool cok = ok && c0 + i < C;
-      const float d = cok ? dp[(long)i * L] : 0.f;
-      xh[i] = cok ? (xp[(long)i * L] - m) * rs : 0.f;
-      g[i] = cok ? d * w[c0 + i] : 0.f;
+      const float d = g[i];
+      xh[i] = cok ? (xh[i] - m) * rs : 0.f;
+      g[i] = d * wsh[c0 + i];
       s1 += g[i];
       s2 += g[i] * xh[i];
       dwacc[i] = fmaf(d, xh[i], dwacc[i]);
       dbacc[i] += d;
     }
-    __syncthreads();  // the previous tile's readers of red[] are done
-    red[0][wid][lane] = s1;
-    red[1][wid][lane] = s2;
-    __syncthreads();
+    red[par][0][wid][lane] = s1;
+    red[par][1][wid][lane] = s2;
+    __syncthreads();  // the next tile writes the other half of red[]; its barrier is behind this tile's readers
     if (ok) {
-      const float a1 = (red[0][0][lane] + red[0][1][lane] + red[0][2][lane] + red[0][3][lane]) / C;
-      const float a2 = (red[1][0][lane] + red[1][1][lane] + red[1][2][lane] + red[1][3][lane]) / C;
-      float* dxp = dx + b * dxbs + l + (long)c0 * L;
+      const float(*r1)[64] = red[par][0];
+      const float(*r2)[64] = red[par][1];
+      const float a1 = (((r1[0][lane] + r1[1][lane]) + (r1[2][lane] + r1[3][lane])) +
+                        ((r1[4][lane] + r1[5][lane]) + (r1[6][lane] + r1[7][lane]))) / C;
+      const float a2 = (((r2[0][lane] + r2[1][lane]) + (r2[2][lane] + r2[3][lane])) +
+                        ((r2[4][lane] + r2[5][lane]) + (r2[6][lane] + r2[7][lane]))) / C;
 #pragma unroll
       for (int i = 0; i < CPW; ++i) {
         if (c0 + i < C) {
           float o = rs * (g[i] - a1 - xh[i] * a2);
-          if (accumulate_dx) o += dxp[(long)i * L];
+          if (ACC) o += old[i];
           dxp[(long)i * L] = o;
         }
       }
@@ -1021,11 +1047,19 @@ extern "C" int cn_layernorm_c_fwd_f32(const float* x, long xbs, const float* w, 
   return cn_check_launch();
 }
 
+// Blocks of the C <= 128 backward for `ntiles` tiles of 64 pixels. Two blocks of 8 waves fit a CU (256 CUs): up to 512
+// blocks every tile has its own; beyond that a block walks ceil(ntiles / 512) tiles, and past 4096 tiles eight, so
+// that the per-lane chain behind dw / db stays short (1250 tiles of a [8, 128, 100, 100] batch: 512 blocks of 2 - 3).
+static long ln_bwd_blocks(long ntiles) {
+  long nblk = ntiles < 512 ? ntiles : 512;
+  if (ntiles / 8 > nblk) nblk = ntiles / 8;
+  return nblk < 2048 ? nblk : 2048;
+}
+
 // Workspace of cn_layernorm_c_bwd_f32 in floats (per-block partial parameter gradients).
 extern "C" int cn_layernorm_c_workspace_floats(int B, int C, int L) {
   const long ntiles = ((long)B * L + 63) / 64;
-  const long nblk = ntiles < 2048 ? ntiles : 2048;
-  return C <= 128 ? (int)(nblk * 2 * C) : 0;
+  return C <= 128 ? (int)(ln_bwd_blocks(ntiles) * 2 * C) : 0;
 }
 
 // dw/db are ACCUMULATED: zero them first for a fresh gradient. ws: cn_layernorm_c_workspace_floats(B, C, L)
@@ -1039,15 +1073,21 @@ extern "C" int cn_layernorm_c_bwd_f32(const float* x, long xbs, const float* dy,
   if (C > 512) return CN_ERR_ARG;
   if (C <= 128) {
     const long ntiles = (P + 63) / 64;
-    const int nblk = (int)(ntiles < 2048 ? ntiles : 2048);
+    const int nblk = (int)ln_bwd_blocks(ntiles);
     if (ws == nullptr || ws_floats < (long)nblk * 2 * C) return CN_ERR_ARG;
     const dim3 grid((unsigned)nblk);
 #define CN_LN_BWD(CPW_)                                                                                           \
-  CN_LAUNCH((cn_ln_bwd_reg_kernel<CPW_>), grid, dim3(256), 0, (hipStream_t)stream, x, xbs, dy, dybs, w, mu, \
-                     rstd, dx, dxbs, ws, B, C, L, accumulate_dx, (int)ntiles)
-    if (C <= 32) CN_LN_BWD(8);
-    else if (C <= 64) CN_LN_BWD(16);
-    else CN_LN_BWD(32);
+  do {                                                                                                            \
+    if (accumulate_dx)                                                                                            \
+      CN_LAUNCH((cn_ln_bwd_reg_kernel<CPW_, true>), grid, dim3(64 * LN_BWD_WAVES), 0, (hipStream_t)stream, x,     \
+                xbs, dy, dybs, w, mu, rstd, dx, dxbs, ws, B, C, L, (int)ntiles);                                  \
+    else                                                                                                          \
+      CN_LAUNCH((cn_ln_bwd_reg_kernel<CPW_, false>), grid, dim3(64 * LN_BWD_WAVES), 0, (hipStream_t)stream, x,    \
+                xbs, dy, dybs, w, mu, rstd, dx, dxbs, ws, B, C, L, (int)ntiles);                                  \
+  } while (0)
+    if (C <= 32) CN_LN_BWD(4);
+    else if (C <= 64) CN_LN_BWD(8);
+    else CN_LN_BWD(16);
 #undef CN_LN_BWD
     CN_LAUNCH(cn_ln_param_finalize_kernel, dim3((2 * C + 31) / 32, 16), dim3(256), 0, (hipStream_t)stream, ws,
                        nblk, C, dw, db);
