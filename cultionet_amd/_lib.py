@@ -91,6 +91,11 @@ SIGNATURES = {
     "cn_chip_hist_u32": [P, I, P, I, I, L, I, P],
     "cn_hist_batch_reduce": [P, P, P, P, I, I, I, I, P],
     "cn_label_counts_i64": [P, I, L, P, I, P],
+    "cn_prune_workspace_words": [L],
+    "cn_prune_magnitude_u8": [P, P, L, L, P, L, P],
+    "cn_mask_select_f32": [P, P, P, L, P],
+    "cn_prune_reset_f32": [P, P, P, L, P],
+    "cn_prune_count_u32": [P, L, P, P],
     # ---- bf16 NHWC mixed-precision path ----
     "cn_bconv_packed_elems": [I, I, I],
     "cn_pack_weights_bf16": [P, P, I, I, I, L, L, L, P],
@@ -203,7 +208,7 @@ def call(name: str, *args) -> int:
 
 LONG_RESULT = {"cn_launch_count", "cn_bconv_packed_elems", "cn_bwgrad_workspace_floats", "cn_bn_workspace_floats_bf16",
                "cn_bn_group_workspace_floats_bf16", "cn_pretime_workspace_floats",
-               "cn_sca_workspace_floats_bf16"}
+               "cn_sca_workspace_floats_bf16", "cn_prune_workspace_words"}
 
 DOUBLE_RESULT = {"cn_profile_top_bytes"}
 

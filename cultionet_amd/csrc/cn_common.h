@@ -112,3 +112,20 @@ __device__ __forceinline__ float cn_silu_grad(float x) {
   const float s = cn_sigmoid(x);
   return s * (1.0f + x * (1.0f - s));
 }
+
+// One thread's run of equal bins: LDS-private integer histograms (cn_stats.hip, cn_prune.hip).
+// `add` closes the run when the bin changes, `flush` closes the last one.
+struct CnHistRun {
+  int bin;
+  unsigned int count;
+  __device__ __forceinline__ void add(unsigned int* lds, int b) {
+    if (b == bin) { ++count; return; }
+    if (count) __hip_atomic_fetch_add(lds + bin, count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    bin = b;
+    count = 1;
+  }
+  __device__ __forceinline__ void flush(unsigned int* lds) {
+    if (count) __hip_atomic_fetch_add(lds + bin, count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    count = 0;
+  }
+};

@@ -419,4 +419,4 @@ extern "C" int cn_amp_count_skip(const float* found_inf, int* skipped, void* str
   return cn_check_launch();
 }
 
-extern "C" int cn_version() { return 103; }
+extern "C" int cn_version() { return 104; }

@@ -42,22 +42,6 @@ typedef unsigned int u32;
 typedef unsigned long long u64;
 typedef unsigned __int128 u128;
 
-// One thread's run of equal bins: `add` closes the run when the bin changes, `flush` closes the last one.
-struct CnHistRun {
-  int bin;
-  u32 count;
-  __device__ __forceinline__ void add(u32* lds, int b) {
-    if (b == bin) { ++count; return; }
-    if (count) __hip_atomic_fetch_add(lds + bin, count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    bin = b;
-    count = 1;
-  }
-  __device__ __forceinline__ void flush(u32* lds) {
-    if (count) __hip_atomic_fetch_add(lds + bin, count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    count = 0;
-  }
-};
-
 __device__ __forceinline__ int cn_hist_bin(int v, int top) { return v < 0 ? 0 : (v > top ? top : v); }
 
 // DT: 1 int32, 2 int16, 3 uint16 (the codes of cn_prepare_chips_f32)

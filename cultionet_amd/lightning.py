@@ -607,6 +607,9 @@ class HipTrainer:
     The optimizer state and the launches of a step are a cultionet_amd.optim.NativeOptimizer (``trainer.opt``):
     ``state_dict()`` / ``load_state_dict()`` stop and resume a run, or continue one from the optimizer state of a Lightning
     checkpoint and hand it back.
+
+    ``pruner``: a cultionet_amd.pruning.MagnitudePruner of this model (``--model-pruning``): every step masks the
+    gradient before clipping and the parameters after the update, ``prune(amount)`` runs a round between steps.
     """
 
     _KINDS = {"Adam": 0, "AdamW": 0, "SGD": 1, "RAdam": 2}  # CN_OPT_* of csrc/cn_optim.hip
@@ -615,7 +618,7 @@ class HipTrainer:
                  lr_fn: T.Optional[T.Callable[[int], T.Union[float, T.Tuple[float, float]]]] = None, comm=None,
                  total_steps: T.Optional[int] = None, precision: str = "32-true", replay: bool = False,
                  gradient_clip_algorithm: str = "norm", accumulate_grad_batches: int = 1,
-                 steps_per_epoch: T.Optional[int] = None):
+                 steps_per_epoch: T.Optional[int] = None, pruner=None):
         from .optim import NativeOptimizer
 
         self.lit = lit
@@ -653,6 +656,10 @@ class HipTrainer:
         hyper = {"lr": lit.learning_rate, "weight_decay": lit.weight_decay, "eps": lit.eps}
         self.opt = NativeOptimizer(list(lit.cultionet_model.parameters()), self.store, cls_name,
                                    **{k: hyper[k] for k in takes}, **fixed)
+        # global magnitude pruning (cultionet_amd.pruning.MagnitudePruner): the step keeps pruned entries at zero
+        if pruner is not None and pruner.store is not self.store:
+            raise ValueError("the pruner belongs to another ParamStore than this model's")
+        self.pruner = self.opt.pruner = pruner
         self.total = torch.zeros(1, dtype=torch.float32, device=dev)
         self.clip = gradient_clip_val
         if lr_fn is None:
@@ -853,14 +860,28 @@ class HipTrainer:
         self.opt.step_flat(store.flat_grad.data_ptr(), self._mask, lr, beta1, self._beta2, self._eps, self._wd, scale,
                            self.clip, self.clip_algorithm)
 
+    def prune(self, amount: T.Union[int, float]) -> int:
+        """One round of global magnitude pruning (``MagnitudePruner.prune``) between optimizer steps; returns the
+        number of entries pruned."""
+        if self.pruner is None:
+            raise RuntimeError("HipTrainer was built without a pruner")
+        if self._micro != 0:
+            raise RuntimeError("prune inside a group of accumulated micro-batches: the gradients summed so far were "
+                               "taken with the weights about to be pruned (prune after an optimizer step)")
+        return self.pruner.prune(amount)
+
     def state_dict(self) -> T.Dict[str, T.Any]:
         """What a resumed run needs besides the module's own state_dict: ``optimizer`` in torch's optimizer-state format
         (what ``torch.optim.<kind>.state_dict()`` holds after the same steps: it can go into ``optimizer_states[0]`` of a
-        Lightning checkpoint), the schedule's clock and the accumulation phase. A copy: later steps do not change it."""
+        Lightning checkpoint), the schedule's clock and the accumulation phase, and ``pruner`` when one is attached.
+        A copy: later steps do not change it."""
         import copy
 
-        return {"optimizer": copy.deepcopy(self.opt.state_dict()), "step_count": self.step_count, "micro": self._micro,
-                "param_steps": self.param_steps}
+        d = {"optimizer": copy.deepcopy(self.opt.state_dict()), "step_count": self.step_count, "micro": self._micro,
+             "param_steps": self.param_steps}
+        if self.pruner is not None:
+            d["pruner"] = self.pruner.state_dict()
+        return d
 
     def load_state_dict(self, d: T.Mapping[str, T.Any]) -> None:
         """Resume from ``state_dict()``. ``d["optimizer"]`` may equally be ``optimizer_states[0]`` of a Lightning
@@ -875,6 +896,10 @@ class HipTrainer:
             self.opt._psteps = [int(t) for t in steps]
         if "step_count" in d:
             self.opt.step_count = int(d["step_count"])
+        if "pruner" in d:
+            if self.pruner is None:
+                raise RuntimeError("the state holds a pruner: build the trainer with pruner=MagnitudePruner(...)")
+            self.pruner.load_state_dict(d["pruner"])
 
     def training_step(self, batch: Data, last: bool = False) -> torch.Tensor:
         """One micro-batch; the optimizer steps once ``accumulate_grad_batches`` of them are summed, or at once with

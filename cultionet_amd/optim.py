@@ -71,6 +71,10 @@ class NativeOptimizer(torch.optim.Optimizer):
     A parameter without a gradient (frozen, or ``grad is None``) is skipped for that step, as torch optimizers skip it.
     Every parameter keeps its own step count. ``set_clip`` fuses gradient clipping into the step.
 
+    ``pruner`` (default None: the launches are the ones above): a cultionet_amd.pruning.MagnitudePruner of the same store.
+    The step then zeroes the pruned entries of the gradient buffer it is about to read, in place and before the
+    sum of squares (clipping sees the masked gradient), and the pruned entries of the parameters after the update.
+
     Under a GradScaler the host counts advance at every ``step()``; steps the scaler skipped are counted on the device
     (``skipped``) and subtracted inside the kernel, and folded into the host counts only when the trainable set changes
     and at ``state_dict()``.
@@ -95,6 +99,8 @@ class NativeOptimizer(torch.optim.Optimizer):
         self._mask: T.Optional[T.Tuple[bool, ...]] = None  # the parameters of the last step (or table): store order
         self._segs = None      # (mask, anchor's count at build, [(offset, length, step)], device table, chunks, (lo, hi))
         self._amp_used = False
+        # a cultionet_amd.pruning.MagnitudePruner: the step masks the gradient it reads and the parameters it wrote
+        self.pruner = None
         self.store = None
         if store is not None:
             self._bind(store)
@@ -212,8 +218,15 @@ class NativeOptimizer(torch.optim.Optimizer):
         if amp is not None:
             self._amp_used = True
             amp = (amp[0], amp[1], self.skipped.data_ptr())
+        pruner = self.pruner
+        if pruner is not None:
+            if pruner.store is not store:
+                raise ValueError("the pruner belongs to another ParamStore")
+            pruner.mask_gradients(grad)
         launch_step(store.flat.data_ptr(), grad, self.exp_avg, self.exp_avg_sq, store.numel, self.sumsq, self.opt_kind,
                     clip, clip_algorithm, lr, beta1, beta2, eps, wd, self.step_count, scale, seg, amp)
+        if pruner is not None:
+            pruner.mask_parameters()
         store.bump(mask if segmented else None)  # only the stepped weights changed: only their packed copies refresh
 
     def _hyper(self) -> T.Tuple[float, float, float, float, float]:

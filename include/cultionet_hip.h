@@ -34,7 +34,9 @@ extern "C" {
 
 /* cn_version(): 100 initial ABI; 101 adds cn_grad_sumsq_seg_f32 / cn_adamw_step_seg_f32 (frozen parameters);
  * 102 adds cn_optim_step_f32 / cn_optim_step_seg_f32 (Adam, SGD, RAdam; value clipping);
- * 103 adds cn_optim_step_amp_f32 / cn_amp_count_skip (the segmented step under a device-side loss scaler). */
+ * 103 adds cn_optim_step_amp_f32 / cn_amp_count_skip (the segmented step under a device-side loss scaler);
+ * 104 adds cn_prune_magnitude_u8 / cn_mask_select_f32 / cn_prune_reset_f32 / cn_prune_count_u32 (global magnitude
+ * pruning of the flat parameter buffer). */
 int cn_version(void);
 
 /* ---- packed weights for the implicit-GEMM kernels -------------------------------------------
@@ -448,6 +450,29 @@ int cn_chip_hist_u32(const void* x, int dtype, unsigned int* hist, int B, int C,
 int cn_hist_batch_reduce(unsigned int* batch_hist, unsigned long long* dataset_hist, const long long* weights,
                          long long* records, int batch_index, int capacity, int C, int nbins, void* stream);
 int cn_label_counts_i64(const void* y, int ydtype, long N, long long* counts, int nlab, void* stream);
+
+/* ---- global magnitude pruning of the flat parameter buffer ----------------------------------------------------------
+ * torch.nn.utils.prune.global_unstructured(..., L1Unstructured, amount) (ModelPruning, callbacks.py:268-269) over
+ * integers. flags: one byte per flat element, bit 0 = alive, bit 1 = prunable; an element is eligible when both are set,
+ * pruned when only bit 1 is. Keys are bits(|w|): -0.0 and +0.0 are equal, non-finite values order by bit pattern.
+ * magnitude: clears bit 0 of the k eligible elements of smallest key; among equal keys at the threshold the lowest index
+ *   goes first, so exactly k bits are cleared (the caller tracks the eligible count and guarantees 1 <= k <= it).
+ *   Radix selection (3 histogram + pick launches over 11 + 10 + 10 bits), per-chunk tie count, one-block scan, commit:
+ *   9 launches, no allocation, no synchronisation, integer sums only. ws: cn_prune_workspace_words(n) uint32 words,
+ *   ZERO-FILLED before its first use (every call leaves the histogram zero), one per stream; afterwards ws[0] = the
+ *   threshold key and ws[1] = the ties pruned. CN_ERR_ARG: n outside [1, 2^31), k outside [1, n], w not 16-byte or
+ *   flags not 4-byte aligned, ws too small.
+ * mask_select: dst[i] = pruned(i) ? +0.0 : src[i], a select on the loaded words (a pruned inf / NaN becomes +0.0, every
+ *   other value keeps its bits); dst == src allowed. dst / src 16-byte, flags 4-byte aligned. One launch.
+ * reset: p[i] = prunable(i) ? (alive(i) ? snapshot[i] : +0.0) : p[i] (the lottery-ticket reset). One launch.
+ * count: out[0] += eligible elements (the caller zeroes it). One launch. */
+long cn_prune_workspace_words(long n);
+int cn_prune_magnitude_u8(const float* w, unsigned char* flags, long n, long k, unsigned int* ws, long ws_words,
+                          void* stream);
+int cn_mask_select_f32(float* dst, const float* src, const unsigned char* flags, long n, void* stream);
+int cn_prune_reset_f32(float* p, const float* snapshot, const unsigned char* flags, long n, void* stream);
+int cn_prune_count_u32(const unsigned char* flags, long n, unsigned int* out, void* stream);
+
 
 
 /* ================================================================================================================
