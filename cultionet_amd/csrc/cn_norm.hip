@@ -220,123 +220,6 @@ __global__ __launch_bounds__(256) void cn_bn_bwd_apply_kernel(const float* __res
   }
 }
 
-// ---- small tensors (B*L <= 2048 values per channel: the 13x13 level): ONE launch, one block per
-// channel, the channel's values held in registers between the statistics and the normalisation -- x (and dy) are
-// read once and the partial-sums round trip + second launch disappear. Same fp64 statistics as the two-pass path.
-template <int NV>
-__global__ __launch_bounds__(256) void cn_bn_fused_fwd_kernel(const float* __restrict__ x, long xbs,
-                                                             float* __restrict__ mean, float* __restrict__ rstd,
-                                                             const float* __restrict__ gamma,
-                                                             const float* __restrict__ beta,
-                                                             const float* __restrict__ res, long rbs,
-                                                             float* __restrict__ y, long ybs, int B, int C, int L,
-                                                             int act, float eps, float momentum,
-                                                             float* __restrict__ running_mean,
-                                                             float* __restrict__ running_var) {
-  __shared__ double scratch[4];
-  const int c = blockIdx.x, n = B * L;
-  float v[NV];
-  double s = 0.0, ss = 0.0;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    const int i = threadIdx.x + k * 256;
-    v[k] = 0.f;
-    if (i < n) {
-      const int b = i / L, l = i - b * L;
-      v[k] = x[b * xbs + (long)c * L + l];
-      s += v[k];
-      ss += (double)v[k] * v[k];
-    }
-  }
-  s = cn_block_sum<double, 256>(s, scratch);
-  ss = cn_block_sum<double, 256>(ss, scratch);
-  const double count = (double)n;
-  const double md = s / count;
-  double var = ss / count - md * md;
-  if (var < 0.0) var = 0.0;
-  const float m = (float)md, rs = (float)(1.0 / sqrt(var + (double)eps));
-  if (threadIdx.x == 0) {
-    mean[c] = m;
-    rstd[c] = rs;
-    if (running_mean != nullptr) {
-      const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-      running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
-      running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-    }
-  }
-  const float sc = gamma[c] * rs, be = beta[c];
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    const int i = threadIdx.x + k * 256;
-    if (i < n) {
-      const int b = i / L, l = i - b * L;
-      float z = (v[k] - m) * sc + be;
-      if (act == 1) z = cn_silu(z);
-      if (res) z += res[b * rbs + (long)c * L + l];
-      y[b * ybs + (long)c * L + l] = z;
-    }
-  }
-}
-
-template <int NV>
-__global__ __launch_bounds__(256) void cn_bn_fused_bwd_kernel(const float* __restrict__ x, long xbs,
-                                                             const float* __restrict__ dy, long dybs,
-                                                             const float* __restrict__ mean,
-                                                             const float* __restrict__ rstd,
-                                                             const float* __restrict__ gamma,
-                                                             const float* __restrict__ beta, int training,
-                                                             float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                             int accumulate_params, float* __restrict__ dx, long dxbs,
-                                                             int B, int C, int L, int act, int accumulate) {
-  __shared__ double scratch[4];
-  const int c = blockIdx.x, n = B * L;
-  const float m = mean[c], rs = rstd[c], ga = gamma[c], be = beta[c];
-  float xh[NV], dz[NV];
-  double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    const int i = threadIdx.x + k * 256;
-    xh[k] = 0.f;
-    dz[k] = 0.f;
-    if (i < n) {
-      const int b = i / L, l = i - b * L;
-      xh[k] = (x[b * xbs + (long)c * L + l] - m) * rs;
-      float d = dy[b * dybs + (long)c * L + l];
-      if (act == 1) d *= cn_silu_grad(ga * xh[k] + be);
-      dz[k] = d;
-      s1 += d;
-      s2 += (double)d * xh[k];
-    }
-  }
-  s1 = cn_block_sum<double, 256>(s1, scratch);
-  s2 = cn_block_sum<double, 256>(s2, scratch);
-  if (threadIdx.x == 0) {
-    if (accumulate_params) {
-      dgamma[c] += (float)s2;
-      dbeta[c] += (float)s1;
-    } else {
-      dgamma[c] = (float)s2;
-      dbeta[c] = (float)s1;
-    }
-  }
-  if (dx == nullptr) return;
-  const double count = (double)n;
-  const float c1 = training ? (float)(s1 / count) : 0.f, c2 = training ? (float)(s2 / count) : 0.f;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    const int i = threadIdx.x + k * 256;
-    if (i < n) {
-      const int b = i / L, l = i - b * L;
-      float g = (dz[k] - c1 - xh[k] * c2) * (ga * rs);
-      float* o = dx + b * dxbs + (long)c * L + l;
-      if (accumulate) g += *o;
-      *o = g;
-    }
-  }
-}
-
-#define BN_FUSED_MAX (8 * 256)  // larger channels are faster as two wide launches than as one block per channel
-
 // Single BatchNorm with few channels (BatchNorm3d of the time reduction: C = 3 channels of 3.2M elements at batch 32
 // were 192 blocks on 256 CUs, ~2 TB/s): up to 256 splits per channel, reduced block-parallel by the apply kernels.
 static int bn_splits_wide(int C, long L) {
@@ -365,6 +248,365 @@ static dim3 plane_grid(int B, int C, int L) {
 
 extern "C" int cn_bn_workspace_doubles(int C) { return C * BN_SPLIT_MAX * 2; }
 
+// ---------------------------------------------------------------------------
+// Grouped BatchNorm (+ SiLU): G (<= 4) BatchNorm layers over G same-shaped tensors in one launch (pair) -- the
+// dilation branches of ResidualAConv (convolution.py:376-395). sum_outputs != 0 fuses the ResUNet-a sum
+//   y = res + sum_g act(bn_g(x_g))
+// into the one normalisation pass (the sequential form re-reads and re-writes the running sum once per branch).
+// The single-tensor entry points fill the same argument block with G = 1.
+// ---------------------------------------------------------------------------
+#define BN_MAX_GROUPS 4
+struct CnBnGroupArgs {
+  const float* x[BN_MAX_GROUPS];
+  const float* gamma[BN_MAX_GROUPS];
+  const float* beta[BN_MAX_GROUPS];
+  float* mean[BN_MAX_GROUPS];
+  float* rstd[BN_MAX_GROUPS];
+  float* running_mean[BN_MAX_GROUPS];
+  float* running_var[BN_MAX_GROUPS];
+  float* y[BN_MAX_GROUPS];         // forward outputs (sum mode: y[0] only)
+  const float* dy[BN_MAX_GROUPS];  // backward: output gradients (sum mode: all the same pointer)
+  float* dx[BN_MAX_GROUPS];
+  float* dgamma[BN_MAX_GROUPS];
+  float* dbeta[BN_MAX_GROUPS];
+  int accumulate_dx[BN_MAX_GROUPS];
+  long xbs, ybs, dybs, dxbs, rbs;
+  const float* res;
+  int G, B, C, L, act, splits, training, sum_outputs, accumulate_params;
+  int vec4;  // L % 4 == 0 and every plane the pass touches 16-byte aligned => float4 accesses
+  float eps, momentum;
+  double* part;  // [G][C][splits][2]
+};
+
+// ---------------------------------------------------------------------------
+// Resident BatchNorm: ONE launch per pass. A block owns channel c of one group (GS == 1, grid = (C, G)) or, in the
+// summed forward, of all GS = G groups (grid = (C)). It issues all its loads up front, keeps the channel's B*L values in registers (NV units of 16 bytes, or of one dword
+// where a plane is not 16-byte aligned, per thread and tensor), sums in fp64 like the two-pass kernels, reduces across
+// the block and applies from the registers: x (and dy) are read once, no partial sums go through memory and the second,
+// dependent launch is gone. No block waits for another one: a channel that does not fit one block stays two-pass.
+// ---------------------------------------------------------------------------
+#define BN_RES_CHUNK 4  // units of the residual / the old dx fetched ahead of their stores
+template <bool V4> struct CnBnUnit { typedef float type; };
+template <> struct CnBnUnit<true> { typedef float4 type; };
+
+__device__ __forceinline__ void cn_bn_clear(float& v) { v = 0.f; }
+__device__ __forceinline__ void cn_bn_clear(float4& v) { v.x = v.y = v.z = v.w = 0.f; }
+__device__ __forceinline__ void cn_bn_stat(float v, double& s, double& ss) {
+  s += v;
+  ss += (double)v * v;
+}
+__device__ __forceinline__ void cn_bn_stat(const float4& v, double& s, double& ss) {
+  s += ((double)v.x + (double)v.y) + ((double)v.z + (double)v.w);
+  ss += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
+}
+template <class F> __device__ __forceinline__ float cn_bn_map(float a, float b, F f) { return f(a, b); }
+template <class F> __device__ __forceinline__ float4 cn_bn_map(const float4& a, const float4& b, F f) {
+  float4 r;
+  r.x = f(a.x, b.x); r.y = f(a.y, b.y); r.z = f(a.z, b.z); r.w = f(a.w, b.w);
+  return r;
+}
+
+// Both sums of a thread through one pair of barriers; every thread returns the block's totals. The empty asm pins the
+// two sums in front of the barrier: without it the compiler finished the second sum behind the first reduction and
+// held every value's double in registers until then (that spilled).
+template <int NT>
+__device__ __forceinline__ void cn_bn_block_sum2(double& a, double& b, double* scratch) {
+  asm volatile("" : "+v"(a), "+v"(b));
+  a = cn_wave_sum(a);
+  b = cn_wave_sum(b);
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) {
+    scratch[2 * wid] = a;
+    scratch[2 * wid + 1] = b;
+  }
+  __syncthreads();
+  a = b = 0.0;
+#pragma unroll
+  for (int i = 0; i < NT / 64; ++i) {
+    a += scratch[2 * i];
+    b += scratch[2 * i + 1];
+  }
+}
+
+// Unit i = t + k * T of a channel of B planes of n units each, k = 0, 1, ...: (b, l) advances by (T / n, T % n) with
+// one carry, so the only divisions are the two of the constructor. Unit i exists iff b < B.
+struct CnBnWalk {
+  int b, l, n, qt, rt;
+  // The thread index goes through an empty asm: the compiler then cannot merge the walks of one kernel and keep every
+  // unit's offsets in registers from the loads to the stores (that spilled; recomputing them is a few integer ops).
+  __device__ __forceinline__ CnBnWalk(int t, int T, int n_) : n(n_) {
+    asm volatile("" : "+v"(t));
+    b = t / n_;
+    l = t - b * n_;
+    qt = T / n_;
+    rt = T - qt * n_;
+  }
+  __device__ __forceinline__ void next() {
+    b += qt;
+    l += rt;
+    if (l >= n) {
+      l -= n;
+      ++b;
+    }
+  }
+};
+
+template <int T, int NV, int GS, bool V4>
+__global__ __launch_bounds__(T) void cn_bn_res_fwd_kernel(const CnBnGroupArgs a) {
+  typedef typename CnBnUnit<V4>::type V;
+  constexpr int U = V4 ? 4 : 1;
+  __shared__ double scratch[2 * (T / 64)];
+  const int c = blockIdx.x, g0 = GS == 1 ? blockIdx.y : 0;
+  const int n = a.L / U;
+  const long r0 = (long)c * a.L;
+  V v[GS][NV];
+  {
+    CnBnWalk w(threadIdx.x, T, n);
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+      if (w.b < a.B) {
+        const long o = w.b * a.xbs + r0 + w.l * U;
+#pragma unroll
+        for (int g = 0; g < GS; ++g) v[g][k] = *reinterpret_cast<const V*>(a.x[g0 + g] + o);
+      } else {
+#pragma unroll
+        for (int g = 0; g < GS; ++g) cn_bn_clear(v[g][k]);
+      }
+      w.next();
+    }
+  }
+  const double count = (double)a.B * a.L;
+  float m[GS], sc[GS], be[GS];
+#pragma unroll
+  for (int g = 0; g < GS; ++g) {
+    double s = 0.0, ss = 0.0;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) cn_bn_stat(v[g][k], s, ss);  // a unit past the end holds zeros
+    cn_bn_block_sum2<T>(s, ss, scratch);
+    const double md = s / count;
+    double var = ss / count - md * md;
+    if (var < 0.0) var = 0.0;
+    m[g] = (float)md;
+    const float rs = (float)(1.0 / sqrt(var + (double)a.eps));
+    if (threadIdx.x == 0) {
+      a.mean[g0 + g][c] = m[g];
+      a.rstd[g0 + g][c] = rs;
+      if (a.running_mean[g0 + g] != nullptr) {
+        const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
+        float* rm = a.running_mean[g0 + g];
+        float* rv = a.running_var[g0 + g];
+        rm[c] = (1.f - a.momentum) * rm[c] + a.momentum * m[g];
+        rv[c] = (1.f - a.momentum) * rv[c] + a.momentum * (float)unbiased;
+      }
+    }
+    sc[g] = a.gamma[g0 + g][c] * rs;
+    be[g] = a.beta[g0 + g][c];
+  }
+  // The residual is fetched BN_RES_CHUNK units at a time, each batch ahead of its stores (next to every store, each
+  // load waited for the store before it: see cn_ln_fwd_reg_kernel), so it costs a fixed few registers.
+  const bool has_res = a.res != nullptr;
+  const int act = a.act;
+  float* yp = a.y[g0];
+  CnBnWalk w(threadIdx.x, T, n);
+#pragma unroll
+  for (int k0 = 0; k0 < NV; k0 += BN_RES_CHUNK) {
+    V rr[BN_RES_CHUNK];
+    if (has_res) {
+      CnBnWalk wr = w;
+#pragma unroll
+      for (int j = 0; j < BN_RES_CHUNK; ++j) {
+        if (k0 + j < NV && wr.b < a.B) rr[j] = *reinterpret_cast<const V*>(a.res + wr.b * a.rbs + r0 + wr.l * U);
+        wr.next();
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < BN_RES_CHUNK; ++j) {
+      const int k = k0 + j;
+      if (k < NV) {
+        if (w.b < a.B) {
+          V acc;
+#pragma unroll
+          for (int g = 0; g < GS; ++g) {
+            const float mg = m[g], sg = sc[g], bg = be[g];
+            const V z = cn_bn_map(v[g][k], v[g][k], [&](float xv, float) {
+              const float t = (xv - mg) * sg + bg;
+              return act == 1 ? cn_silu(t) : t;
+            });
+            if (g == 0) {
+              if (has_res) acc = cn_bn_map(rr[j], z, [](float r, float f) { return r + f; });
+              else if (a.sum_outputs) acc = cn_bn_map(z, z, [](float f, float) { return 0.f + f; });
+              else acc = z;
+            } else {
+              acc = cn_bn_map(acc, z, [](float p, float f) { return p + f; });  // res + f_0 + f_1 + ...
+            }
+          }
+          *reinterpret_cast<V*>(yp + w.b * a.ybs + r0 + w.l * U) = acc;
+        }
+        w.next();
+      }
+    }
+  }
+}
+
+// Backward: the block holds xhat and dz = dy * SiLU'(gamma * xhat + beta) of its channel (SiLU' evaluated once), forms
+// sum dz and sum dz * xhat in fp64, writes dgamma / dbeta and stores dx. Always one group per block, grid = (C, G),
+// also behind one dy for all groups: a block that owned its channel in all groups and loaded dy once was measured
+// SLOWER (C = 128 at 50 x 50: 24.2 us against 17.9; 25 x 25: 12.1 against 8.6 -- half the blocks, twice the registers,
+// and the second read of dy comes from the caches).
+template <int T, int NV, bool V4>
+__global__ __launch_bounds__(T) void cn_bn_res_bwd_kernel(const CnBnGroupArgs a) {
+  typedef typename CnBnUnit<V4>::type V;
+  constexpr int U = V4 ? 4 : 1;
+  __shared__ double scratch[2 * (T / 64)];
+  const int c = blockIdx.x, g = blockIdx.y;
+  const int n = a.L / U;
+  const long r0 = (long)c * a.L;
+  V xh[NV], dz[NV];
+  {
+    CnBnWalk w(threadIdx.x, T, n);
+    const float* xp = a.x[g];
+    const float* dyp = a.dy[g];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+      if (w.b < a.B) {
+        xh[k] = *reinterpret_cast<const V*>(xp + w.b * a.xbs + r0 + w.l * U);
+        dz[k] = *reinterpret_cast<const V*>(dyp + w.b * a.dybs + r0 + w.l * U);
+      } else {
+        cn_bn_clear(xh[k]);
+        cn_bn_clear(dz[k]);
+      }
+      w.next();
+    }
+  }
+  const double count = (double)a.B * a.L;
+  const int act = a.act;
+  const float m = a.mean[g][c], rs = a.rstd[g][c], ga = a.gamma[g][c], be = a.beta[g][c];
+  double s1 = 0.0, s2 = 0.0;
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    // a unit past the end holds x = dy = 0: dz = 0 there, and both sums are left as they are
+    xh[k] = cn_bn_map(xh[k], xh[k], [&](float xv, float) { return (xv - m) * rs; });
+    dz[k] = cn_bn_map(dz[k], xh[k], [&](float dv, float h) {
+      if (act == 1) dv *= cn_silu_grad(ga * h + be);
+      s1 += dv;
+      s2 += (double)dv * h;
+      return dv;
+    });
+  }
+  cn_bn_block_sum2<T>(s1, s2, scratch);
+  if (threadIdx.x == 0) {
+    if (a.accumulate_params) {
+      a.dgamma[g][c] += (float)s2;
+      a.dbeta[g][c] += (float)s1;
+    } else {
+      a.dgamma[g][c] = (float)s2;
+      a.dbeta[g][c] = (float)s1;
+    }
+  }
+  float* dxp = a.dx[g];
+  if (dxp == nullptr) return;
+  const bool acc = a.accumulate_dx[g] != 0;
+  const float k1 = a.training ? (float)(s1 / count) : 0.f, k2 = a.training ? (float)(s2 / count) : 0.f, kg = ga * rs;
+  CnBnWalk w(threadIdx.x, T, n);
+#pragma unroll
+  for (int k0 = 0; k0 < NV; k0 += BN_RES_CHUNK) {
+    V pv[BN_RES_CHUNK];
+    if (acc) {  // the old dx, a batch ahead of its stores
+      CnBnWalk wr = w;
+#pragma unroll
+      for (int j = 0; j < BN_RES_CHUNK; ++j) {
+        if (k0 + j < NV && wr.b < a.B) pv[j] = *reinterpret_cast<const V*>(dxp + wr.b * a.dxbs + r0 + wr.l * U);
+        wr.next();
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < BN_RES_CHUNK; ++j) {
+      const int k = k0 + j;
+      if (k < NV) {
+        if (w.b < a.B) {
+          V o = cn_bn_map(dz[k], xh[k], [&](float d, float h) { return (d - k1 - h * k2) * kg; });
+          if (acc) o = cn_bn_map(o, pv[j], [](float gr, float prev) { return gr + prev; });
+          *reinterpret_cast<V*>(dxp + w.b * a.dxbs + r0 + w.l * U) = o;
+        }
+        w.next();
+      }
+    }
+  }
+}
+
+// The rule that chooses the path: a pure function of the launch's shape (pass, groups, summed or not, B, C, L, unit).
+// BN_RES_SHAPES lists the block shapes (threads T, units NV per thread and tensor) with the most summed groups a block
+// of that shape takes in the forward and whether the backward (two tensors per value: xhat and dz) has it: those whose
+// data registers, 4 * NV * tensors with 16-byte units, the compiler fits without scratch beside ~45 registers of
+// addressing and fp64 sums under the cap of 128 of a 1024-thread block. The first shape that holds the channel is
+// taken. At batch 8 that is: forward 100 x 100 (20 000 units) resident unless summed, two summed groups up to
+// 50 x 50; backward up to 50 x 50.
+struct CnBnPlan {
+  int T, NV, GS;  // NV == 0: two-pass
+};
+static const struct { int T, NV, gs_fwd, bwd; } BN_RES_SHAPES[] = {{512, 4, 3, 1}, {1024, 5, 3, 1}, {1024, 10, 2, 1},
+                                                                    {1024, 20, 1, 0}};
+// A block streams its channel at the rate of ONE CU, so a launch of few blocks with much to stream is slower resident
+// than as two wide launches. Isolated, in us, resident against two-pass (tools/bn_bench.py, profiles/
+// r09_batchnorm_f32.txt; values = B * L * groups of the block):
+//   blocks  values   forward         backward
+//     9     80 000   26.8 / 15.4
+//    64     80 000   29.9 / 23.7
+//    64     40 000   17.8 / 16.0
+//    64     20 000   11.0 / 12.3      9.3 / 13.1
+//   128     20 000   12.1 / 16.1     14.2 / 19.2
+//   128     40 000   19.8 / 21.2
+//   256     80 000   47.9 / 61.5
+// so with fewer than BN_RES_FULL_BLOCKS blocks only blocks of at most BN_RES_SMALL values go resident (below that a
+// launch is fixed cost, not bytes: every 25 x 25 and 13 x 13 launch is 3 to 5 us faster resident).
+#define BN_RES_FULL_BLOCKS 128
+#define BN_RES_SMALL 20480
+
+static CnBnPlan bn_resident_plan(bool backward, int G, bool summed, int B, int C, int L, bool v4) {
+  const CnBnPlan none = {0, 0, 0};
+  const long units = (long)B * (L / (v4 ? 4 : 1));
+  const int GS = (!backward && summed) ? G : 1;  // the summed forward: a block owns its channel in all G groups
+  for (const auto& s : BN_RES_SHAPES) {
+    if ((backward ? !s.bwd : GS > s.gs_fwd) || (long)s.T * s.NV < units) continue;
+#ifndef CN_BN_RESIDENT_ALL  // diagnostic build: every shape that fits goes resident (tools/bn_bench.py prices the rule)
+    if ((long)C * (GS == 1 ? G : 1) < BN_RES_FULL_BLOCKS && (long)B * L * GS > BN_RES_SMALL) break;
+#endif
+    const CnBnPlan p = {s.T, s.NV, GS};
+    return p;
+  }
+  return none;
+}
+
+template <bool BWD, int T, int NV, int GS>
+static void bn_resident_launch_one(const CnBnGroupArgs& a, hipStream_t stream) {
+  const dim3 grid(a.C, GS == 1 ? a.G : 1);
+  if constexpr (BWD) {
+    if (a.vec4) CN_LAUNCH((cn_bn_res_bwd_kernel<T, NV, true>), grid, dim3(T), 0, stream, a);
+    else CN_LAUNCH((cn_bn_res_bwd_kernel<T, NV, false>), grid, dim3(T), 0, stream, a);
+  } else {
+    if (a.vec4) CN_LAUNCH((cn_bn_res_fwd_kernel<T, NV, GS, true>), grid, dim3(T), 0, stream, a);
+    else CN_LAUNCH((cn_bn_res_fwd_kernel<T, NV, GS, false>), grid, dim3(T), 0, stream, a);
+  }
+}
+
+// One case per (shape, groups per block) of BN_RES_SHAPES.
+template <bool BWD>
+static bool bn_resident_launch(const CnBnPlan& p, const CnBnGroupArgs& a, hipStream_t stream) {
+#define CN_BN_RES(T_, NV_, GS_)                           \
+  if (p.T == T_ && p.NV == NV_ && p.GS == GS_) {          \
+    bn_resident_launch_one<BWD, T_, NV_, GS_>(a, stream); \
+    return true;                                          \
+  }
+  CN_BN_RES(512, 4, 1) CN_BN_RES(1024, 5, 1) CN_BN_RES(1024, 10, 1)
+  if constexpr (!BWD) {
+    CN_BN_RES(512, 4, 2) CN_BN_RES(512, 4, 3) CN_BN_RES(1024, 5, 2) CN_BN_RES(1024, 5, 3) CN_BN_RES(1024, 10, 2)
+    CN_BN_RES(1024, 20, 1)
+  }
+#undef CN_BN_RES
+  return false;
+}
+
 // Forward. x,y viewed as [B][C][L] (L = H*W for BatchNorm2d, T*H*W for BatchNorm3d).
 // training != 0: batch statistics (saved to mean/rstd [C]) and running stats updated in place.
 // ws: workspace of cn_bn_workspace_doubles(C) doubles.
@@ -374,13 +616,18 @@ extern "C" int cn_bn_act_fwd_f32(const float* x, long xbs, const float* gamma, c
                                  float momentum, float eps, int act, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (B <= 0 || C <= 0 || L <= 0) return CN_OK;
-  if (training && (long)B * L <= BN_FUSED_MAX && C >= 32) {
-#define CN_BN_FWD(NV_)                                                                                               \
-  CN_LAUNCH((cn_bn_fused_fwd_kernel<NV_>), dim3(C), dim3(256), 0, stream, x, xbs, mean, rstd, gamma, beta, res, \
-                     rbs, y, ybs, B, C, L, act, eps, momentum, running_mean, running_var)
-    CN_BN_FWD(8);
-#undef CN_BN_FWD
-    return cn_check_launch();
+  if (training) {
+    CnBnGroupArgs a = {};
+    a.x[0] = x; a.gamma[0] = gamma; a.beta[0] = beta; a.mean[0] = mean; a.rstd[0] = rstd;
+    a.running_mean[0] = running_mean; a.running_var[0] = running_mean != nullptr ? running_var : nullptr;
+    a.y[0] = y; a.res = res;
+    a.xbs = xbs; a.ybs = ybs; a.rbs = rbs;
+    a.G = 1; a.B = B; a.C = C; a.L = L; a.act = act; a.training = 1; a.sum_outputs = res != nullptr;
+    a.eps = eps; a.momentum = momentum;
+    a.vec4 = L % 4 == 0 && xbs % 4 == 0 && ybs % 4 == 0 && (res == nullptr || rbs % 4 == 0) &&
+             ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(res)) & 15) == 0;
+    const CnBnPlan p = bn_resident_plan(false, 1, false, B, C, L, a.vec4 != 0);
+    if (p.NV != 0 && bn_resident_launch<false>(p, a, stream)) return cn_check_launch();
   }
   if (training) {
     const int splits = bn_splits_wide(C, L);
@@ -407,13 +654,17 @@ extern "C" int cn_bn_act_bwd_f32(const float* x, long xbs, const float* dy, long
                                  int training, int act, int accumulate_dx, int accumulate_params, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (B <= 0 || C <= 0 || L <= 0) return CN_OK;
-  if ((long)B * L <= BN_FUSED_MAX && C >= 32) {
-#define CN_BN_BWD(NV_)                                                                                              \
-  CN_LAUNCH((cn_bn_fused_bwd_kernel<NV_>), dim3(C), dim3(256), 0, stream, x, xbs, dy, dybs, mean, rstd, gamma, \
-                     beta, training, dgamma, dbeta, accumulate_params, dx, dxbs, B, C, L, act, accumulate_dx)
-    CN_BN_BWD(8);
-#undef CN_BN_BWD
-    return cn_check_launch();
+  {
+    CnBnGroupArgs a = {};
+    a.x[0] = x; a.dy[0] = dy; a.gamma[0] = gamma; a.beta[0] = beta;
+    a.mean[0] = const_cast<float*>(mean); a.rstd[0] = const_cast<float*>(rstd);
+    a.dx[0] = dx; a.dgamma[0] = dgamma; a.dbeta[0] = dbeta; a.accumulate_dx[0] = accumulate_dx;
+    a.xbs = xbs; a.dybs = dybs; a.dxbs = dxbs;
+    a.G = 1; a.B = B; a.C = C; a.L = L; a.act = act; a.training = training; a.accumulate_params = accumulate_params;
+    a.vec4 = L % 4 == 0 && xbs % 4 == 0 && dybs % 4 == 0 && (dx == nullptr || dxbs % 4 == 0) &&
+             ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0;
+    const CnBnPlan p = bn_resident_plan(true, 1, false, B, C, L, a.vec4 != 0);
+    if (p.NV != 0 && bn_resident_launch<true>(p, a, stream)) return cn_check_launch();
   }
   const int splits = bn_splits_wide(C, L);
   CN_LAUNCH(cn_bn_bwd_partial_kernel, dim3(C, splits), dim3(256), 0, stream, x, xbs, dy, dybs, mean, rstd,
@@ -428,34 +679,8 @@ extern "C" int cn_bn_act_bwd_f32(const float* x, long xbs, const float* dy, long
 }
 
 // ---------------------------------------------------------------------------
-// Grouped BatchNorm (+ SiLU): G (<= 4) BatchNorm layers over G same-shaped tensors in one launch pair -- the
-// dilation branches of ResidualAConv (convolution.py:376-395). sum_outputs != 0 fuses the ResUNet-a sum
-//   y = res + sum_g act(bn_g(x_g))
-// into the one normalisation pass (the sequential form re-reads and re-writes the running sum once per branch).
+// Grouped BatchNorm, two-pass: the channels that do not fit one block (CnBnGroupArgs: above the resident kernels).
 // ---------------------------------------------------------------------------
-#define BN_MAX_GROUPS 4
-struct CnBnGroupArgs {
-  const float* x[BN_MAX_GROUPS];
-  const float* gamma[BN_MAX_GROUPS];
-  const float* beta[BN_MAX_GROUPS];
-  float* mean[BN_MAX_GROUPS];
-  float* rstd[BN_MAX_GROUPS];
-  float* running_mean[BN_MAX_GROUPS];
-  float* running_var[BN_MAX_GROUPS];
-  float* y[BN_MAX_GROUPS];         // forward outputs (sum mode: y[0] only)
-  const float* dy[BN_MAX_GROUPS];  // backward: output gradients (sum mode: all the same pointer)
-  float* dx[BN_MAX_GROUPS];
-  float* dgamma[BN_MAX_GROUPS];
-  float* dbeta[BN_MAX_GROUPS];
-  int accumulate_dx[BN_MAX_GROUPS];
-  long xbs, ybs, dybs, dxbs, rbs;
-  const float* res;
-  int G, B, C, L, act, splits, training, sum_outputs, accumulate_params;
-  int vec4;  // backward: L % 4 == 0 and every x / dy / dx plane 16-byte aligned => float4 accesses
-  float eps, momentum;
-  double* part;  // [G][C][splits][2]
-};
-
 __global__ __launch_bounds__(256) void cn_bn_group_partial_kernel(const CnBnGroupArgs a) {
   __shared__ double scratch[4];
   const int c = blockIdx.x, sp = blockIdx.y, g = blockIdx.z;
@@ -704,6 +929,10 @@ extern "C" int cn_bn_act_group_fwd_f32(int G, const float* const* xs, long xbs, 
            (reinterpret_cast<uintptr_t>(res) & 15) == 0;
   for (int g = 0; g < G; ++g)
     if ((reinterpret_cast<uintptr_t>(a.x[g]) | reinterpret_cast<uintptr_t>(a.y[g])) & 15) a.vec4 = 0;
+  if (training) {
+    const CnBnPlan p = bn_resident_plan(false, G, sum_outputs != 0, B, C, L, a.vec4 != 0);
+    if (p.NV != 0 && bn_resident_launch<false>(p, a, stream)) return cn_check_launch();
+  }
   if (training)
     CN_LAUNCH(cn_bn_group_partial_kernel, dim3(C, a.splits, G), dim3(256), 0, stream, a);
   CN_LAUNCH(cn_bn_group_apply_kernel, plane_grid(B, C, L), dim3(256), 0, stream, a);
@@ -736,8 +965,10 @@ extern "C" int cn_bn_act_group_bwd_f32(int G, const float* const* xs, long xbs, 
     if ((reinterpret_cast<uintptr_t>(a.x[g]) | reinterpret_cast<uintptr_t>(a.dy[g]) |
          reinterpret_cast<uintptr_t>(a.dx[g])) & 15)
       a.vec4 = 0;
-  CN_LAUNCH(cn_bn_group_bwd_partial_kernel, dim3(C, a.splits, G), dim3(256), 0, stream, a);
+  const CnBnPlan p = bn_resident_plan(true, G, false, B, C, L, a.vec4 != 0);
+  if (p.NV != 0 && bn_resident_launch<true>(p, a, stream)) return cn_check_launch();
   const dim3 pg = plane_grid(B, C, L);
+  CN_LAUNCH(cn_bn_group_bwd_partial_kernel, dim3(C, a.splits, G), dim3(256), 0, stream, a);
   CN_LAUNCH(cn_bn_group_bwd_apply_kernel, dim3(pg.x * G, pg.y, pg.z), dim3(256), 0, stream, a, (int)pg.x);
   return cn_check_launch();
 }

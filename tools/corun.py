@@ -56,6 +56,25 @@ victims = {
 }
 
 
+def bn_bwd_victim(HW, G=2):
+    """Grouped BatchNorm backward of G x [8, 128, HW] on the compute stream: one 1024-thread block per channel and group
+    where the library takes the resident path (round 9), the two-pass kernels in a build of an earlier round."""
+    xs = [torch.randn(B, C, HW, device=dev) for _ in range(G)]
+    dys = [torch.randn(B, C, HW, device=dev) for _ in range(G)]
+    dxs = [torch.empty(B, C, HW, device=dev) for _ in range(G)]
+    vec = [[torch.randn(C, device=dev).abs() + 0.5 for _ in range(G)] for _ in range(6)]  # mean rstd gamma beta dg db
+    tab = lambda ts: (ctypes.c_void_p * G)(*[t.data_ptr() for t in ts])
+    bws = torch.empty(G * _lib.query("cn_bn_workspace_doubles", C), dtype=torch.float64, device=dev)
+    keep = (tab(xs), tab(dys), tab(dxs), [tab(v) for v in vec], (ctypes.c_int * G)(), xs, dys, dxs, vec)
+    return lambda: _lib.call("cn_bn_act_group_bwd_f32", G, keep[0], C * HW, keep[1], C * HW, keep[3][0], keep[3][1],
+                             keep[3][2], keep[3][3], keep[2], C * HW, keep[4], keep[3][4], keep[3][5], bws.data_ptr(), B, C,
+                             HW, 1, 1, 1, ms)
+
+
+victims["bn_group_bwd 2x128 ch 50x50"] = bn_bwd_victim(2500)
+victims["bn_group_bwd 2x128 ch 25x25"] = bn_bwd_victim(625)
+
+
 def timed(fn, k, corun):
     torch.cuda.synchronize()
     if corun:
