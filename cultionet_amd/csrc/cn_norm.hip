@@ -2,226 +2,50 @@
 // of NCHW tensors, and per-channel sums. HBM-bound streaming kernels (gfx950).
 //
 // Reference ops: nn.BatchNorm2d / BatchNorm3d + SiLU inside ConvBlock2d
-// (/root/reference/src/cultionet/nn/modules/convolution.py:71-120, models/nunet.py:18-57),
+// (cultionet/nn/modules/convolution.py:71-120, models/nunet.py:18-57),
 // nn.LayerNorm over channels in NHWC (nunet.py:93-97, convolution.py:338-353).
 // Here tensors stay NCHW: a LayerNorm "row" is the C values of one pixel (stride L),
 // lanes walk consecutive pixels so every access is coalesced.
+//
+// fp32 BatchNorm: the single-tensor and the grouped entry points fill one argument block (CnBnGroupArgs, G = 1 for a
+// single call) and share every kernel: the resident ones (one launch per pass, a channel in the registers of a block)
+// and, for the channels that fit no block, the two-pass family cn_bn_group_* (partial sums in fp64 through the
+// workspace, then an apply launch whose blocks reduce their channel's rows themselves). The entry points differ in the
+// number of partial rows only: bn_splits_wide for a single call, bn_splits for a grouped one.
 #include "cn_common.h"
 
+#include <initializer_list>
+
 #define BN_SPLIT_MAX 256  // workspace rows per channel
-#define BN_SPLIT_GROUP 64 // cap of the grouped kernels and the channel sums (every thread walks the partials serially there)
+#define BN_SPLIT_GROUP 64 // cap of the grouped calls and the channel sums
 
-// ---------------------------------------------------------------------------
-// BatchNorm statistics: x viewed as [B][C][L] (batch stride xbs). Partial sums in fp64.
-// part[c][split][2] = {sum, sumsq} over this block's share.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void cn_bn_partial_kernel(const float* __restrict__ x, long xbs, int B, int C,
-                                                           int L, int splits, double* __restrict__ part, int vec4) {
-  __shared__ double scratch[4];
-  const int c = blockIdx.x, sp = blockIdx.y;
-  double s = 0.0, ss = 0.0;
-  if (vec4) {  // L % 4 == 0, 16-byte aligned planes: one float4 per lane and iteration
-    const int L4 = L >> 2;
-    const int per = (L4 + splits - 1) / splits;
-    const int beg = sp * per;
-    const int end = (beg + per < L4) ? beg + per : L4;
-    for (int b = 0; b < B; ++b) {
-      const float4* xp = reinterpret_cast<const float4*>(x + b * xbs + (long)c * L);
-      for (int l = beg + threadIdx.x; l < end; l += 256) {
-        const float4 v = xp[l];
-        s += ((double)v.x + (double)v.y) + ((double)v.z + (double)v.w);  // fp64: a channel far from zero
-        ss += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
-      }
-    }
-  } else {
-    const int per = (L + splits - 1) / splits;
-    const int beg = sp * per;
-    const int end = (beg + per < L) ? beg + per : L;
-    for (int b = 0; b < B; ++b) {
-      const float* xp = x + b * xbs + (long)c * L;
-      for (int l = beg + threadIdx.x; l < end; l += 256) {
-        const float v = xp[l];
-        s += v;
-        ss += (double)v * v;
-      }
-    }
-  }
-  s = cn_block_sum<double, 256>(s, scratch);
-  ss = cn_block_sum<double, 256>(ss, scratch);
-  if (threadIdx.x == 0) {
-    part[((long)c * splits + sp) * 2 + 0] = s;
-    part[((long)c * splits + sp) * 2 + 1] = ss;
-  }
-}
+#define BN_SERIAL_ROWS 8  // up to here every thread adds the partial rows itself
 
-// Sum of a channel's `splits` partial pairs by the whole block (thread t takes partials t, t + 256, ...): every thread
-// returns the totals.
-__device__ __forceinline__ void cn_bn_sum_parts(const double* __restrict__ part, int c, int splits, double& s,
-                                                double& ss) {
-  __shared__ double scratch[4];
+// Sum of a channel's `splits` partial pairs (rows: [splits][2]); every thread returns the totals, the same bits in
+// every thread of every block of the channel. Few rows (the wide launches: 2 x 128 channels at 100 x 100 have 4): each
+// thread walks them, block-uniform loads and no cross-lane traffic in a block that then touches ~1000 elements. More
+// (up to BN_SPLIT_MAX): every wave sums them itself, lane t taking rows t, t + 64, ... -- no barrier and no LDS.
+__device__ __forceinline__ void cn_bn_sum_parts(const double* __restrict__ rows, int splits, double& s, double& ss) {
   double a = 0.0, b = 0.0;
-  for (int i = threadIdx.x; i < splits; i += 256) {
-    a += part[((long)c * splits + i) * 2 + 0];
-    b += part[((long)c * splits + i) * 2 + 1];
-  }
-  s = cn_block_sum<double, 256>(a, scratch);
-  ss = cn_block_sum<double, 256>(b, scratch);
-}
-
-// Eval mode: mean/rstd from running statistics.
-__global__ void cn_bn_eval_stats_kernel(const float* __restrict__ running_mean, const float* __restrict__ running_var,
-                                        int C, float eps, float* __restrict__ mean, float* __restrict__ rstd) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  mean[c] = running_mean[c];
-  rstd[c] = 1.0f / sqrtf(running_var[c] + eps);
-}
-
-// y = act(gamma * (x - mean) * rstd + beta) (+ residual). act: 0 none, 1 SiLU.
-// Training (part != nullptr): every block reduces its channel's `splits` partial sums itself (a few dozen
-// doubles) instead of waiting for a separate finalize launch; block (0, c, 0) publishes mean / rstd for the
-// backward pass and updates the running statistics.
-__global__ __launch_bounds__(256) void cn_bn_apply_kernel(const float* __restrict__ x, long xbs,
-                                                         float* __restrict__ mean, float* __restrict__ rstd,
-                                                         const float* __restrict__ gamma,
-                                                         const float* __restrict__ beta,
-                                                         const float* __restrict__ res, long rbs,
-                                                         float* __restrict__ y, long ybs, int B, int C, int L, int act,
-                                                         const double* __restrict__ part, int splits, double count,
-                                                         float eps, float momentum, float* __restrict__ running_mean,
-                                                         float* __restrict__ running_var) {
-  const int c = blockIdx.y, b = blockIdx.z;
-  float m, rs;
-  if (part != nullptr) {
-    double s, ss;
-    cn_bn_sum_parts(part, c, splits, s, ss);
-    const double md = s / count;
-    double var = ss / count - md * md;
-    if (var < 0.0) var = 0.0;
-    m = (float)md;
-    rs = (float)(1.0 / sqrt(var + (double)eps));
-    if (blockIdx.x == 0 && b == 0 && threadIdx.x == 0) {
-      mean[c] = m;
-      rstd[c] = rs;
-      if (running_mean != nullptr) {
-        const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
-        running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-      }
+  if (splits <= BN_SERIAL_ROWS) {
+    for (int i = 0; i < splits; ++i) {
+      a += rows[2 * i];
+      b += rows[2 * i + 1];
     }
-  } else {
-    m = mean[c];
-    rs = rstd[c];
+    s = a;
+    ss = b;
+    return;
   }
-  const float sc = gamma[c] * rs, be = beta[c];
-  const long r0 = (long)c * L;
-  const float* xp = x + b * xbs + r0;
-  const float* rp = res ? res + b * rbs + r0 : nullptr;
-  float* yp = y + b * ybs + r0;
-  for (int l = blockIdx.x * 256 + threadIdx.x; l < L; l += gridDim.x * 256) {
-    float z = (xp[l] - m) * sc + be;
-    if (act == 1) z = cn_silu(z);
-    if (rp) z += rp[l];
-    yp[l] = z;
+  for (int i = threadIdx.x & 63; i < splits; i += 64) {
+    a += rows[2 * i];
+    b += rows[2 * i + 1];
   }
-}
-
-// Backward pass 1: per-channel partial sums of dz and dz*xhat, dz = dy * act'(z).
-__global__ __launch_bounds__(256) void cn_bn_bwd_partial_kernel(const float* __restrict__ x, long xbs,
-                                                               const float* __restrict__ dy, long dybs,
-                                                               const float* __restrict__ mean,
-                                                               const float* __restrict__ rstd,
-                                                               const float* __restrict__ gamma,
-                                                               const float* __restrict__ beta, int B, int C, int L,
-                                                               int act, int splits, double* __restrict__ part,
-                                                               int vec4) {
-  __shared__ double scratch[4];
-  const int c = blockIdx.x, sp = blockIdx.y;
-  const float m = mean[c], rs = rstd[c], ga = gamma[c], be = beta[c];
-  double s1 = 0.0, s2 = 0.0;
-  auto term = [&](float xv, float dv) {
-    const float xh = (xv - m) * rs;
-    float dz = dv;
-    if (act == 1) dz *= cn_silu_grad(ga * xh + be);
-    s1 += dz;
-    s2 += (double)dz * xh;
-  };
-  if (vec4) {
-    const int L4 = L >> 2;
-    const int per = (L4 + splits - 1) / splits;
-    const int beg = sp * per;
-    const int end = (beg + per < L4) ? beg + per : L4;
-    for (int b = 0; b < B; ++b) {
-      const float4* xp = reinterpret_cast<const float4*>(x + b * xbs + (long)c * L);
-      const float4* dp = reinterpret_cast<const float4*>(dy + b * dybs + (long)c * L);
-      for (int l = beg + threadIdx.x; l < end; l += 256) {
-        const float4 xv = xp[l], dv = dp[l];
-        term(xv.x, dv.x); term(xv.y, dv.y); term(xv.z, dv.z); term(xv.w, dv.w);
-      }
-    }
-  } else {
-    const int per = (L + splits - 1) / splits;
-    const int beg = sp * per;
-    const int end = (beg + per < L) ? beg + per : L;
-    for (int b = 0; b < B; ++b) {
-      const float* xp = x + b * xbs + (long)c * L;
-      const float* dp = dy + b * dybs + (long)c * L;
-      for (int l = beg + threadIdx.x; l < end; l += 256) term(xp[l], dp[l]);
-    }
-  }
-  s1 = cn_block_sum<double, 256>(s1, scratch);
-  s2 = cn_block_sum<double, 256>(s2, scratch);
-  if (threadIdx.x == 0) {
-    part[((long)c * splits + sp) * 2 + 0] = s1;
-    part[((long)c * splits + sp) * 2 + 1] = s2;
-  }
-}
-
-// Backward pass 2: dx (+)= gamma*rstd*(dz - mean(dz) - xhat*mean(dz*xhat))   [train]
-//                  dx (+)= gamma*rstd*dz                                        [eval]
-// Every block reduces its channel's partial sums itself; block (0, c, 0) accumulates dgamma / dbeta.
-__global__ __launch_bounds__(256) void cn_bn_bwd_apply_kernel(const float* __restrict__ x, long xbs,
-                                                             const float* __restrict__ dy, long dybs,
-                                                             const float* __restrict__ mean,
-                                                             const float* __restrict__ rstd,
-                                                             const float* __restrict__ gamma,
-                                                             const float* __restrict__ beta,
-                                                             const double* __restrict__ part, int splits,
-                                                             double count, int training,
-                                                             float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                             int accumulate_params, float* __restrict__ dx, long dxbs,
-                                                             int B, int C, int L, int act, int accumulate) {
-  const int c = blockIdx.y, b = blockIdx.z;
-  double s1, s2;
-  cn_bn_sum_parts(part, c, splits, s1, s2);
-  if (blockIdx.x == 0 && b == 0 && threadIdx.x == 0) {
-    if (accumulate_params) {
-      dgamma[c] += (float)s2;
-      dbeta[c] += (float)s1;
-    } else {
-      dgamma[c] = (float)s2;
-      dbeta[c] = (float)s1;
-    }
-  }
-  if (dx == nullptr) return;
-  const float m = mean[c], rs = rstd[c], ga = gamma[c], be = beta[c];
-  const float c1 = training ? (float)(s1 / count) : 0.f, c2 = training ? (float)(s2 / count) : 0.f;
-  const long r0 = (long)c * L;
-  const float* xp = x + b * xbs + r0;
-  const float* dp = dy + b * dybs + r0;
-  float* dxp = dx + b * dxbs + r0;
-  for (int l = blockIdx.x * 256 + threadIdx.x; l < L; l += gridDim.x * 256) {
-    const float xh = (xp[l] - m) * rs;
-    float dz = dp[l];
-    if (act == 1) dz *= cn_silu_grad(ga * xh + be);
-    float g = (dz - c1 - xh * c2) * (ga * rs);
-    if (accumulate) g += dxp[l];
-    dxp[l] = g;
-  }
+  s = cn_wave_sum(a);
+  ss = cn_wave_sum(b);
 }
 
 // Single BatchNorm with few channels (BatchNorm3d of the time reduction: C = 3 channels of 3.2M elements at batch 32
-// were 192 blocks on 256 CUs, ~2 TB/s): up to 256 splits per channel, reduced block-parallel by the apply kernels.
+// were 192 blocks on 256 CUs, ~2 TB/s): up to 256 splits per channel, summed by every wave of the apply kernels (cn_bn_sum_parts).
 static int bn_splits_wide(int C, long L) {
   int s = (2048 + C - 1) / C;
   const long maxs = (L + 511) / 512;
@@ -253,7 +77,7 @@ extern "C" int cn_bn_workspace_doubles(int C) { return C * BN_SPLIT_MAX * 2; }
 // dilation branches of ResidualAConv (convolution.py:376-395). sum_outputs != 0 fuses the ResUNet-a sum
 //   y = res + sum_g act(bn_g(x_g))
 // into the one normalisation pass (the sequential form re-reads and re-writes the running sum once per branch).
-// The single-tensor entry points fill the same argument block with G = 1.
+// The single-tensor entry points fill the same argument block with G = 1 (bn_single_args), the residual as the sum.
 // ---------------------------------------------------------------------------
 #define BN_MAX_GROUPS 4
 struct CnBnGroupArgs {
@@ -607,83 +431,18 @@ static bool bn_resident_launch(const CnBnPlan& p, const CnBnGroupArgs& a, hipStr
   return false;
 }
 
-// Forward. x,y viewed as [B][C][L] (L = H*W for BatchNorm2d, T*H*W for BatchNorm3d).
-// training != 0: batch statistics (saved to mean/rstd [C]) and running stats updated in place.
-// ws: workspace of cn_bn_workspace_doubles(C) doubles.
-extern "C" int cn_bn_act_fwd_f32(const float* x, long xbs, const float* gamma, const float* beta,
-                                 float* running_mean, float* running_var, const float* res, long rbs, float* y,
-                                 long ybs, float* mean, float* rstd, double* ws, int B, int C, int L, int training,
-                                 float momentum, float eps, int act, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (B <= 0 || C <= 0 || L <= 0) return CN_OK;
-  if (training) {
-    CnBnGroupArgs a = {};
-    a.x[0] = x; a.gamma[0] = gamma; a.beta[0] = beta; a.mean[0] = mean; a.rstd[0] = rstd;
-    a.running_mean[0] = running_mean; a.running_var[0] = running_mean != nullptr ? running_var : nullptr;
-    a.y[0] = y; a.res = res;
-    a.xbs = xbs; a.ybs = ybs; a.rbs = rbs;
-    a.G = 1; a.B = B; a.C = C; a.L = L; a.act = act; a.training = 1; a.sum_outputs = res != nullptr;
-    a.eps = eps; a.momentum = momentum;
-    a.vec4 = L % 4 == 0 && xbs % 4 == 0 && ybs % 4 == 0 && (res == nullptr || rbs % 4 == 0) &&
-             ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(res)) & 15) == 0;
-    const CnBnPlan p = bn_resident_plan(false, 1, false, B, C, L, a.vec4 != 0);
-    if (p.NV != 0 && bn_resident_launch<false>(p, a, stream)) return cn_check_launch();
-  }
-  if (training) {
-    const int splits = bn_splits_wide(C, L);
-    CN_LAUNCH(cn_bn_partial_kernel, dim3(C, splits), dim3(256), 0, stream, x, xbs, B, C, L, splits, ws,
-                       (int)(L % 4 == 0 && xbs % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0));
-    CN_LAUNCH(cn_bn_apply_kernel, plane_grid(B, C, L), dim3(256), 0, stream, x, xbs, mean, rstd, gamma, beta,
-                       res, rbs, y, ybs, B, C, L, act, (const double*)ws, splits, (double)B * L, eps, momentum,
-                       running_mean, running_var);
-  } else {
-    CN_LAUNCH(cn_bn_eval_stats_kernel, dim3((C + 63) / 64), dim3(64), 0, stream, running_mean,
-                       running_var, C, eps, mean, rstd);
-    CN_LAUNCH(cn_bn_apply_kernel, plane_grid(B, C, L), dim3(256), 0, stream, x, xbs, mean, rstd, gamma, beta,
-                       res, rbs, y, ybs, B, C, L, act, (const double*)nullptr, 0, 1.0, eps, momentum,
-                       (float*)nullptr, (float*)nullptr);
-  }
-  return cn_check_launch();
-}
-
-// Backward. dgamma/dbeta (+)= per accumulate_params; dx (+)= per accumulate_dx.
-// coef: scratch [2*C] floats; ws as in forward.
-extern "C" int cn_bn_act_bwd_f32(const float* x, long xbs, const float* dy, long dybs, const float* mean,
-                                 const float* rstd, const float* gamma, const float* beta, float* dx, long dxbs,
-                                 float* dgamma, float* dbeta, float* coef, double* ws, int B, int C, int L,
-                                 int training, int act, int accumulate_dx, int accumulate_params, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (B <= 0 || C <= 0 || L <= 0) return CN_OK;
-  {
-    CnBnGroupArgs a = {};
-    a.x[0] = x; a.dy[0] = dy; a.gamma[0] = gamma; a.beta[0] = beta;
-    a.mean[0] = const_cast<float*>(mean); a.rstd[0] = const_cast<float*>(rstd);
-    a.dx[0] = dx; a.dgamma[0] = dgamma; a.dbeta[0] = dbeta; a.accumulate_dx[0] = accumulate_dx;
-    a.xbs = xbs; a.dybs = dybs; a.dxbs = dxbs;
-    a.G = 1; a.B = B; a.C = C; a.L = L; a.act = act; a.training = training; a.accumulate_params = accumulate_params;
-    a.vec4 = L % 4 == 0 && xbs % 4 == 0 && dybs % 4 == 0 && (dx == nullptr || dxbs % 4 == 0) &&
-             ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0;
-    const CnBnPlan p = bn_resident_plan(true, 1, false, B, C, L, a.vec4 != 0);
-    if (p.NV != 0 && bn_resident_launch<true>(p, a, stream)) return cn_check_launch();
-  }
-  const int splits = bn_splits_wide(C, L);
-  CN_LAUNCH(cn_bn_bwd_partial_kernel, dim3(C, splits), dim3(256), 0, stream, x, xbs, dy, dybs, mean, rstd,
-                     gamma, beta, B, C, L, act, splits, ws,
-                     (int)(L % 4 == 0 && xbs % 4 == 0 && dybs % 4 == 0 &&
-                           ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0));
-  (void)coef;
-  CN_LAUNCH(cn_bn_bwd_apply_kernel, dx != nullptr ? plane_grid(B, C, L) : dim3(1, C, 1), dim3(256), 0,
-                     stream, x, xbs, dy, dybs, mean, rstd, gamma, beta, (const double*)ws, splits, (double)B * L,
-                     training, dgamma, dbeta, accumulate_params, dx, dxbs, B, C, L, act, accumulate_dx);
-  return cn_check_launch();
-}
-
 // ---------------------------------------------------------------------------
-// Grouped BatchNorm, two-pass: the channels that do not fit one block (CnBnGroupArgs: above the resident kernels).
+// Two-pass BatchNorm, single (G = 1) and grouped calls alike: the channels that do not fit one block, the launches of
+// few blocks on large planes, and every eval forward (the apply kernel alone).
+// One body each, instantiated for MAXG = BN_MAX_GROUPS and for MAXG = 1: in a single call the group index is the
+// constant 0, so the operands are kernel arguments and not entries of a table indexed at run time -- one dependent
+// scalar load less per kernel, 0.6-0.8 us of a 9-21 us launch pair on 3 channels.
+// Pass 1: part[g][c][split][2] = {sum, sumsq} of x over this block's share, in fp64. grid = (C, splits, G)
 // ---------------------------------------------------------------------------
+template <int MAXG>
 __global__ __launch_bounds__(256) void cn_bn_group_partial_kernel(const CnBnGroupArgs a) {
   __shared__ double scratch[4];
-  const int c = blockIdx.x, sp = blockIdx.y, g = blockIdx.z;
+  const int c = blockIdx.x, sp = blockIdx.y, g = MAXG == 1 ? 0 : blockIdx.z;
   double s = 0.0, ss = 0.0;
   if (a.vec4) {
     const int L4 = a.L >> 2;
@@ -720,23 +479,23 @@ __global__ __launch_bounds__(256) void cn_bn_group_partial_kernel(const CnBnGrou
   }
 }
 
-// grid = (blocks over L, C, B)
+// Pass 2: y_g = act(gamma * (x_g - mean) * rstd + beta), or y_0 = res + sum_g of that. act: 0 none, 1 SiLU.
+// Training: every block reduces its channel's `splits` partial rows itself instead of waiting for a separate finalize
+// launch. Eval: mean / rstd from the running statistics. Block (0, c, 0) publishes mean / rstd for the backward pass
+// and, in training, updates the running statistics. grid = (blocks over L, C, B)
+template <int MAXG>
 __global__ __launch_bounds__(256) void cn_bn_group_apply_kernel(const CnBnGroupArgs a) {
   const int c = blockIdx.y, b = blockIdx.z;
-  float m[BN_MAX_GROUPS], sc[BN_MAX_GROUPS], be[BN_MAX_GROUPS];
+  float m[MAXG], sc[MAXG], be[MAXG];
   const double count = (double)a.B * a.L;
 #pragma unroll
-  for (int g = 0; g < BN_MAX_GROUPS; ++g) {
+  for (int g = 0; g < MAXG; ++g) {
     m[g] = sc[g] = be[g] = 0.f;
     if (g < a.G) {
       float rs;
       if (a.training) {
-        double s = 0.0, ss = 0.0;
-        const double* p = a.part + ((long)g * a.C + c) * a.splits * 2;
-        for (int i = 0; i < a.splits; ++i) {
-          s += p[2 * i];
-          ss += p[2 * i + 1];
-        }
+        double s, ss;
+        cn_bn_sum_parts(a.part + ((long)g * a.C + c) * a.splits * 2, a.splits, s, ss);
         const double md = s / count;
         double var = ss / count - md * md;
         if (var < 0.0) var = 0.0;
@@ -770,7 +529,7 @@ __global__ __launch_bounds__(256) void cn_bn_group_apply_kernel(const CnBnGroupA
     for (int l = blockIdx.x * 256 + threadIdx.x; l < (a.L >> 2); l += gridDim.x * 256) {
       float4 acc = rp ? reinterpret_cast<const float4*>(rp)[l] : z4;
 #pragma unroll
-      for (int g = 0; g < BN_MAX_GROUPS; ++g) {
+      for (int g = 0; g < MAXG; ++g) {
         if (g < a.G) {
           const float4 xv = reinterpret_cast<const float4*>(a.x[g] + b * a.xbs + r0)[l];
           float4 z;
@@ -790,7 +549,7 @@ __global__ __launch_bounds__(256) void cn_bn_group_apply_kernel(const CnBnGroupA
   for (int l = blockIdx.x * 256 + threadIdx.x; l < a.L; l += gridDim.x * 256) {
     float acc = rp ? rp[l] : 0.f;
 #pragma unroll
-    for (int g = 0; g < BN_MAX_GROUPS; ++g) {
+    for (int g = 0; g < MAXG; ++g) {
       if (g < a.G) {
         float z = (a.x[g][b * a.xbs + r0 + l] - m[g]) * sc[g] + be[g];
         if (a.act == 1) z = cn_silu(z);
@@ -802,9 +561,11 @@ __global__ __launch_bounds__(256) void cn_bn_group_apply_kernel(const CnBnGroupA
   }
 }
 
+// Backward pass 1: per-channel partial sums of dz and dz * xhat, dz = dy * act'(z). grid = (C, splits, G)
+template <int MAXG>
 __global__ __launch_bounds__(256) void cn_bn_group_bwd_partial_kernel(const CnBnGroupArgs a) {
   __shared__ double scratch[4];
-  const int c = blockIdx.x, sp = blockIdx.y, g = blockIdx.z;
+  const int c = blockIdx.x, sp = blockIdx.y, g = MAXG == 1 ? 0 : blockIdx.z;
   const float m = a.mean[g][c], rs = a.rstd[g][c], ga = a.gamma[g][c], be = a.beta[g][c];
   double s1 = 0.0, s2 = 0.0;
   auto term = [&](float xv, float dv) {
@@ -846,16 +607,16 @@ __global__ __launch_bounds__(256) void cn_bn_group_bwd_partial_kernel(const CnBn
   }
 }
 
-// grid = (blocks over L x G, C, B)
+// Backward pass 2: dx (+)= gamma*rstd*(dz - mean(dz) - xhat*mean(dz*xhat))   [train]
+//                  dx (+)= gamma*rstd*dz                                        [eval]
+// Every block reduces its channel's partial rows itself; block (0, c, 0) of a group writes or accumulates dgamma /
+// dbeta. grid = (blocks over L x G, C, B), or (G, C, 1) when no group wants dx.
+template <int MAXG>
 __global__ __launch_bounds__(256) void cn_bn_group_bwd_apply_kernel(const CnBnGroupArgs a, int bx_per_group) {
-  const int g = blockIdx.x / bx_per_group, bx = blockIdx.x - g * bx_per_group;
+  const int g = MAXG == 1 ? 0 : blockIdx.x / bx_per_group, bx = blockIdx.x - g * bx_per_group;
   const int c = blockIdx.y, b = blockIdx.z;
-  double s1 = 0.0, s2 = 0.0;
-  const double* p = a.part + ((long)g * a.C + c) * a.splits * 2;
-  for (int i = 0; i < a.splits; ++i) {
-    s1 += p[2 * i];
-    s2 += p[2 * i + 1];
-  }
+  double s1, s2;
+  cn_bn_sum_parts(a.part + ((long)g * a.C + c) * a.splits * 2, a.splits, s1, s2);
   if (bx == 0 && b == 0 && threadIdx.x == 0) {
     if (a.accumulate_params) {
       a.dgamma[g][c] += (float)s2;
@@ -901,6 +662,95 @@ __global__ __launch_bounds__(256) void cn_bn_group_bwd_apply_kernel(const CnBnGr
   for (int l = bx * 256 + threadIdx.x; l < a.L; l += bx_per_group * 256) dxp[l] = grad(xp[l], dp[l], acc ? dxp[l] : 0.f);
 }
 
+// May a call use 16-byte accesses? L and every batch stride a multiple of 4 floats, every plane base 16-byte aligned.
+// tabs: pointer tables of CnBnGroupArgs (unused slots are NULL and pass, as a NULL `one` does). One flag covers both
+// passes of a call.
+static int bn_vec4(int L, std::initializer_list<long> strides, std::initializer_list<const float* const*> tabs,
+                   const float* one = nullptr) {
+  bool ok = L % 4 == 0 && reinterpret_cast<uintptr_t>(one) % 16 == 0;
+  for (long s : strides) ok = ok && s % 4 == 0;
+  for (const float* const* t : tabs)
+    for (int g = 0; g < BN_MAX_GROUPS; ++g) ok = ok && reinterpret_cast<uintptr_t>(t[g]) % 16 == 0;
+  return ok;
+}
+
+// The argument block of a single call: G = 1 and up to BN_SPLIT_MAX partial rows. The forward and the backward entry
+// add their own operands.
+static CnBnGroupArgs bn_single_args(const float* x, long xbs, const float* gamma, const float* beta, const float* mean,
+                                    const float* rstd, double* ws, int B, int C, int L, int training, int act) {
+  CnBnGroupArgs a = {};
+  a.x[0] = x; a.gamma[0] = gamma; a.beta[0] = beta;
+  a.mean[0] = const_cast<float*>(mean); a.rstd[0] = const_cast<float*>(rstd);
+  a.xbs = xbs; a.G = 1; a.B = B; a.C = C; a.L = L; a.act = act; a.training = training;
+  a.part = ws; a.splits = bn_splits_wide(C, L);
+  return a;
+}
+
+// A two-pass kernel on 256 threads: the instance of a single call or the grouped one.
+#define BN_2P_LAUNCH(kernel_, grid_, ...)                                                           \
+  do {                                                                                              \
+    if (a.G == 1) CN_LAUNCH((kernel_<1>), grid_, dim3(256), 0, stream, a, ##__VA_ARGS__);           \
+    else CN_LAUNCH((kernel_<BN_MAX_GROUPS>), grid_, dim3(256), 0, stream, a, ##__VA_ARGS__);        \
+  } while (0)
+
+// Forward of a filled argument block: resident where bn_resident_plan allows, else the partial sums (training only) and
+// the apply launch.
+static int bn_forward(CnBnGroupArgs& a, hipStream_t stream) {
+  for (int g = 0; g < a.G; ++g)
+    if (!a.training && (a.running_mean[g] == nullptr || a.running_var[g] == nullptr)) return CN_ERR_ARG;
+  a.vec4 = bn_vec4(a.L, {a.xbs, a.ybs, a.res ? a.rbs : 0}, {a.x, a.y}, a.res);
+  if (a.training) {
+    const CnBnPlan p = bn_resident_plan(false, a.G, a.sum_outputs != 0, a.B, a.C, a.L, a.vec4 != 0);
+    if (p.NV != 0 && bn_resident_launch<false>(p, a, stream)) return cn_check_launch();
+    BN_2P_LAUNCH(cn_bn_group_partial_kernel, dim3(a.C, a.splits, a.G));
+  }
+  BN_2P_LAUNCH(cn_bn_group_apply_kernel, plane_grid(a.B, a.C, a.L));
+  return cn_check_launch();
+}
+
+// Backward of a filled argument block. With no dx wanted at all the apply launch shrinks to one block per channel and
+// group: the parameter gradients alone.
+static int bn_backward(CnBnGroupArgs& a, hipStream_t stream) {
+  bool any_dx = false;
+  for (int g = 0; g < a.G; ++g) any_dx |= a.dx[g] != nullptr;
+  a.vec4 = bn_vec4(a.L, {a.xbs, a.dybs, any_dx ? a.dxbs : 0}, {a.x, a.dy, a.dx});
+  const CnBnPlan p = bn_resident_plan(true, a.G, false, a.B, a.C, a.L, a.vec4 != 0);
+  if (p.NV != 0 && bn_resident_launch<true>(p, a, stream)) return cn_check_launch();
+  const dim3 pg = any_dx ? plane_grid(a.B, a.C, a.L) : dim3(1, a.C, 1);
+  BN_2P_LAUNCH(cn_bn_group_bwd_partial_kernel, dim3(a.C, a.splits, a.G));
+  BN_2P_LAUNCH(cn_bn_group_bwd_apply_kernel, dim3(pg.x * a.G, pg.y, pg.z), (int)pg.x);
+  return cn_check_launch();
+}
+
+// Forward. x,y viewed as [B][C][L] (L = H*W for BatchNorm2d, T*H*W for BatchNorm3d).
+// training != 0: batch statistics (saved to mean/rstd [C]) and running stats updated in place; == 0: the running
+// statistics (required), copied to mean / rstd for the backward. ws: workspace of cn_bn_workspace_doubles(C) doubles.
+extern "C" int cn_bn_act_fwd_f32(const float* x, long xbs, const float* gamma, const float* beta,
+                                 float* running_mean, float* running_var, const float* res, long rbs, float* y,
+                                 long ybs, float* mean, float* rstd, double* ws, int B, int C, int L, int training,
+                                 float momentum, float eps, int act, void* stream_) {
+  if (B <= 0 || C <= 0 || L <= 0) return CN_OK;
+  CnBnGroupArgs a = bn_single_args(x, xbs, gamma, beta, mean, rstd, ws, B, C, L, training, act);
+  a.running_mean[0] = running_mean; a.running_var[0] = running_mean != nullptr ? running_var : nullptr;
+  a.y[0] = y; a.ybs = ybs; a.res = res; a.rbs = rbs; a.sum_outputs = res != nullptr;  // y = res + act(bn(x))
+  a.eps = eps; a.momentum = momentum;
+  return bn_forward(a, (hipStream_t)stream_);
+}
+
+// Backward. dgamma/dbeta (+)= per accumulate_params; dx (+)= per accumulate_dx; dx may be NULL (parameters only).
+// coef: unused, kept for the ABI (may be NULL); ws as in forward.
+extern "C" int cn_bn_act_bwd_f32(const float* x, long xbs, const float* dy, long dybs, const float* mean,
+                                 const float* rstd, const float* gamma, const float* beta, float* dx, long dxbs,
+                                 float* dgamma, float* dbeta, float* coef, double* ws, int B, int C, int L,
+                                 int training, int act, int accumulate_dx, int accumulate_params, void* stream_) {
+  (void)coef;
+  if (B <= 0 || C <= 0 || L <= 0) return CN_OK;
+  CnBnGroupArgs a = bn_single_args(x, xbs, gamma, beta, mean, rstd, ws, B, C, L, training, act);
+  a.dy[0] = dy; a.dybs = dybs; a.dx[0] = dx; a.dxbs = dxbs; a.accumulate_dx[0] = accumulate_dx;
+  a.dgamma[0] = dgamma; a.dbeta[0] = dbeta; a.accumulate_params = accumulate_params;
+  return bn_backward(a, (hipStream_t)stream_);
+}
+
 // Host arrays of G device pointers; ws: G * cn_bn_workspace_doubles(C) doubles.
 // sum_outputs == 0: ys[g] = act(bn_g(xs[g])) (res must be NULL); != 0: ys[0] = res + sum_g act(bn_g(xs[g])).
 extern "C" int cn_bn_act_group_fwd_f32(int G, const float* const* xs, long xbs, const float* const* gammas,
@@ -909,7 +759,6 @@ extern "C" int cn_bn_act_group_fwd_f32(int G, const float* const* xs, long xbs, 
                                        long ybs, float* const* means, float* const* rstds, double* ws, int B, int C,
                                        int L, int training, float momentum, float eps, int act, int sum_outputs,
                                        void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
   if (G < 1 || G > BN_MAX_GROUPS || (!sum_outputs && res != nullptr)) return CN_ERR_ARG;
   if (B <= 0 || C <= 0 || L <= 0) return CN_OK;
   CnBnGroupArgs a = {};
@@ -917,7 +766,6 @@ extern "C" int cn_bn_act_group_fwd_f32(int G, const float* const* xs, long xbs, 
     a.x[g] = xs[g]; a.gamma[g] = gammas[g]; a.beta[g] = betas[g];
     a.running_mean[g] = running_means ? running_means[g] : nullptr;
     a.running_var[g] = running_vars ? running_vars[g] : nullptr;
-    if (!training && (a.running_mean[g] == nullptr || a.running_var[g] == nullptr)) return CN_ERR_ARG;
     a.mean[g] = means[g]; a.rstd[g] = rstds[g];
     a.y[g] = sum_outputs ? ys[0] : ys[g];
   }
@@ -925,18 +773,7 @@ extern "C" int cn_bn_act_group_fwd_f32(int G, const float* const* xs, long xbs, 
   a.G = G; a.B = B; a.C = C; a.L = L; a.act = act; a.training = training; a.sum_outputs = sum_outputs;
   a.eps = eps; a.momentum = momentum; a.part = ws;
   a.splits = bn_splits(C * G, L);
-  a.vec4 = (L % 4 == 0) && xbs % 4 == 0 && ybs % 4 == 0 && (res == nullptr || rbs % 4 == 0) &&
-           (reinterpret_cast<uintptr_t>(res) & 15) == 0;
-  for (int g = 0; g < G; ++g)
-    if ((reinterpret_cast<uintptr_t>(a.x[g]) | reinterpret_cast<uintptr_t>(a.y[g])) & 15) a.vec4 = 0;
-  if (training) {
-    const CnBnPlan p = bn_resident_plan(false, G, sum_outputs != 0, B, C, L, a.vec4 != 0);
-    if (p.NV != 0 && bn_resident_launch<false>(p, a, stream)) return cn_check_launch();
-  }
-  if (training)
-    CN_LAUNCH(cn_bn_group_partial_kernel, dim3(C, a.splits, G), dim3(256), 0, stream, a);
-  CN_LAUNCH(cn_bn_group_apply_kernel, plane_grid(B, C, L), dim3(256), 0, stream, a);
-  return cn_check_launch();
+  return bn_forward(a, (hipStream_t)stream_);
 }
 
 // dys: per-group output gradients (the same pointer G times after a summed forward). dxs[g] may be NULL.
@@ -946,7 +783,6 @@ extern "C" int cn_bn_act_group_bwd_f32(int G, const float* const* xs, long xbs, 
                                        long dxbs, const int* accumulate_dx, float* const* dgammas,
                                        float* const* dbetas, double* ws, int B, int C, int L, int training, int act,
                                        int accumulate_params, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
   if (G < 1 || G > BN_MAX_GROUPS) return CN_ERR_ARG;
   if (B <= 0 || C <= 0 || L <= 0) return CN_OK;
   CnBnGroupArgs a = {};
@@ -960,17 +796,7 @@ extern "C" int cn_bn_act_group_bwd_f32(int G, const float* const* xs, long xbs, 
   a.G = G; a.B = B; a.C = C; a.L = L; a.act = act; a.training = training; a.accumulate_params = accumulate_params;
   a.part = ws;
   a.splits = bn_splits(C * G, L);
-  a.vec4 = (L % 4 == 0) && xbs % 4 == 0 && dybs % 4 == 0 && dxbs % 4 == 0;
-  for (int g = 0; g < G; ++g)
-    if ((reinterpret_cast<uintptr_t>(a.x[g]) | reinterpret_cast<uintptr_t>(a.dy[g]) |
-         reinterpret_cast<uintptr_t>(a.dx[g])) & 15)
-      a.vec4 = 0;
-  const CnBnPlan p = bn_resident_plan(true, G, false, B, C, L, a.vec4 != 0);
-  if (p.NV != 0 && bn_resident_launch<true>(p, a, stream)) return cn_check_launch();
-  const dim3 pg = plane_grid(B, C, L);
-  CN_LAUNCH(cn_bn_group_bwd_partial_kernel, dim3(C, a.splits, G), dim3(256), 0, stream, a);
-  CN_LAUNCH(cn_bn_group_bwd_apply_kernel, dim3(pg.x * G, pg.y, pg.z), dim3(256), 0, stream, a, (int)pg.x);
-  return cn_check_launch();
+  return bn_backward(a, (hipStream_t)stream_);
 }
 
 // ---------------------------------------------------------------------------

@@ -569,7 +569,6 @@ def bn_act(x: Var, bn, act: int, residual: T.Optional[Var] = None, channels: T.O
             s = _stream()
             if residual is not None:
                 give_grad(residual, dy)
-            coef = _new((2 * C,), xt)
             if x.req:
                 dx, acc = grad_buffer(x)
                 dxp, dxbs = dx.data_ptr(), bstride(dx)
@@ -577,7 +576,7 @@ def bn_act(x: Var, bn, act: int, residual: T.Optional[Var] = None, channels: T.O
                 dxp, dxbs, acc = None, 0, 0
             _lib.call("cn_bn_act_bwd_f32", xt.data_ptr(), bstride(xt), dy.data_ptr(), bstride(dy), mean.data_ptr(),
                       rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), dxp, dxbs, store.grad_of(gamma).data_ptr(),
-                      store.grad_of(beta).data_ptr(), coef.data_ptr(), ws.data_ptr(), B, C, L, 1 if use_batch else 0,
+                      store.grad_of(beta).data_ptr(), None, ws.data_ptr(), B, C, L, 1 if use_batch else 0,
                       act, acc, 1, s)
             yv.grad = None
 

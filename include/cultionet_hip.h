@@ -149,8 +149,11 @@ int cn_channel_sum_f32(const float* x, long xbs, int B, int C, int L, float* out
 
 /* ---- nn.BatchNorm2d / BatchNorm3d (+ SiLU, + residual add) (convolution.py:71-120, nunet.py:18-57)
  * tensors viewed as [B][C][L]; act: 0 none, 1 SiLU; y = act(bn(x)) (+ res).
- * training: batch stats saved to mean/rstd[C], running stats updated (momentum, unbiased var).
- * ws: cn_bn_workspace_doubles(C) doubles; coef: 2*C floats scratch. */
+ * training: batch stats saved to mean/rstd[C], running stats updated (momentum, unbiased var; running_mean NULL: no
+ * update). training == 0: the running statistics normalise and are copied to mean/rstd; without them CN_ERR_ARG.
+ * ws: cn_bn_workspace_doubles(C) doubles; coef: unused, kept for the ABI, may be NULL.
+ * A single call is the grouped call below with G = 1 and the residual as its sum: the same kernels run both, resident
+ * (one launch per pass) where a channel fits a block, else two launches (one for the eval forward). */
 int cn_bn_workspace_doubles(int C);
 int cn_bn_act_fwd_f32(const float* x, long xbs, const float* gamma, const float* beta, float* running_mean,
                       float* running_var, const float* res /*nullable*/, long rbs, float* y, long ybs, float* mean,
@@ -165,8 +168,10 @@ int cn_bn_act_bwd_f32(const float* x, long xbs, const float* dy, long dybs, cons
  * branches of ResidualAConv, convolution.py:376-395). All pointer arguments ending in `s` are HOST arrays of G device
  * pointers. sum_outputs == 0: ys[g] = act(bn_g(xs[g])), res must be NULL. sum_outputs != 0: the ResUNet-a sum
  * ys[0] = res + sum_g act(bn_g(xs[g])) fused into the normalisation pass. ws: G * cn_bn_workspace_doubles(C) doubles.
+ * training == 0 needs the running statistics of every layer (else CN_ERR_ARG).
  * Backward: dys[g] = gradient of output g (the same pointer G times after a summed forward; the residual's gradient
- * is that tensor itself); dxs[g] nullable; accumulate_dx: HOST array of G flags. */
+ * is that tensor itself); dxs[g] nullable (all NULL: the parameter gradients alone, on a small grid); accumulate_dx:
+ * HOST array of G flags. */
 int cn_bn_act_group_fwd_f32(int G, const float* const* xs, long xbs, const float* const* gammas,
                             const float* const* betas, float* const* running_means, float* const* running_vars,
                             const float* res /*nullable*/, long rbs, float* const* ys, long ybs, float* const* means,

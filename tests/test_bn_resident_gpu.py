@@ -1,6 +1,8 @@
 """The single-launch ("resident") fp32 BatchNorm kernels of cn_norm.hip and the rule that chooses between them and the
 two-pass kernels -- which keep the channels that do not fit a block, also behind one dy for all groups -- against the
-float64 restatement of tests/test_norm_ref.py (bn_fwd64, bn_bwd64) through the C ABI.
+float64 restatement of tests/test_norm_ref.py (bn_fwd64, bn_bwd64) through the C ABI. The single-tensor and the
+grouped entry points run the same kernels, resident and two-pass: the cases reach both through either entry, and
+test_bn_single_equals_grouped_g1 asks for identical bits from the two.
 
 Every comparison is per element with the bound forms of tests/test_norm_gpu.py's docstring (c = 16, u = 2^-24, D = 0:
 the sums are fp64), through that file's _bn_check. Each case names the number of launches it expects from
@@ -118,7 +120,7 @@ CASES = {
     "bwd_params_write_shared": _case(2, 3, 5, 64, summed=True, acc_params=0, null=1),
     "eval_G2": _case(2, 3, 5, 64, training=0, fwd=1, bwd=1),  # the eval forward is the apply kernel alone
     "eval_G2_shared": _case(2, 3, 5, 64, training=0, summed=True, res=True, fwd=1, bwd=1),
-    "eval_one": _case(1, 3, 5, 64, training=0, single=True, fwd=2, bwd=1),
+    "eval_one": _case(1, 3, 5, 64, training=0, single=True, fwd=1, bwd=1),
     # channels that fit no block, behind one dy for all groups: the two-pass kernels
     "twopass_shared_G2": _case(2, 8, 4, 10000, summed=True, res=True, fwd=2, bwd=2),
     "twopass_shared_G3_mixed": _case(3, 3, 4, 10000, summed=True, acc=(1, 0, 0), null=2, fwd=2, bwd=2),
@@ -126,6 +128,16 @@ CASES = {
     "twopass_shared_scalar": _case(2, 5, 4, 2501, summed=True, res=True, acc=(0, 1), fwd=2, bwd=2),
     "twopass_shared_params_write": _case(2, 3, 4, 10000, summed=True, acc_params=0, null=0, fwd=2, bwd=2),
     "twopass_shared_eval": _case(2, 3, 4, 10000, summed=True, training=0, fwd=1, bwd=2),
+    "twopass_all_null": _case(2, 3, 4, 10000, null="all", fwd=2, bwd=2),  # no dx at all: one block per channel and group
+    # the same two-pass kernels through the single entry points (4 blocks of 30 000 values; 12 505 and 22 509 dwords)
+    "one_twopass": _case(1, 3, 4, 10000, single=True, res=True, fwd=2, bwd=2),
+    # 12 505 dword values fit the forward's largest block shape (20 480), not the backward's (10 240)
+    "one_twopass_scalar": _case(1, 5, 4, 2501, single=True, res=True, acc=(1,), fwd=1, bwd=2),
+    "one_twopass_scalar_fwd": _case(1, 9, 4, 2501, single=True, res=True, acc=(1,), fwd=2, bwd=2),
+    "one_twopass_gaps": _case(1, 3, 4, 10000, single=True, layout="gaps", fwd=2, bwd=2),
+    "one_twopass_odd": _case(1, 3, 4, 10000, single=True, layout="odd", fwd=2, bwd=2),  # L % 4 == 0 on dwords
+    "one_twopass_params_write": _case(1, 3, 4, 10000, single=True, null=0, acc_params=0, fwd=2, bwd=2),
+    "one_twopass_eval": _case(1, 3, 4, 10000, single=True, training=0, fwd=1, bwd=2),
 }
 
 
@@ -185,7 +197,7 @@ def test_bn_resident_vs_float64(name):
     ws = torch.full((G * _lib.query("cn_bn_workspace_doubles", C),), NAN, dtype=torch.float64, device=dev)
     coef = torch.full((2 * C,), NAN, device=dev)
     xbs, ybs, dybs, dxbs = x_in[0].stride(0), y_out[0][0].stride(0), dy_in[0].stride(0), dx_out[0][0].stride(0)
-    dx_ptr = [None if k["null"] == g else dx_out[g][0].data_ptr() for g in range(G)]
+    dx_ptr = [None if k["null"] in (g, "all") else dx_out[g][0].data_ptr() for g in range(G)]
     P = lambda ts: _tab([t.data_ptr() for t in ts])
 
     n0 = _launches()
@@ -228,7 +240,7 @@ def test_bn_resident_vs_float64(name):
         if not summed:
             got["y"] = y_out[g][0]
         ref = dict(bwds[g])
-        if k["null"] == g:
+        if k["null"] in (g, "all"):
             assert torch.isnan(dx_out[g][1]).all(), f"{name} layer {g}: no dx buffer was passed"
         else:
             got["dx"] = dx_out[g][0]
@@ -247,3 +259,54 @@ def test_bn_resident_vs_float64(name):
             dm, _, rrel = _bn_stat_allowance(fwds[g], bool(training), 0)
             bound = bound + _bn_y_bound(fwds[g], xs[g].double(), gammas[g], betas[g], ress[g], dm, rrel)
         _within(y_out[0][0], y_sum, bound, f"{name} sum")
+
+
+@pytest.mark.parametrize("training", [1, 0], ids=["train", "eval"])
+@pytest.mark.parametrize("res", [False, True], ids=["plain", "res"])
+@pytest.mark.parametrize("B,C,L", [(3, 4, 10000), (5, 4, 2501)])
+def test_bn_single_equals_grouped_g1(B, C, L, res, training):
+    """One body: cn_bn_act_{fwd,bwd}_f32 and cn_bn_act_group_{fwd,bwd}_f32 with G = 1 (sum_outputs = 1 where there is a
+    residual) give bit-identical y, mean, rstd, running statistics, dx, dgamma and dbeta on the same inputs. At both
+    shapes the two entries cut a channel into the same number of partial rows (20 and 5: both capped by
+    (L + 511) / 512), so equal kernels see equal arguments. Outputs start as NaN: torch.equal fails on a value left
+    unwritten."""
+    from cultionet_amd import _lib
+
+    dev = _dev()
+    gen = torch.Generator().manual_seed(C * 1000 + L)
+    x = _x(B, C, L, 10)
+    gamma = (1 + 0.2 * torch.randn(C, generator=gen)).to(dev)
+    beta = (0.2 * torch.randn(C, generator=gen)).to(dev)
+    old_m, old_v = (0.2 * torch.randn(C, generator=gen)).to(dev), (0.5 + torch.rand(C, generator=gen)).to(dev)
+    r = _randn((B, C, L), 90) if res else None
+    dy = _randn((B, C, L), 100)
+    rp, rbs = (r.data_ptr(), r.stride(0)) if res else (None, 0)
+    nan = lambda *shape: torch.full(shape, NAN, device=dev)
+
+    def run(single):
+        o = dict(y=nan(B, C, L), mean=nan(C), rstd=nan(C), running_mean=old_m.clone(), running_var=old_v.clone(),
+                 dx=nan(B, C, L), dgamma=nan(C), dbeta=nan(C))
+        ws = torch.full((_lib.query("cn_bn_workspace_doubles", C),), NAN, dtype=torch.float64, device=dev)
+        bs = x.stride(0)
+        if single:
+            _lib.call("cn_bn_act_fwd_f32", x.data_ptr(), bs, gamma.data_ptr(), beta.data_ptr(),
+                      o["running_mean"].data_ptr(), o["running_var"].data_ptr(), rp, rbs, o["y"].data_ptr(), bs,
+                      o["mean"].data_ptr(), o["rstd"].data_ptr(), ws.data_ptr(), B, C, L, training, MOM, EPS, 1, _s())
+            _lib.call("cn_bn_act_bwd_f32", x.data_ptr(), bs, dy.data_ptr(), bs, o["mean"].data_ptr(),
+                      o["rstd"].data_ptr(), gamma.data_ptr(), beta.data_ptr(), o["dx"].data_ptr(), bs,
+                      o["dgamma"].data_ptr(), o["dbeta"].data_ptr(), None, ws.data_ptr(), B, C, L, training, 1, 0, 0,
+                      _s())
+        else:
+            P = lambda t: _tab([t.data_ptr()])
+            _lib.call("cn_bn_act_group_fwd_f32", 1, P(x), bs, P(gamma), P(beta), P(o["running_mean"]),
+                      P(o["running_var"]), rp, rbs, P(o["y"]), bs, P(o["mean"]), P(o["rstd"]), ws.data_ptr(), B, C, L,
+                      training, MOM, EPS, 1, 1 if res else 0, _s())
+            _lib.call("cn_bn_act_group_bwd_f32", 1, P(x), bs, P(dy), bs, P(o["mean"]), P(o["rstd"]), P(gamma), P(beta),
+                      P(o["dx"]), bs, (ctypes.c_int * 1)(0), P(o["dgamma"]), P(o["dbeta"]), ws.data_ptr(), B, C, L,
+                      training, 1, 0, _s())
+        torch.cuda.synchronize()
+        return o
+
+    one, grouped = run(True), run(False)
+    for key in one:
+        assert torch.equal(one[key], grouped[key]), f"{key}: the single and the grouped entry differ"

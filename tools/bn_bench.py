@@ -4,7 +4,8 @@ hooked, and every distinct call (groups, shape, strides, alignment, summed or no
 flags) is replayed on buffers of its own. Kernel durations come from torch.profiler (one call at a time on one stream,
 the operands rotating over several buffer sets so that no call finds its inputs in the caches); a call's time is the sum
 of its kernels. MB: the bytes the call's kernels move (one launch: every operand once; two launches: x and dy once per
-pass, dy once per pass and GROUP unless the kernels that loop the groups ran). Ends with the sum over one step.
+pass, dy once per pass and GROUP unless the kernels that loop the groups ran). Four single calls that a step may not
+make (fixed_rows) are timed as well, with n/step 0. Ends with the sum over one step.
 
     python tools/bn_bench.py [out.txt] [reps] [label]      (CN_LIB_PATH selects the library build)"""
 import ctypes
@@ -204,7 +205,23 @@ def label(d):
     return t + ("" if d["aligned"] and d["L"] % 4 == 0 else " dword") + ("" if d["train"] else " eval")
 
 
+def fixed_rows():
+    """Single calls on the two-pass kernels that a default step may not make (n/step 0 then: outside the step's sum):
+    the BatchNorm3d view of the time reduction both ways, an eval forward and a backward of 32 channels at 100 x 100."""
+    def fwd(C, L, train):
+        return dict(kind="fwd", G=1, B=8, C=C, L=L, train=train, act=1, summed=0, res=False, strides=(C * L, C * L, 0),
+                    aligned=True, single=1)
+
+    def bwd(C, L):
+        return dict(kind="bwd", G=1, B=8, C=C, L=L, train=1, act=1, shared=False, acc=(0,), null=(False,),
+                    strides=(C * L, C * L, C * L), aligned=True, single=1)
+
+    return [fwd(3, 120000, 1), bwd(3, 120000), fwd(32, 10000, 0), bwd(32, 10000)]
+
+
 calls = step_calls()
+for d in fixed_rows():
+    calls.setdefault(tuple(sorted(d.items())), 0)
 lines = [f"library: {LABEL}",
          f"{'call':<44}{'n/step':>7}{'launches':>9}{'median us':>11}{'min':>8}{'max':>8}{'MB':>8}{'GB/s':>8}  kernels"]
 total = 0.0
