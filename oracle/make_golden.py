@@ -10,6 +10,9 @@ calc_loss, autograd) on PyTorch-CPU fp32 with key-seeded weights
 (oracle.towerunet_oracle.seeded_state_dict) and seeded inputs (seeded_batch), so
 the GPU box can rebuild identical weights/inputs without a weight file. The
 fixtures hold inputs' seeds and expected outputs only (data, no source).
+
+--f64-only writes f64_<name>.npz: the same reference code, weights and inputs in float64, for the cases
+tests/test_oracle_golden.py pins. It writes no fp32 fixture.
 """
 from __future__ import annotations
 
@@ -107,6 +110,78 @@ def _train_case(ns, hidden, B, H, W, with_mask, seed=7, stages=False, loss_name=
     return out
 
 
+# The cases of tests/test_oracle_golden.py::test_oracle_train_matches_reference_vectors, with the arguments main() writes
+# their fp32 fixtures with: name -> ((hidden, B, H, W, with_mask), keywords of _train_case)
+F64_TRAIN_CASES = {
+    "train_h8_b2_28": ((8, 2, 28, 28, False), {}),
+    "train_h8_b2_28_masked": ((8, 2, 28, 28, True), {}),
+    "train_h8_b2_28_tanimoto": ((8, 2, 28, 28, True), {"loss_name": "TanimotoDistLoss"}),
+    "train_h8_b2_28_combined": ((8, 2, 28, 28, True), {"loss_name": "TanimotoCombined"}),
+    "train_h8_b2_28_noattn": ((8, 2, 28, 28, False), {"attention_weights": None}),
+    "train_h8_b2_28_dil3": ((8, 2, 28, 28, False), {"dilations": [1, 3]}),
+    "train_h32_b1_100_masked": ((32, 1, 100, 100, True), {}),
+    "train_h8_b2_28_poolmax": ((8, 2, 28, 28, True), {"pool_by_max": True}),
+    "train_h8_b2_28_res": ((8, 2, 28, 28, False), {"res_block_type": "res", "attention_weights": None}),
+    "train_h8_b2_28_bnfirst": ((8, 2, 28, 28, False), {"batchnorm_first": True}),
+    "train_h8_b2_28_sca": ((8, 2, 28, 28, True), {"attention_weights": "spatial_channel"}),
+}
+
+
+def _train_case_f64(ns, hidden, B, H, W, with_mask, seed=7, loss_name="TanimotoComplementLoss", **kw):
+    """The step of _train_case with the reference model, the inputs and the loss in float64 (`.double()` of the same
+    key-seeded fp32 weights and seeded fp32 inputs: every value is carried over exactly). fp32 runs of this model differ
+    from one another by up to 1.5e-5 through the order of ATen's sums alone; in double that becomes ~1e-14, so these
+    vectors pin the oracle's STRUCTURE on any machine (tests/test_oracle_golden.py: 1e-10). Maps, losses, gradient norms
+    and the recorded BatchNorm running statistics only -- no stages, no probes."""
+    m = _ref_model(ns, hidden, loss_name=loss_name, **kw).double()
+    m.train()
+    x, y, bdist = O.seeded_batch(B, height=H, width=W, seed=seed, with_mask=with_mask)
+    batch = ns.Data(x=x.double(), y=y, bdist=bdist.double(), lon=torch.zeros(B), lat=torch.zeros(B))
+    pred = m(batch)
+    loss, rep = m.calc_loss(batch, pred)
+    loss.backward()
+    out = {}
+    for k in ("distance", "edge", "crop"):
+        assert pred[k].dtype == torch.float64, (k, pred[k].dtype)  # nothing on the path fell back to fp32
+        out[k] = pred[k].detach().numpy().copy()
+    assert loss.dtype == torch.float64
+    out["loss"] = np.float64(loss.item())
+    for k, v in rep.items():
+        out[k] = np.float64(v.item())
+    names, norms = [], []
+    for n, p in m.named_parameters():
+        assert p.grad.dtype == torch.float64
+        names.append(n.replace("cultionet_TowerUNet.mask_model.", ""))
+        norms.append(float(p.grad.norm()))
+    out["grad_names"] = np.array(names)
+    out["grad_norms"] = np.array(norms, dtype=np.float64)
+    sd = m.state_dict()
+    k0 = next(k for k in sd if "tower_fusion.tower_a.res_conv" in k and k.endswith("running_mean"))[:-len("running_mean")]
+    out["bn_key"] = np.array(k0.replace("cultionet_TowerUNet.mask_model.", ""))
+    out["bn_running_mean"] = sd[k0 + "running_mean"].numpy().copy()
+    out["bn_running_var"] = sd[k0 + "running_var"].numpy().copy()
+    assert out["bn_running_mean"].dtype == np.float64
+    out["meta"] = np.array([hidden, B, H, W, int(with_mask), seed])
+    return out
+
+
+def _eval_case_f64(ns, hidden, B, C, T, H, W, seed=11):
+    """_eval_case in float64: the calibration pass and the eval forward both in double; the three whole maps."""
+    m = _ref_model(ns, hidden, in_channels=C, in_time=T).double()
+    xc, yc, bc = O.seeded_batch(B, channels=C, time=T, height=H, width=W, seed=seed + 1000)
+    cal = ns.Data(x=xc.double(), y=yc, bdist=bc.double(), lon=torch.zeros(B), lat=torch.zeros(B))
+    calibrate_bn(m, lambda: m(cal))
+    x, y, bdist = O.seeded_batch(B, channels=C, time=T, height=H, width=W, seed=seed)
+    batch = ns.Data(x=x.double(), y=y, bdist=bdist.double(), lon=torch.zeros(B), lat=torch.zeros(B))
+    with torch.no_grad():
+        pred = m(batch)
+    out = {"meta": np.array([hidden, B, C, T, H, W, seed])}
+    for k in ("distance", "edge", "crop"):
+        assert pred[k].dtype == torch.float64
+        out[f"{k}_crop"] = pred[k].numpy().copy()
+    return out
+
+
 def calibrate_bn(model, forward):
     """Make the BatchNorm running statistics those of one train-mode pass (momentum 1.0), as a trained
     checkpoint's would be; with the raw key-seeded running stats eval-mode activations are not
@@ -161,6 +236,16 @@ def main():
         sd = m.state_dict()
         save("state_dict_keys_h32.npz", {"keys": np.array(list(sd.keys())),
                                          "shapes": np.array([",".join(map(str, v.shape)) for v in sd.values()])})
+        return
+    if "--f64-only" in sys.argv:
+        # the float64 twins of the cases tests/test_oracle_golden.py pins (f64_<name>.npz); the fp32 fixtures are not
+        # touched. A case the reference cannot run in double is reported and left without a twin.
+        for name, (args, kw) in F64_TRAIN_CASES.items():
+            try:
+                save(f"f64_{name}.npz", _train_case_f64(ns, *args, **kw))
+            except Exception as e:  # noqa: BLE001
+                print(f"f64_{name}: the reference does not run in float64: {type(e).__name__}: {e}")
+        save("f64_eval_h8_b2_28.npz", _eval_case_f64(ns, 8, 2, 3, 12, 28, 28))
         return
     if "--h64-only" in sys.argv:
         # the CLI default width (scripts/args.yml:220-226: hidden_channels 64)

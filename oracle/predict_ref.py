@@ -20,7 +20,14 @@ import numpy as np
 import torch
 
 
-def predict_scene(model, scene: np.ndarray, window_size: int, padding: int, mean=None, std=None) -> np.ndarray:
+def predict_scene(model, scene: np.ndarray, window_size: int, padding: int, mean=None, std=None,
+                  autocast: bool = False) -> np.ndarray:
+    """autocast=True: the eval forward under ``torch.autocast("cpu", dtype=torch.bfloat16)`` -- the reference's predict
+    precision is 16-mixed (CPU autocast has no fp16; bf16 is the MI355X-native flavour) -- with the three maps widened
+    to fp32 before the writer's arithmetic. Its distance from the fp32 mosaic is the reference's OWN bf16 spread on a
+    scene, the yardstick of the mixed-precision predict tests. The default is the fp32 forward."""
+    import contextlib
+
     C, Tn, H, W = scene.shape
     S = window_size + 2 * padding
     out = np.zeros((3, H, W), dtype=np.uint16)
@@ -39,9 +46,10 @@ def predict_scene(model, scene: np.ndarray, window_size: int, padding: int, mean
             x = np.clip(tile.astype(np.float32) / np.float32(10000.0), np.float32(1e-9), np.float32(1.0))
             if mean is not None:
                 x = (x - np.asarray(mean, np.float32).reshape(C, 1, 1, 1)) / np.asarray(std, np.float32).reshape(C, 1, 1, 1)
-            with torch.no_grad():
+            ctx = torch.autocast("cpu", dtype=torch.bfloat16) if autocast else contextlib.nullcontext()
+            with torch.no_grad(), ctx:
                 pred = model(torch.from_numpy(x.astype(np.float32))[None])
-            stack = np.concatenate([pred[k][0].numpy()[:, padding:padding + h, padding:padding + w]
+            stack = np.concatenate([pred[k][0].float().numpy()[:, padding:padding + h, padding:padding + w]
                                     for k in ("distance", "edge", "crop")], axis=0)
             out[:, r0:r0 + h, c0:c0 + w] = np.clip(stack * 10000.0, 0, 10000.0).astype(np.uint16)
     return out

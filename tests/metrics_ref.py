@@ -87,6 +87,40 @@ def out_bound(ref, n):
     return half_ulp32(ref) + n * 2.0 ** -52 * np.abs(ref) + 1e-12
 
 
+GRID = 1024  # grid_inputs: dist and bdist are k / GRID
+
+
+def grid_inputs(n, seed, lo=-1, hi=3):
+    """(dist, edge, crop, bdist, labels) with dist and bdist on the grid k / 1024 in [0, 1), edge and crop ~ U[0, 1),
+    labels in lo..hi. On that grid d = dist - bdist is a multiple of 2^-10 below 1 in size, so d, |d| (fp32) and d * d
+    (double, a multiple of 2^-20 below 1) are exact, and any partial sum of up to 2^20 of them is a multiple of 2^-20
+    below 2^20: 40 significant bits, exact in double. The kernel's two real sums are then the same double WHATEVER the
+    order of its additions (threads, blocks, atomics); grid_premise asserts all of this on the arrays themselves."""
+    rng = np.random.default_rng(seed)
+    dist, bdist = (rng.integers(0, GRID, n).astype(np.float32) / np.float32(GRID) for _ in range(2))
+    edge, crop = (rng.random(n, dtype=np.float32) for _ in range(2))
+    return dist, edge, crop, bdist, rng.integers(lo, hi + 1, n)
+
+
+def grid_premise(dist, bdist, labels):
+    """The premise under which the two real sums do not depend on the order of the additions, asserted on the inputs
+    (NaN is allowed where the label is -1: the kernel never reads those pixels into a sum): at most 2^20 pixels, every
+    valid dist and bdist is k / 1024 with 0 <= k < 1024, so that every |d| is a multiple of 2^-10 and every d^2 a
+    multiple of 2^-20, both below 1 -- each partial sum is an integer below 2^40 times 2^-20."""
+    dist, bdist = (np.asarray(a, dtype=np.float32).reshape(-1) for a in (dist, bdist))
+    valid = np.asarray(labels).reshape(-1) != -1
+    assert dist.size <= 1 << 20
+    for a in (dist[valid], bdist[valid]):
+        k = a.astype(np.float64) * GRID
+        assert np.array_equal(k, np.round(k)) and (k >= 0).all() and (k < GRID).all()
+    d = (dist[valid] - bdist[valid]).astype(np.float32)
+    assert np.array_equal(d.astype(np.float64), dist[valid].astype(np.float64) - bdist[valid].astype(np.float64))
+    ad, dd = np.abs(d).astype(np.float64), d.astype(np.float64) ** 2
+    for t, step in ((ad, 2.0 ** 10), (dd, 2.0 ** 20)):
+        assert np.array_equal(t * step, np.round(t * step)) and (t < 1.0).all()
+        assert t.size * step < 2.0 ** 53  # every partial sum is an integer below 2^53, counted in units of 1 / step
+
+
 def eval_cases(klass, seed=5, shape=(3, 37, 41)):
     """(name, dist, edge, crop, bdist, y) of test_eval_metrics_kernel_against_restatement for edge class `klass`, labels
     in -1..klass: random maps with and without masked pixels and the four degenerate confusion matrices -- no positive

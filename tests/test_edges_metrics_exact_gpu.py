@@ -420,13 +420,15 @@ def _plant_nans(arrays, at):
 def test_eval_metrics_f32_skips_nans_under_masked_labels():
     """NaN in dist / bdist / edge / crop at pixels labelled -1: all 7 outputs stay finite and equal, bit for bit, those
     of the NaN-free run (a kernel multiplying by the mask would turn 0 * NaN into NaN)."""
-    n, klass = 700, 2
-    dist, edge, crop, bdist, y = _metric_inputs(n, 330, hi=2)
+    n, klass = 700, 2  # three blocks add their partial sums atomically, in an order that changes from run to run
+    dist, edge, crop, bdist, y = M.grid_inputs(n, 330, hi=2)
     at = np.arange(40) * 17 + 5
     y[at] = -1
+    M.grid_premise(dist, bdist, y)  # the two real sums are exact in any order: equality of two runs is a theorem
     clean_c, clean_o = _metrics(dist, edge, crop, bdist, y, klass, 0.5)
     nd, nb, ne, nc = _plant_nans((dist, bdist, edge, crop), at)
     assert all(np.isnan(a).sum() >= 16 for a in (nd, nb, ne, nc))
+    M.grid_premise(nd, nb, y)
     counts, out = _metrics(nd, ne, nc, nb, y, klass, 0.5)
     ref_c = M.eval_counts_ref(nd, ne, nc, nb, y, klass, 0.5)
     _check_metrics("eval metrics NaN under masked labels", counts, out, ref_c, n)
@@ -452,8 +454,33 @@ def test_eval_metrics_f32_nans_at_valid_pixels():
     _check_metrics("eval metrics NaN at valid pixels", counts, out, ref_c, n)
     assert np.isnan(out[[0, 1, 6]]).all() and np.isfinite(out[2:6]).all()
     assert np.array_equal(counts[INTEGER_COUNTS], clean_c[INTEGER_COUNTS])
+    # two runs are compared bit for bit on grid inputs only: there the sums do not depend on the order of the atomics
+    dist, _, _, bdist, _ = M.grid_inputs(n, 341)
+    M.grid_premise(dist, bdist, y)
+    clean_c, clean_o = _metrics(dist, edge, crop, bdist, y, klass, 0.5)
     counts, out = _metrics(dist, ne, nc, bdist, y, klass, 0.5)
     assert np.array_equal(counts, clean_c) and np.array_equal(out.view(np.uint32), clean_o.view(np.uint32))
+
+
+# n = 257: two blocks; the capped grid: 1024 blocks race on the atomics and every thread loops twice
+@pytest.mark.parametrize("n", [257, 1024 * 256 + 777])
+@pytest.mark.parametrize("klass", [2, 3])
+def test_eval_metrics_f32_grid_inputs_equal_the_restatement(n, klass):
+    """dist and bdist on the grid k / 1024 (metrics_ref.grid_inputs): every |d| and d^2 and every partial sum of them is
+    exact in double (grid_premise asserts it), so the kernel's sums cannot depend on the order of its additions and
+    ALL ELEVEN counts must EQUAL the float64 restatement -- the two real sums included, which random inputs only bound
+    by n 2^-53. The seven outputs stay within metrics_ref.out_bound."""
+    if n > 1 << 18:
+        assert (n + 255) // 256 > 1024 and n > 1024 * 256
+    dist, edge, crop, bdist, y = M.grid_inputs(n, 360 + n % 1000 + klass)
+    assert set(np.unique(y).tolist()) == {-1, 0, 1, 2, 3}
+    M.grid_premise(dist, bdist, y)
+    ref_c = M.eval_counts_ref(dist, edge, crop, bdist, y, klass, 0.5)
+    assert ref_c[1] > 0 and ref_c[2] > 0 and ref_c[1] != ref_c[2]
+    counts, out = _metrics(dist, edge, crop, bdist, y, klass, 0.5)
+    print(f"EXACT eval metrics on the grid n={n} klass={klass}: {int((counts != ref_c).sum())} of 11 counts differ")
+    assert np.array_equal(counts, ref_c), f"counts {dict(zip(M.NAMES, counts))}, want {dict(zip(M.NAMES, ref_c))}"
+    _check_metrics(f"eval metrics on the grid n={n} klass={klass}", counts, out, ref_c, n)
 
 
 def test_eval_metrics_f32_all_masked_and_empty():

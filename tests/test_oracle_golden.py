@@ -2,10 +2,27 @@
 
 The vectors in tests/golden were produced by the REAL reference (stub-imported
 from /root/reference by oracle/make_golden.py). This pins the oracle without
-needing /root/reference at run time. Tolerance: the oracle runs the same ATen
-kernels in the same order as the reference, so outputs are expected to be equal
-to ~1e-6 (exactly equal on the generating machine; thread-count dependent
-summation order elsewhere).
+needing /root/reference at run time.
+
+What the maps and stages are held to, and what that replaced. They were held to 2e-6 (stages 1e-5) of the fp32 vectors.
+That number held only in the summation order of the machine that wrote the vectors: the fp32 vectors themselves are
+1.5e-6 .. 1.5e-5 (stages: up to 3.3e-5) away from a float64 evaluation of the same model, so 2e-6 was below their own
+rounding error, and a different thread count or ATen build moved the oracle past it (up to 7.8e-6 on the maps) with
+nothing wrong. It pinned ATen's summation order, not the oracle. In its place, stated plainly as a trade of one number
+for another:
+
+  (1) structure: the oracle run in DOUBLE against the reference run in double (tests/golden/f64_<name>.npz, written by
+      oracle/make_golden.py --f64-only): maps, losses and running statistics to 1e-10, gradient norms to 1e-9 relative.
+      fp32 (u = 6e-8) runs of this model differ by up to 1.5e-5; the same amplification at u = 1.1e-16 gives ~3e-14, and
+      the double oracle moves by 1e-14 between thread counts: 1e-10 leaves three orders of margin and is four orders
+      tighter than 2e-6, on every machine.
+  (2) accuracy: with T the in-test double run, E_o = max |oracle fp32 - T| is at most 2 x E_G = max |vector fp32 - T|,
+      per map and per recorded stage. Both are fp32 evaluations of one function; measured over thread counts 1, 3, 8
+      and 16 the ratio stays below 1.4 on the maps and 1.7 on the stages. A stage vector must also lie within 1e-5 of
+      T relative to the stage's magnitude, so that it is known to be that stage.
+
+The losses, gradient norms, probes and running statistics keep their fp32 assertions against the fp32 vectors. Run with
+-s to read the E_o / E_G ratios.
 """
 import os
 
@@ -15,14 +32,29 @@ import torch
 
 from oracle import towerunet_oracle as O
 
-TOL = 2e-6
+TOL = 2e-6     # losses and running statistics in fp32
+TOL64 = 1e-10  # maps, losses and running statistics in double (gradient norms: 1e-9 of max(1, |norm|))
+ACCURACY = 2.0  # the oracle's fp32 error may be at most this many times the reference vectors' own fp32 error
+MAPS = ("distance", "edge", "crop")
 GOLDEN_THREADS = 8  # oracle/make_golden.py writes every fixture at torch.set_num_threads(8)
+
+
+def _fp32_no_worse_than_the_vectors(name, got32, golden32, truth64):
+    """E_G = max |reference fp32 vector - T| and E_o = max |oracle fp32 - T| per map (or stage), T the oracle's double
+    run (pinned to the reference's double run by the caller): both are fp32 evaluations of one function, so
+    E_o <= 2 E_G."""
+    for k in got32:
+        e_g = float(np.abs(golden32[k].astype(np.float64) - truth64[k]).max())
+        e_o = float(np.abs(got32[k].astype(np.float64) - truth64[k]).max())
+        print(f"BOUND {name} {k}: E_o {e_o:.3e} / E_G {e_g:.3e} = {e_o / e_g:.2f} (threads {torch.get_num_threads()})")
+        assert e_g > 0.0 and e_o <= ACCURACY * e_g, (name, k, e_o, e_g)
 
 
 @pytest.fixture(autouse=True)
 def _golden_thread_count():
-    """ATen's CPU reductions split by thread count, so the oracle reproduces the vectors to TOL only at the thread
-    count they were written with (other counts move the maps by ~3e-6), whatever the machine's core count."""
+    """ATen's CPU reductions split by thread count; at the count the vectors were written with the oracle reproduces
+    them most closely (on the generating machine bit for bit). No assertion needs it: the map and stage checks are
+    sized by the vectors' own error, and the file passes with 1, 3 and 16 here as well."""
     prev = torch.get_num_threads()
     torch.set_num_threads(GOLDEN_THREADS)
     yield
@@ -57,12 +89,35 @@ def _run_train(g, **model_kw):
 )
 def test_oracle_train_matches_reference_vectors(golden_dir, name, kw, loss_name):
     g = np.load(os.path.join(golden_dir, name + ".npz"))
+    g64 = np.load(os.path.join(golden_dir, "f64_" + name + ".npz"))
+    assert np.array_equal(g64["meta"], g["meta"]) and list(g64["grad_names"]) == list(g["grad_names"])
+    # (1) structure: the oracle in double against the reference in double
+    m64, x, y, bdist = _run_train(g, **kw)
+    m64 = m64.double()
+    truth, stages64 = m64(x.double(), return_stages=True)
+    loss64, rep64 = O.calc_loss(truth, y, bdist.double(), loss_name=loss_name)
+    loss64.backward()
+    truth = {k: truth[k].detach().numpy() for k in MAPS}
+    assert all(t.dtype == np.float64 for t in truth.values()) and loss64.dtype == torch.float64
+    for k in MAPS:
+        assert np.abs(truth[k] - g64[k]).max() <= TOL64, k
+    assert abs(loss64.item() - float(g64["loss"])) <= TOL64
+    for k in ("dloss", "eloss", "closs"):
+        assert abs(rep64[k].item() - float(g64[k])) <= TOL64, k
+    norms64 = {n: float(p.grad.norm()) for n, p in m64.named_parameters()}
+    for n, ref in zip(g64["grad_names"], g64["grad_norms"]):
+        assert abs(norms64[str(n)] - ref) <= 1e-9 * max(1.0, abs(ref)), n
+    sd64 = m64.state_dict()
+    assert str(g64["bn_key"]) == (str(g["bn_key"]) if "bn_key" in g.files else str(g64["bn_key"]))
+    for s in ("running_mean", "running_var"):
+        assert np.abs(sd64[str(g64["bn_key"]) + s].numpy() - g64["bn_" + s]).max() <= TOL64, s
+    # (2) accuracy in fp32: no further from the double run than twice the reference's own fp32 vectors are
     m, x, y, bdist = _run_train(g, **kw)
     pred, stages = m(x, return_stages=True)
     loss, rep = O.calc_loss(pred, y, bdist, loss_name=loss_name)
     loss.backward()
-    for k in ("distance", "edge", "crop"):
-        assert np.abs(pred[k].detach().numpy() - g[k]).max() <= TOL, k
+    _fp32_no_worse_than_the_vectors(name, {k: pred[k].detach().numpy() for k in MAPS}, {k: g[k] for k in MAPS},
+                                    truth)
     assert abs(loss.item() - float(g["loss"])) <= TOL
     for k in ("dloss", "eloss", "closs"):
         assert abs(rep[k].item() - float(g[k])) <= TOL
@@ -70,7 +125,12 @@ def test_oracle_train_matches_reference_vectors(golden_dir, name, kw, loss_name)
         if key.startswith("stage."):
             s = key[len("stage."):]
             s = {"pre_unet": "embeddings"}.get(s, s)
-            assert np.abs(stages[s].detach().numpy() - g[key]).max() <= 1e-5, key
+            t64 = stages64[s].detach().numpy()
+            # the vector IS this stage (a wrong tensor would be off by O(1)): 1e-5 relative to the stage's magnitude,
+            # the stages reach 13.5 ...
+            assert np.abs(g[key].astype(np.float64) - t64).max() <= 1e-5 * max(1.0, float(np.abs(t64).max())), key
+            # ... and the fp32 oracle is no worse on it than the vector (whose own error is up to 3.3e-5 here)
+            _fp32_no_worse_than_the_vectors(name, {key: stages[s].detach().numpy()}, {key: g[key]}, {key: t64})
     names = list(g["grad_names"])
     norms = {n: float(p.grad.double().norm()) for n, p in m.named_parameters()}
     for n, ref in zip(names, g["grad_norms"]):
@@ -100,8 +160,20 @@ def test_oracle_eval_matches_reference_vectors(golden_dir):
     x, _, _ = O.seeded_batch(B, channels=C, time=T, height=H, width=W, seed=seed)
     with torch.no_grad():
         pred = m(x)
-    for k in ("distance", "edge", "crop"):
-        assert np.abs(pred[k].numpy() - g[f"{k}_crop"]).max() <= TOL
+    # the same in double, calibration pass included: the structure against the reference in double ...
+    g64 = np.load(os.path.join(golden_dir, "f64_eval_h8_b2_28.npz"))
+    assert np.array_equal(g64["meta"], g["meta"])
+    m64 = O.TowerUNet(C, T, hidden_channels=hidden)
+    m64.load_state_dict(O.seeded_state_dict(m64.state_dict()))
+    m64 = m64.double()
+    calibrate_bn(m64, lambda: m64(xc.double()))
+    with torch.no_grad():
+        truth = {k: v.numpy() for k, v in m64(x.double()).items() if k in MAPS}
+    for k in MAPS:
+        assert truth[k].dtype == np.float64 and np.abs(truth[k] - g64[f"{k}_crop"]).max() <= TOL64, k
+    # ... and the fp32 maps no further from it than twice the reference's own fp32 vectors are
+    _fp32_no_worse_than_the_vectors("eval_h8_b2_28", {k: pred[k].numpy() for k in MAPS},
+                                    {k: g[f"{k}_crop"] for k in MAPS}, truth)
 
 
 def test_state_dict_surface():

@@ -4,6 +4,8 @@ import numpy as np
 import pytest
 import torch
 
+import predict_bound_ref as P
+
 pytestmark = pytest.mark.gpu
 
 
@@ -39,23 +41,40 @@ def test_sliding_window_predict_matches_restatement(H, W, ws, pad):
     assert got.shape == (3, H, W) and got.max() <= 10000
 
 
+def _yardstick(ref, scene, ws, pad, mean, std):
+    """(the oracle's fp32 mosaic, the reference's own bf16 spread on this scene): the nine statistics of
+    |oracle under CPU bf16 autocast - oracle fp32| (tests/predict_bound_ref.py), computed on the CPU."""
+    from oracle import predict_ref
+
+    s = scene.cpu().numpy().astype(np.float64)
+    want = predict_ref.predict_scene(ref, s, ws, pad, mean.numpy(), std.numpy())
+    cast = predict_ref.predict_scene(ref, s, ws, pad, mean.numpy(), std.numpy(), autocast=True)
+    return want, P.band_stats(cast, want)
+
+
 def test_sliding_window_predict_bf16_mixed():
-    """precision="bf16-mixed" (the reference's default predict precision is 16-mixed): same mosaic within the bf16
-    tolerance of the probabilities (2e-2 absolute = 200 counts worst case, mean well below 1e-2)."""
+    """precision="bf16-mixed" (the reference's default predict precision is 16-mixed): the same mosaic as the fp32 path
+    within 1.5 x the reference's own bf16 spread on this scene, for the mean, the 99.9th percentile and the max of every
+    band (the margin test_bf16_train_step_matches_reference gives), and a mean of at most 60 counts (6e-3).
+
+    A cap of 400 counts on the max stood here and failed at 431: the reference's own bf16 run of this scene moves the
+    fp32 mosaic by up to 484 counts, so that cap asked more of the kernels than the reference delivers."""
     from cultionet_amd.predict import SlidingWindowPredictor
 
-    lit, _ = _pair()
+    lit, ref = _pair()
     H, W, ws, pad = 70, 95, 40, 4
     g = torch.Generator().manual_seed(5)
     scene = torch.randint(0, 9000, (3, 12, H, W), generator=g, dtype=torch.int32).to(torch.int16).cuda()
     mean = torch.tensor([0.31, 0.28, 0.35])
     std = torch.tensor([0.21, 0.19, 0.24])
+    _, yard = _yardstick(ref, scene, ws, pad, mean, std)
     kw = dict(window_size=ws, padding=pad, batch_size=3, mean=mean, std=std)
     f32 = SlidingWindowPredictor(lit, **kw).predict_scene(scene).cpu().numpy().astype(np.int64)
     b16 = SlidingWindowPredictor(lit, precision="bf16-mixed", **kw).predict_scene(scene).cpu().numpy().astype(np.int64)
     d = np.abs(f32 - b16)
     assert b16.shape == (3, H, W) and b16.max() <= 10000
-    assert d.max() <= 400, d.max()
+    print(f"bf16-mixed against the fp32 path: max {d.max()}, mean {d.mean():.2f}")
+    P.assert_within_spread("predict bf16-mixed vs the fp32 path", P.band_stats(b16, f32), yard)
     assert d.mean() <= 60, d.mean()
     assert (b16 != f32).any()  # the bf16 path really ran
     with pytest.raises(ValueError):
@@ -66,9 +85,9 @@ def test_sliding_window_predict_bf16_mixed():
 def test_sliding_window_predict_bf16_mixed_vs_restatement(pack):
     """The `predict` headline path -- precision="bf16-mixed", fused inference ConvBlock2d, launch-plan replay, packed
     batches -- against the CPU restatement of the reference's predict path (oracle/predict_ref.py, fp32), not against
-    the repo's own fp32 mosaic: <= 400 counts max (4e-2 in probability), mean <= 60 counts (6e-3)."""
+    the repo's own fp32 mosaic: <= 400 counts max (4e-2 in probability), mean <= 60 counts (6e-3), and every one of
+    the nine band statistics within 1.5 x the reference's own bf16 spread on this scene."""
     from cultionet_amd.predict import SlidingWindowPredictor
-    from oracle import predict_ref
 
     lit, ref = _pair()
     H, W, ws, pad = 70, 95, 40, 4
@@ -76,15 +95,18 @@ def test_sliding_window_predict_bf16_mixed_vs_restatement(pack):
     scene = torch.randint(0, 9000, (3, 12, H, W), generator=g, dtype=torch.int32).to(torch.int16)
     mean = torch.tensor([0.31, 0.28, 0.35])
     std = torch.tensor([0.21, 0.19, 0.24])
-    want = predict_ref.predict_scene(ref, scene.numpy().astype(np.float64), ws, pad, mean.numpy(), std.numpy())
+    want, yard = _yardstick(ref, scene, ws, pad, mean, std)
     sp = SlidingWindowPredictor(lit, window_size=ws, padding=pad, batch_size=3, mean=mean, std=std,
                                 precision="bf16-mixed", pixels_per_launch=pack)
-    for _ in range(2):  # second call: the recorded launch plan is replayed
+    for call in range(2):  # second call: the recorded launch plan is replayed
         got = sp.predict_scene(scene.cuda()).cpu().numpy().astype(np.int64)
         d = np.abs(got - want.astype(np.int64))
         assert got.shape == (3, H, W) and got.max() <= 10000
+        print(f"bf16-mixed pack {pack} call {call} against the fp32 restatement: max {d.max()}, mean {d.mean():.2f}")
         assert d.max() <= 400, d.max()
         assert d.mean() <= 60, d.mean()
+        P.assert_within_spread(f"predict bf16-mixed pack {pack} call {call} vs the fp32 restatement",
+                               P.band_stats(got, want), yard)
 
 
 def _prologue_ref(raw, mean, std):

@@ -168,8 +168,11 @@ def test_dropin_autocast_matches_native_bf16_step(golden_dir, name):
 
 def test_predictor_16_mixed_for_both_variants():
     """SlidingWindowPredictor(precision="16-mixed") on a small raw scene: within the bf16 map tolerance of the fp32
-    predictor for an SCA model and a max-pool model."""
+    predictor for an SCA model and a max-pool model, and within 1.5 x the spread of the reference's own bf16 run
+    (the oracle built with the variant's arguments, tests/predict_bound_ref.py) in every band and statistic."""
+    import predict_bound_ref as P
     from cultionet_amd.predict import SlidingWindowPredictor
+    from oracle import predict_ref
     from oracle import towerunet_oracle as O
     from oracle.make_golden import calibrate_bn
     from oracle.selfcheck import build_pair
@@ -189,5 +192,12 @@ def test_predictor_16_mixed_for_both_variants():
         b16 = SlidingWindowPredictor(lit, precision="16-mixed", **kw).predict_scene(scene).cpu().numpy().astype(np.int64)
         d = np.abs(f32 - b16)
         assert b16.shape == (3, H, W) and b16.max() <= 10000, variant
+        print(f"16-mixed {variant} against the fp32 path: max {d.max()}, mean {d.mean():.2f}")
         assert d.max() <= 800 and d.mean() <= 60, (variant, d.max(), d.mean())  # 8e-2 max, 6e-3 mean in probability
         assert (b16 != f32).any(), variant  # the bf16 path really ran
+        # and no further from it than 1.5 x what the reference's own bf16 run of THIS variant moves its fp32 mosaic
+        s = scene.cpu().numpy().astype(np.float64)
+        want = predict_ref.predict_scene(ref, s, ws, pad, mean.numpy(), std.numpy())
+        cast = predict_ref.predict_scene(ref, s, ws, pad, mean.numpy(), std.numpy(), autocast=True)
+        P.assert_within_spread(f"predict 16-mixed {variant} vs the fp32 path", P.band_stats(b16, f32),
+                               P.band_stats(cast, want))

@@ -101,12 +101,11 @@ def test_bucket_plan_key_follows_requires_grad():
 def test_step_key_follows_requires_grad():
     from cultionet_amd import replay as R
 
-    if not torch.cuda.is_available():  # step_key names the current stream: a CPU stand-in for it
-        orig = torch.cuda.current_stream
-        torch.cuda.current_stream = lambda device=None: types.SimpleNamespace(cuda_stream=0)
-    else:
-        orig = None
+    # step_key names the current stream of x.device; the tensors here live on the CPU, for which torch has no stream
+    # (with a GPU present the real function raises on a CPU device). A stand-in on every machine: no GPU is touched.
+    orig = torch.cuda.current_stream
     try:
+        torch.cuda.current_stream = lambda device=None: types.SimpleNamespace(cuda_stream=0)
         ps = [torch.nn.Parameter(torch.zeros(4)) for _ in range(2)]
         store = types.SimpleNamespace(uid=1, params=ps, trainable_mask=lambda: tuple(p.requires_grad for p in ps))
         tr = types.SimpleNamespace(store=store, bf16=False, lit=types.SimpleNamespace(loss_name="TanimotoDistLoss"))
@@ -117,5 +116,4 @@ def test_step_key_follows_requires_grad():
         ps[1].requires_grad_(True)
         assert k1 != k2 and R.step_key(tr, batch) == k1
     finally:
-        if orig is not None:
-            torch.cuda.current_stream = orig
+        torch.cuda.current_stream = orig
