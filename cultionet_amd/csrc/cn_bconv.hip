@@ -1007,8 +1007,9 @@ static int cnb_launch(CnBGeom& g, int G, hipStream_t stream, double flops, CnBFi
     cn_prof_name("cn_bconv_kernel<%d, %d, %d, 2>", WN, (KSC == 2 ? NPv : (KSC == 4 ? (NPv <= 6 ? 6 : 10) : 10)), KSC);
   else
     cn_prof_name("cn_bconv_kernel<%d, %d, %d, 4>", WN, (KSC == 2 ? NPv : (KSC == 4 ? (NPv <= 6 ? 6 : 10) : 10)), KSC);
-  cn_prof_desc("bconv B%d %dx%d %d->%d cls%d taps%d s%d/%d", g.B, g.Hin, g.Win, g.Cin, g.Cout, g.ncls, g.cls[0].ntaps,
-               g.is, g.os);
+  cn_prof_desc("bconv B%d %dx%d %d->%d cls%d taps%d s%d/%d G%d il%d st%d fin%d", g.B, g.Hin, g.Win, g.Cin, g.Cout,
+               g.ncls, g.cls[0].ntaps, g.is, g.os, G, g.interleave, g.stats[0] != nullptr ? 1 : 0,
+               g.fin_cnt != nullptr ? 1 : 0);
   {  // bf16 operands / results, every group its own tensors; the packed weights of all classes once
     int taps_all = 0;
     for (int c = 0; c < g.ncls; ++c) taps_all += g.cls[c].ntaps;

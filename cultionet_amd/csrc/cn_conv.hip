@@ -628,9 +628,9 @@ static int cn_launch_igemm_v(const float* x, const float* wp, const float* bias,
   g.splits = splits < 1 ? 1 : splits;
   dim3 grid(cn_xcd_grid((long)g.grid_x * g.grid_y * g.splits));
   cn_prof_name("cn_conv_igemm_vec_kernel<%d, %d, %d, %d, %d>", WAVES_N, TN, TM, NV, RP);
-  cn_prof_desc("igemm_vec<%d,%d,%d,%d,%d> G%d B%d %d->%d %dx%d->%dx%d taps%d cls%d is%d os%d grid%dx%dx%d", WAVES_N, TN,
-               TM, NV, RP, g.G, g.B, g.Cin, g.Cout, g.Hin, g.Win, g.Hout, g.Wout, max_taps, g.ncls, g.is, g.os,
-               total_tiles, (g.Cout + NT - 1) / NT, splits);
+  cn_prof_desc("igemm_vec<%d,%d,%d,%d,%d> G%d B%d %d->%d %dx%d->%dx%d taps%d cls%d is%d os%d grid%dx%dx%d il%d", WAVES_N,
+               TN, TM, NV, RP, g.G, g.B, g.Cin, g.Cout, g.Hin, g.Win, g.Hout, g.Wout, max_taps, g.ncls, g.is, g.os,
+               total_tiles, (g.Cout + NT - 1) / NT, splits, g.interleave);
   cn_prof_bytes(4.0 * g.G * ((double)g.B * g.Cin * g.Hin * g.Win + (double)g.B * g.Cout * g.Hout * g.Wout / (g.shared_y ? g.G : 1) +
                              (double)(max_taps > 0 ? max_taps : 1) * g.Cin * g.Cout));
   cn_prof_before(stream);
@@ -662,9 +662,9 @@ static int cn_launch_igemm_t(const float* x, const float* wp, const float* bias,
   g.splits = splits < 1 ? 1 : splits;
   dim3 grid(cn_xcd_grid((long)g.grid_x * g.grid_y * g.splits));
   cn_prof_name("cn_conv_igemm_kernel<%d, %d, %d>", WAVES_N, TN, NI_T);
-  cn_prof_desc("igemm_dw<%d,%d,%d> G%d B%d %d->%d %dx%d->%dx%d taps%d cls%d is%d os%d grid%dx%dx%d", WAVES_N, TN, NI_T,
-               g.G, g.B, g.Cin, g.Cout, g.Hin, g.Win, g.Hout, g.Wout, max_taps, g.ncls, g.is, g.os, total_tiles,
-               (g.Cout + NT - 1) / NT, splits);
+  cn_prof_desc("igemm_dw<%d,%d,%d> G%d B%d %d->%d %dx%d->%dx%d taps%d cls%d is%d os%d grid%dx%dx%d il%d", WAVES_N, TN,
+               NI_T, g.G, g.B, g.Cin, g.Cout, g.Hin, g.Win, g.Hout, g.Wout, max_taps, g.ncls, g.is, g.os, total_tiles,
+               (g.Cout + NT - 1) / NT, splits, g.interleave);
   cn_prof_bytes(4.0 * g.G * ((double)g.B * g.Cin * g.Hin * g.Win + (double)g.B * g.Cout * g.Hout * g.Wout / (g.shared_y ? g.G : 1) +
                              (double)(max_taps > 0 ? max_taps : 1) * g.Cin * g.Cout));
   cn_prof_before(stream);

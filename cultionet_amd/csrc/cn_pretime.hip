@@ -1148,7 +1148,9 @@ static int pt_fill(CnPtArgs& a, const float* x, long xbs, const void* const* par
                    int with_backward) {
   if (!pt_supported(C, T, Cout) || B <= 0 || HW <= 0) return CN_ERR_ARG;
   if ((long)B * HW >= (1L << 30)) return CN_ERR_ARG;  // (32-bit byte offsets of a pixel inside a row of the dz scratch)
-  if (ws == nullptr || ws_floats < cn_pretime_workspace_floats(B, C, T, HW, Cout, with_backward)) return CN_ERR_ARG;
+  // (a refused shape answers -1, which no ws_floats is below: it must be refused here too, not launched)
+  const long need = cn_pretime_workspace_floats(B, C, T, HW, Cout, with_backward);
+  if (need < 0 || ws == nullptr || ws_floats < need) return CN_ERR_ARG;
   a.x = x; a.xbs = xbs; a.B = B; a.C = C; a.T = T; a.HW = HW; a.Cout = Cout; a.P = (long)B * HW;
   a.training = training; a.eps3 = bn[0]; a.mom3 = bn[1]; a.eps2 = bn[2]; a.mom2 = bn[3]; a.epsL = eps_ln;
   a.ntiles = 0;
@@ -1204,7 +1206,14 @@ static int pt_launch(CnPtArgs a, float* ws, hipStream_t stream) {
     }                                                                                                          \
   } while (0)
   const bool prof = cn_prof_on();  // per-pass times for tools/pretime_bench.py (kind 6: not a contraction kernel)
-  if (prof) { cn_prof_name("cn_pretime_kernel<%d%s>", PASS, reg ? ", reg" : ""); cn_prof_before(stream); }
+  if (prof) {
+    cn_prof_name("cn_pretime_kernel<%d%s>", PASS, reg ? ", reg" : "");
+    // the instantiation the branches below select (the name above is what bench.py aggregates by)
+    const int ne = (PASS == 4 && MT != 2) ? NE : 1;
+    if (reg) cn_prof_desc("pretime<%d, 4, 1, 1, %s> B%d C%d T%d HW%d Cout%d", PASS, a.C == 3 ? "3, 12" : "4, 25", a.B, a.C, a.T, a.HW, a.Cout);
+    else cn_prof_desc("pretime<%d, %d, %d, %d, 0, 0> B%d C%d T%d HW%d Cout%d", PASS, pt_cmax(a.C), MT, ne, a.B, a.C, a.T, a.HW, a.Cout);
+    cn_prof_before(stream);
+  }
   if (reg && a.C == 3) {  // Cout <= 32, C T = 36: one cout tile, one entry tile per branch
     if (shmem > 64 * 1024)
       (void)hipFuncSetAttribute((const void*)cn_pretime_kernel<PASS, 4, 1, 1, 3, 12>, hipFuncAttributeMaxDynamicSharedMemorySize,

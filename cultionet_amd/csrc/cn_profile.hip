@@ -10,9 +10,9 @@
 #include "cn_common.h"
 
 namespace {
-struct Rec { hipEvent_t a, b; int kind; double flops, bytes; char desc[96]; char name[64]; };
+struct Rec { hipEvent_t a, b; int kind; double flops, bytes; char desc[128]; char name[64]; };
 struct Agg { char name[64]; double ms, flops, launches, bytes; };
-char g_desc[96] = {0};
+char g_desc[128] = {0};
 char g_name[64] = {0};
 double g_bytes = 0.0;   // algorithmic bytes of the next recorded launch (cn_prof_bytes)
 char g_filter[64] = {0};  // non-empty: record only launches whose cn_prof_name equals it
@@ -122,7 +122,8 @@ extern "C" int cn_profile_end(double* out) {
       }
       g_aggs[i].ms += ms; g_aggs[i].flops += r.flops; g_aggs[i].launches += 1.0; g_aggs[i].bytes += r.bytes;
     }
-    if (df) fprintf(df, "%d\t%s\t%.3f\t%.0f\n", r.kind, r.desc, ms * 1e3, r.flops);
+    // kind, description, microseconds, flops, kernel name (tools/layerprof.py and tools/layers_iso.py read the first four)
+    if (df) fprintf(df, "%d\t%s\t%.3f\t%.0f\t%s\n", r.kind, r.desc, ms * 1e3, r.flops, r.name);
     g_pool.push_back(r.a);
     g_pool.push_back(r.b);
   }

@@ -908,8 +908,6 @@ static int cn_wgrad_launch_vec(const float* S, const float* Bg, float* dW, CnWgr
     g.mq_hi = hi;
   }
   cn_prof_name("cn_wgrad_vec_kernel<%d, %d>", T, g.s == 1 ? 1 : 2);
-  cn_prof_desc("wgrad_vec<%d> G%d N%d A%d %dx%d Bc%d %dx%d s%d grid%dx%dx%d nbuf%d", T, g.G, g.N, g.A, g.Hs, g.Ws, g.Bc,
-               g.Hb, g.Wb, g.s, gx, gy, splits, g.nbuf);
   g.spg = splits;
   g.grid_x = gx; g.grid_y = gy; g.grid_z = splits * g.G;
   const dim3 grid(cn_xcd_grid((long)gx * gy * splits * g.G));
@@ -924,6 +922,8 @@ static int cn_wgrad_launch_vec(const float* S, const float* Bg, float* dW, CnWgr
     out = ws;
   }
   if (T == 9) cn_prof_name("cn_wgrad_vec3_kernel<%d>", g.s == 1 ? 1 : 2);
+  cn_prof_desc("wgrad_vec<%d> G%d N%d A%d %dx%d Bc%d %dx%d s%d grid%dx%dx%d nbuf%d sl%d", T, g.G, g.N, g.A, g.Hs, g.Ws,
+               g.Bc, g.Hb, g.Wb, g.s, gx, gy, splits, g.nbuf, g.slice_stride != 0 ? 1 : 0);
   cn_prof_bytes(4.0 * g.G * ((double)g.N * g.A * g.Hs * g.Ws + (double)g.N * g.Bc * g.Hb * g.Wb + (double)dw_floats));
   cn_prof_before(stream);
   if (T == 9) {  // 3 x 3: twelve waves per block, one kernel row of taps per wave (cn_wgrad_vec3_kernel)
@@ -1010,8 +1010,8 @@ static int cn_wgrad_launch_t(const float* S, const float* Bg, float* dW, CnWgrad
     attr_set = true;
   }
   cn_prof_name("cn_wgrad_kernel<%d>", T);
-  cn_prof_desc("wgrad_dw<%d> N%d A%d %dx%d Bc%d %dx%d s%d grid%dx%dx%d", T, g.N, g.A, g.Hs, g.Ws, g.Bc, g.Hb, g.Wb, g.s,
-               gx, gy, splits);
+  cn_prof_desc("wgrad_dw<%d> N%d A%d %dx%d Bc%d %dx%d s%d grid%dx%dx%d nbuf%d", T, g.N, g.A, g.Hs, g.Ws, g.Bc, g.Hb, g.Wb,
+               g.s, gx, gy, splits, g.nbuf);
   g.grid_x = gx; g.grid_y = gy; g.grid_z = splits;
   cn_prof_before(stream);
   CN_LAUNCH((cn_wgrad_kernel<T>), dim3(cn_xcd_grid((long)gx * gy * splits)), dim3(256), lds, stream, S, Bg,

@@ -14,6 +14,7 @@ NHWC, slack after the end); inputs sit in buffers whose gaps hold a finite garba
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 import sys
@@ -262,9 +263,17 @@ def wgrad_ws_f32(B, Cin, H, W, Cout, Ho, Wo, mode):
 # checks
 # ---------------------------------------------------------------------------------------------------------------------
 
-def check_conv_f32(case, seed=0, accumulate=False, xpad=0, ypad=0, wgrad_ws="full", parts=("y", "dx", "dw")):
+def part(routes, label, *facts):
+    """routes.part(label, *facts) of a tests/route_ledger.py Routes, or nothing to record (the forced sweep's children:
+    forcing a tile and a split is their purpose)."""
+    return contextlib.nullcontext() if routes is None else routes.part(label, *facts)
+
+
+def check_conv_f32(case, seed=0, accumulate=False, xpad=0, ypad=0, wgrad_ws="full", parts=("y", "dx", "dw"), routes=None,
+                   tag=""):
     """cn_conv2d_{fwd,bwd_data,bwd_weight}_f32 on integer inputs: equal to float64. case: B, Cin, H, W, Cout, k,
-    stride, pad, dil, bias. xpad / ypad: extra batch-stride elements of the inputs / outputs."""
+    stride, pad, dil, bias. xpad / ypad: extra batch-stride elements of the inputs / outputs. routes: the recorder
+    of the calling test, which learns the route of every part under the label tag + part."""
     B, Cin, H, W, Cout, k, s, p, d, bias = case
     T = k * k
     Ho, Wo = out_size(H, W, k, s, p, d)
@@ -288,8 +297,9 @@ def check_conv_f32(case, seed=0, accumulate=False, xpad=0, ypad=0, wgrad_ws="ful
         xc = Canvas(x.shape, F32, dev, pitch=Cin * H * W + xpad, fill=GARB, data=x)
         yc = Canvas(y64.shape, F32, dev, pitch=Cout * Ho * Wo + ypad, data=y0 if accumulate else None)
         wp = pack_f32(wd, T, Cin, Cout, T, Cin * T, 1)
-        L.call("cn_conv2d_fwd_f32", xc.ptr, xc.pitch, wp.data_ptr(), None if bd is None else bd.data_ptr(), yc.ptr,
-               yc.pitch, B, Cin, H, W, Cout, k, k, s, p, d, acc, st)
+        with part(routes, tag + "y"):
+            L.call("cn_conv2d_fwd_f32", xc.ptr, xc.pitch, wp.data_ptr(), None if bd is None else bd.data_ptr(), yc.ptr,
+                   yc.pitch, B, Cin, H, W, Cout, k, k, s, p, d, acc, st)
         torch.cuda.synchronize()
         assert_exact(yc.t, y64 + y0, f"y {case}")
         yc.assert_canary(f"y {case}")
@@ -297,8 +307,9 @@ def check_conv_f32(case, seed=0, accumulate=False, xpad=0, ypad=0, wgrad_ws="ful
         dyc = Canvas(dy.shape, F32, dev, pitch=Cout * Ho * Wo + ypad, fill=GARB, data=dy)
         dxc = Canvas(x.shape, F32, dev, pitch=Cin * H * W + xpad, data=x0 if accumulate else None)
         wpt = pack_f32(wd, T, Cout, Cin, Cin * T, T, 1)
-        L.call("cn_conv2d_bwd_data_f32", dyc.ptr, dyc.pitch, wpt.data_ptr(), dxc.ptr, dxc.pitch, B, Cin, H, W, Cout, k,
-               k, s, p, d, acc, st)
+        with part(routes, tag + "dx"):
+            L.call("cn_conv2d_bwd_data_f32", dyc.ptr, dyc.pitch, wpt.data_ptr(), dxc.ptr, dxc.pitch, B, Cin, H, W, Cout,
+                   k, k, s, p, d, acc, st)
         torch.cuda.synchronize()
         assert_exact(dxc.t, dx64 + x0, f"dx {case}")
         dxc.assert_canary(f"dx {case}")
@@ -307,8 +318,9 @@ def check_conv_f32(case, seed=0, accumulate=False, xpad=0, ypad=0, wgrad_ws="ful
         dyc = Canvas(dy.shape, F32, dev, pitch=Cout * Ho * Wo + ypad, fill=GARB, data=dy)
         dwc = Canvas(w.shape, F32, dev, data=w0)
         wsp, wsn, _keep = wgrad_ws_f32(B, Cin, H, W, Cout, Ho, Wo, wgrad_ws)
-        L.call("cn_conv2d_bwd_weight_f32", xc.ptr, xc.pitch, dyc.ptr, dyc.pitch, dwc.ptr, B, Cin, H, W, Cout, k, k, s, p,
-               d, wsp, wsn, st)
+        with part(routes, tag + "dw", "ws " + wgrad_ws):
+            L.call("cn_conv2d_bwd_weight_f32", xc.ptr, xc.pitch, dyc.ptr, dyc.pitch, dwc.ptr, B, Cin, H, W, Cout, k, k, s,
+                   p, d, wsp, wsn, st)
         torch.cuda.synchronize()
         assert_exact(dwc.t, dw64 + w0, f"dw {case} ws={wgrad_ws}")
         dwc.assert_canary(f"dw {case}")
@@ -333,9 +345,11 @@ def bf16_store(v, old, cout, accumulate):
     return rb(rb(v) + old) if cout % 8 == 0 else rb(v + old)
 
 
-def check_conv_bf16(case, seed=0, accumulate=False, xpad=8, ypad=16, wgrad_ws="full", parts=("y", "dx", "dw")):
+def check_conv_bf16(case, seed=0, accumulate=False, xpad=8, ypad=16, wgrad_ws="full", parts=("y", "dx", "dw"),
+                    routes=None, tag=""):
     """cn_conv2d_fwd_bf16 (bf16 NHWC and fp32 NCHW outputs), cn_conv2d_bwd_data_bf16, cn_conv2d_bwd_weight_bf16 on
-    integer inputs: bf16 results equal float64 rounded to nearest even, fp32 ones equal float64."""
+    integer inputs: bf16 results equal float64 rounded to nearest even, fp32 ones equal float64. routes: as in
+    check_conv_f32 (parts "y", "y f32 out", "dx", "dw")."""
     B, Cin, H, W, Cout, k, s, p, d, bias = case
     T = k * k
     Ho, Wo = out_size(H, W, k, s, p, d)
@@ -361,23 +375,26 @@ def check_conv_bf16(case, seed=0, accumulate=False, xpad=8, ypad=16, wgrad_ws="f
     if "y" in parts:
         wp = pack_bf16(wd, T, Cin, Cout, T, Cin * T, 1)
         yc = Canvas(y64.shape, BF, dev, pitch=c8(Cout) + ypad, data=y0)
-        L.call("cn_conv2d_fwd_bf16", xc.ptr, xc.pitch, wp.data_ptr(), None if bd is None else bd.data_ptr(), yc.ptr,
-               yc.pitch, 0, B, Cin, H, W, Cout, k, k, s, p, d, acc, 0, None, st)
+        with part(routes, tag + "y"):
+            L.call("cn_conv2d_fwd_bf16", xc.ptr, xc.pitch, wp.data_ptr(), None if bd is None else bd.data_ptr(), yc.ptr,
+                   yc.pitch, 0, B, Cin, H, W, Cout, k, k, s, p, d, acc, 0, None, st)
         torch.cuda.synchronize()
         assert_exact(yc.t, bf16_store(y64, y0, Cout, accumulate), f"y bf16 {case}")
         yc.assert_canary(f"y bf16 {case}")
         # fp32 NCHW output (the thin heads' hand-over), padded batch stride
         y32 = Canvas(y64.shape, F32, dev, pitch=Cout * Ho * Wo + 4, data=y0)
-        L.call("cn_conv2d_fwd_bf16", xc.ptr, xc.pitch, wp.data_ptr(), None if bd is None else bd.data_ptr(), y32.ptr,
-               0, y32.pitch, B, Cin, H, W, Cout, k, k, s, p, d, acc, 1, None, st)
+        with part(routes, tag + "y f32 out"):
+            L.call("cn_conv2d_fwd_bf16", xc.ptr, xc.pitch, wp.data_ptr(), None if bd is None else bd.data_ptr(),
+                   y32.ptr, 0, y32.pitch, B, Cin, H, W, Cout, k, k, s, p, d, acc, 1, None, st)
         torch.cuda.synchronize()
         assert_exact(y32.t, y64 + (y0 if accumulate else 0), f"y f32 out {case}")
         y32.assert_canary(f"y f32 out {case}")
     if "dx" in parts:
         wpt = pack_bf16(wd, T, Cout, Cin, Cin * T, T, 1)
         dxc = Canvas(x.shape, BF, dev, pitch=c8(Cin) + xpad, data=x0)
-        L.call("cn_conv2d_bwd_data_bf16", dyc.ptr, dyc.pitch, wpt.data_ptr(), dxc.ptr, dxc.pitch, B, Cin, H, W, Cout, k,
-               k, s, p, d, acc, st)
+        with part(routes, tag + "dx"):
+            L.call("cn_conv2d_bwd_data_bf16", dyc.ptr, dyc.pitch, wpt.data_ptr(), dxc.ptr, dxc.pitch, B, Cin, H, W, Cout,
+                   k, k, s, p, d, acc, st)
         torch.cuda.synchronize()
         assert_exact(dxc.t, bf16_store(dx64, x0, Cin, accumulate), f"dx bf16 {case}")
         dxc.assert_canary(f"dx bf16 {case}")
@@ -385,8 +402,9 @@ def check_conv_bf16(case, seed=0, accumulate=False, xpad=8, ypad=16, wgrad_ws="f
         n = bwgrad_ws_floats(B, Cin, H, W, Cout, k, s, p, d, 0, wgrad_ws)
         ws = torch.empty(n + 4, device=dev)
         dwc = Canvas(w.shape, F32, dev, data=w0)
-        L.call("cn_conv2d_bwd_weight_bf16", xc.ptr, xc.pitch, dyc.ptr, dyc.pitch, dwc.ptr, B, Cin, H, W, Cout, k, k, s,
-               p, d, ws.data_ptr(), n, st)
+        with part(routes, tag + "dw", "ws " + wgrad_ws):
+            L.call("cn_conv2d_bwd_weight_bf16", xc.ptr, xc.pitch, dyc.ptr, dyc.pitch, dwc.ptr, B, Cin, H, W, Cout, k, k,
+                   s, p, d, ws.data_ptr(), n, st)
         torch.cuda.synchronize()
         assert_exact(dwc.t, dw64 + w0, f"dw bf16 {case} ws={wgrad_ws}")
         dwc.assert_canary(f"dw bf16 {case}")

@@ -12,7 +12,6 @@ exactly one per convolution -- no K split, no slices, no reduce launch.
 """
 from __future__ import annotations
 
-import ctypes
 import functools
 
 import pytest
@@ -20,6 +19,8 @@ import torch
 
 from conv_exact_worker import (F32, NAN, U32, Canvas, assert_exact, bounded, conv_workspace, ints, lib, pack_f32,
                                premise, ref_conv, stream, term_bound)
+from route_ledger import Routes, case_id
+from route_ledger import profile_top as _profile_top
 
 pytestmark = pytest.mark.gpu
 
@@ -80,26 +81,17 @@ def _problem(case, kind, accumulate):
     return x, w, b, dy, y0, x0, y64, dx64, yabs, dxabs
 
 
-def _launch_counted(name, *args):
-    """One library call inside a profiling window: (launches, [(kernel name, launches recorded)])."""
+def _launch_counted(routes, label, name, *args):
+    """One library call inside a profiling window (the part `label` of the test's route recorder, which always closes
+    the window): (launches, [(kernel name, launches recorded)])."""
     L = lib()
     torch.cuda.synchronize()
-    L.call("cn_profile_set_filter", None)
     n0 = L.query("cn_launch_count", 0)
-    L.call("cn_profile_begin")
-    try:
+    with routes.part(label):
         L.call(name, *args)
         torch.cuda.synchronize()
-    finally:
-        L.call("cn_profile_end", (ctypes.c_double * 24)())
     n1 = L.query("cn_launch_count", 0)
-    recs = []
-    nb, o3 = ctypes.create_string_buffer(96), (ctypes.c_double * 3)()
-    nk = L.query("cn_profile_top", 0, nb, 96, o3)
-    for r in range(nk):
-        L.query("cn_profile_top", r, nb, 96, o3)
-        recs.append((nb.value.decode(), int(o3[2])))
-    return n1 - n0, recs
+    return n1 - n0, _profile_top()
 
 
 def _assert_one_gemm(launches, recs, what):
@@ -107,7 +99,7 @@ def _assert_one_gemm(launches, recs, what):
     assert len(recs) == 1 and recs[0][0].startswith("cn_gemm1x1_kernel<") and recs[0][1] == 1, f"{what}: recorded {recs}"
 
 
-def _check(case, kind, ws, accumulate=False, xpad=0, ypad=0):
+def _check(case, kind, ws, request, tmp_path, accumulate=False, xpad=0, ypad=0):
     B, Cin, H, W, Cout, k, s, p, d, bias = case
     x, w, b, dy, y0, x0, y64, dx64, yabs, dxabs = _problem(case, kind, accumulate)
     dev = torch.device("cuda")
@@ -115,19 +107,20 @@ def _check(case, kind, ws, accumulate=False, xpad=0, ypad=0):
     wd = w.float().to(dev)
     bd = b.float().to(dev) if bias else None
     acc = int(accumulate)
+    routes = Routes(case_id(request), tmp_path, "ws" if ws == "ws" else "atomics", *(["acc"] if accumulate else []))
     with conv_workspace(ws):
         xc = Canvas(x.shape, F32, dev, pitch=Cin * H * W + xpad, fill=NAN, data=x)
         yc = Canvas(y64.shape, F32, dev, pitch=Cout * H * W + ypad, data=y0)
         wp = pack_f32(wd, 1, Cin, Cout, 1, Cin, 1)
-        n, recs = _launch_counted("cn_conv2d_fwd_f32", xc.ptr, xc.pitch, wp.data_ptr(),
-                                  None if bd is None else bd.data_ptr(), yc.ptr, yc.pitch, B, Cin, H, W, Cout, 1, 1, 1,
-                                  0, 1, acc, st)
+        n, recs = _launch_counted(routes, "y", "cn_conv2d_fwd_f32", xc.ptr, xc.pitch, wp.data_ptr(),
+                                  None if bd is None else bd.data_ptr(), yc.ptr, yc.pitch, B, Cin, H, W, Cout, 1,
+                                  1, 1, 0, 1, acc, st)
         _assert_one_gemm(n, recs, f"y {case}")
         dyc = Canvas(dy.shape, F32, dev, pitch=Cout * H * W + ypad, fill=NAN, data=dy)
         dxc = Canvas(x.shape, F32, dev, pitch=Cin * H * W + xpad, data=x0)
         wpt = pack_f32(wd, 1, Cout, Cin, Cin, 1, 1)
-        n, recs = _launch_counted("cn_conv2d_bwd_data_f32", dyc.ptr, dyc.pitch, wpt.data_ptr(), dxc.ptr, dxc.pitch, B,
-                                  Cin, H, W, Cout, 1, 1, 1, 0, 1, acc, st)
+        n, recs = _launch_counted(routes, "dx", "cn_conv2d_bwd_data_f32", dyc.ptr, dyc.pitch, wpt.data_ptr(), dxc.ptr,
+                                  dxc.pitch, B, Cin, H, W, Cout, 1, 1, 1, 0, 1, acc, st)
         _assert_one_gemm(n, recs, f"dx {case}")
     if kind == "int":
         assert_exact(yc.t, y64 + (y0 if accumulate else 0), f"y {case} ws={ws}")
@@ -137,37 +130,39 @@ def _check(case, kind, ws, accumulate=False, xpad=0, ypad=0):
         bounded(dxc.t, dx64, (Cout + 4) * U32 * dxabs, f"dx {case} ws={ws}")
     yc.assert_canary(f"y {case}")
     dxc.assert_canary(f"dx {case}")
+    if kind == "int":  # (the random-input twins run the same launches: the exact tests hold the route)
+        routes.verify()
 
 
 @pytest.mark.parametrize("ws", ["ws", "none"])
 @pytest.mark.parametrize("case", CASES, ids=IDS)
-def test_conv1x1_gemm_exact(case, ws):
-    _check(case, "int", ws)
+def test_conv1x1_gemm_exact(case, ws, request, tmp_path):
+    _check(case, "int", ws, request, tmp_path)
 
 
 @pytest.mark.parametrize("ws", ["ws", "none"])
 @pytest.mark.parametrize("case", CASES, ids=IDS)
-def test_conv1x1_gemm_random_bound(case, ws):
-    _check(case, "rand", ws)
+def test_conv1x1_gemm_random_bound(case, ws, request, tmp_path):
+    _check(case, "rand", ws, request, tmp_path)
 
 
 @pytest.mark.parametrize("case", [CASES[0], CASES[1], CASES[3], CASES[7], CASES[9], CASES[12], CASES[14]],
                          ids=[IDS[i] for i in (0, 1, 3, 7, 9, 12, 14)])
-def test_conv1x1_gemm_exact_accumulate(case):
+def test_conv1x1_gemm_exact_accumulate(case, request, tmp_path):
     """accumulate=True adds to integer-prefilled outputs."""
-    _check(case, "int", "ws", accumulate=True)
+    _check(case, "int", "ws", request, tmp_path, accumulate=True)
 
 
 @pytest.mark.parametrize("case,xpad,ypad", [(CASES[0], 1, 3), (CASES[7], 1, 3), (CASES[1], 4, 8), (CASES[1], 2, 5),
                                             (CASES[9], 3, 1), (CASES[12], 1, 3), (CASES[13], 1, 3)])
 @pytest.mark.parametrize("accumulate", [False, True])
-def test_conv1x1_gemm_exact_padded_batch_strides(case, xpad, ypad, accumulate):
+def test_conv1x1_gemm_exact_padded_batch_strides(case, xpad, ypad, accumulate, request, tmp_path):
     """Padded batch strides of inputs and outputs, including ones that break the 16-byte alignment of every image but
     the first: such launches stage their pixel rows with 4-byte pieces and stay one launch."""
-    _check(case, "int", "ws", accumulate=accumulate, xpad=xpad, ypad=ypad)
+    _check(case, "int", "ws", request, tmp_path, accumulate=accumulate, xpad=xpad, ypad=ypad)
 
 
 @pytest.mark.parametrize("case", [CASES[0], CASES[4], CASES[7], CASES[10]], ids=[IDS[i] for i in (0, 4, 7, 10)])
-def test_conv1x1_gemm_exact_bias_off_and_on(case):
+def test_conv1x1_gemm_exact_bias_off_and_on(case, request, tmp_path):
     """The same shape with the bias flag flipped (the case list fixes one setting per shape)."""
-    _check(case[:9] + (not case[9],), "int", "ws")
+    _check(case[:9] + (not case[9],), "int", "ws", request, tmp_path)

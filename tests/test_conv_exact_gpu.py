@@ -23,9 +23,10 @@ import torch.nn.functional as F
 
 from conv_exact_worker import (BF, F32, GARB, U32, Canvas, assert_exact, bf16_store, bwgrad_ws_floats,
                                check_conv_bf16, check_conv_f32, conv_workspace, ints, lib, out_size, pack_bf16,
-                               pack_f32, premise, rb, ref_conv, ref_convT, stream, term_bound, wgrad_ws_f32)
+                               pack_f32, part, premise, rb, ref_conv, ref_convT, stream, term_bound, wgrad_ws_f32)
 from conv_exact_worker import bounded as _bounded
 from conv_exact_worker import half_ulp_bf16 as _half_ulp_bf16
+from route_ledger import Routes, case_id
 
 pytestmark = pytest.mark.gpu
 
@@ -67,50 +68,118 @@ F32_CASES = [
     (8, 128, 25, 25, 128, 3, 1, 1, 1, False),  # production: up_cu / tower_c
     (8, 640, 25, 25, 128, 3, 1, 1, 1, False),  # production: tower_c block 0
     (8, 576, 50, 50, 128, 3, 1, 1, 1, False),  # production: tower_b block 0
+    # the strided gathers of the training step and the predict forward (routes no case above takes: route ledger)
+    (8, 128, 100, 100, 128, 3, 2, 1, 1, False),
+    (8, 128, 25, 25, 256, 3, 2, 1, 1, False),
+    (4, 128, 28, 28, 256, 3, 2, 1, 1, False),
+    (4, 64, 55, 55, 128, 3, 2, 1, 1, False),
 ]
 
 
-@pytest.mark.parametrize("case", F32_CASES)
-def test_conv2d_f32_exact(case):
+# Cases the route ledger asked for: the smallest shapes a probe of the dispatcher found for every instantiation of
+# cn_conv_igemm_vec_kernel<WAVES_N, TN, TM, NV, RP> and cn_conv_igemm_kernel<WAVES_N, TN, NI_T> no case above reaches.
+# NV follows the staged image (wide planes, dilation 5: 1024 / 2048 / 4096 floats), RP the row padding (W % 4 == 0: 1,
+# W % 2 == 0: 2, odd W or |dx| > 4: 0, odd planes: 3), NI_T the halo plane of the dword kernel (H * W % 4 >= 2), the
+# tile config of 128 couts the block count (hence batch 32).
+F32_LEDGER_CASES = [
+    # B, Cin, H, W, Cout, k, stride, pad, dil, bias
+    (1, 8, 100, 100, 40, 3, 2, 1, 1, False),  # production <1, 2, 6> G1 cls1 is2 os1 taps9 whole il0 ws
+    (1, 8, 12, 12, 128, 3, 1, 5, 5, False),  # _vec<2, 2, 2, 1, 0>
+    (1, 8, 12, 12, 40, 3, 1, 5, 5, False),  # _vec<1, 2, 2, 1, 0>
+    (1, 8, 12, 12, 8, 3, 1, 5, 5, False),  # _vec<1, 1, 2, 1, 0>
+    (1, 8, 13, 13, 128, 3, 2, 1, 1, False),  # production _vec<2, 2, 2, 1, 3> G1 cls1 is2 os1 taps9 whole il0 ws
+    (1, 8, 28, 28, 128, 3, 1, 5, 5, False),  # _vec<4, 1, 3, 1, 0>
+    (1, 8, 3, 101, 8, 3, 1, 5, 5, False),  # <1, 1, 6>
+    (1, 8, 3, 301, 128, 3, 1, 2, 2, False),  # <2, 2, 12>
+    (1, 8, 4, 256, 128, 3, 1, 1, 1, False),  # _vec<4, 1, 3, 2, 1>
+    (1, 8, 4, 512, 40, 3, 1, 1, 1, False),  # _vec<1, 2, 2, 4, 1>
+    (1, 8, 4, 512, 8, 3, 1, 1, 1, False),  # _vec<1, 1, 2, 4, 1>
+    (1, 8, 5, 205, 128, 3, 1, 2, 2, False),  # _vec<4, 1, 3, 2, 3>
+    (1, 8, 5, 205, 40, 3, 1, 1, 1, False),  # _vec<1, 2, 2, 2, 3>
+    (1, 8, 5, 205, 40, 3, 1, 5, 5, False),  # _vec<1, 2, 2, 4, 3>
+    (1, 8, 5, 205, 8, 3, 1, 1, 1, False),  # _vec<1, 1, 2, 2, 3>
+    (1, 8, 5, 205, 8, 3, 1, 5, 5, False),  # _vec<1, 1, 2, 4, 3>
+    (1, 8, 6, 101, 40, 3, 1, 5, 5, False),  # <1, 2, 12>
+    (1, 8, 6, 101, 8, 3, 1, 5, 5, False),  # <1, 1, 12>
+    (1, 8, 6, 510, 40, 3, 1, 1, 1, False),  # _vec<1, 2, 2, 4, 2>
+    (1, 8, 6, 510, 8, 3, 1, 1, 1, False),  # _vec<1, 1, 2, 4, 2>
+    (1, 8, 8, 128, 128, 3, 1, 5, 5, False),  # _vec<4, 1, 3, 2, 0>
+    (1, 8, 8, 128, 40, 3, 1, 2, 2, False),  # _vec<1, 2, 2, 2, 1>
+    (1, 8, 8, 128, 40, 3, 1, 5, 5, False),  # _vec<1, 2, 2, 2, 0>
+    (1, 8, 8, 128, 8, 3, 1, 2, 2, False),  # _vec<1, 1, 2, 2, 1>
+    (1, 8, 8, 128, 8, 3, 1, 5, 5, False),  # _vec<1, 1, 2, 2, 0>
+    (1, 8, 8, 130, 40, 3, 1, 2, 2, False),  # _vec<1, 2, 2, 2, 2>
+    (1, 8, 8, 255, 40, 3, 1, 5, 5, False),  # _vec<1, 2, 2, 4, 0>
+    (1, 8, 8, 255, 8, 3, 1, 5, 5, False),  # _vec<1, 1, 2, 4, 0>
+    (1, 8, 8, 258, 128, 3, 1, 1, 1, False),  # _vec<4, 1, 3, 2, 2>
+    (32, 8, 5, 205, 128, 3, 1, 2, 2, False),  # _vec<4, 1, 5, 2, 3>
+    (32, 8, 8, 129, 128, 3, 1, 1, 1, False),  # _vec<4, 1, 5, 1, 0>
+    (32, 8, 8, 129, 128, 3, 1, 5, 5, False),  # _vec<4, 1, 5, 2, 0>
+    (32, 8, 8, 130, 128, 3, 1, 2, 2, False),  # _vec<4, 1, 5, 2, 2>
+    (8, 72, 8, 258, 128, 3, 1, 1, 1, False),  # _vec<2, 2, 2, 2, 2>
+]
+
+
+@pytest.mark.parametrize("case", F32_LEDGER_CASES, ids=lambda c: "-".join(str(int(v)) for v in c))
+def test_conv2d_f32_exact_ledger_cases(case, request, tmp_path):
     _dev()
+    routes = Routes(case_id(request), tmp_path, "ws")
     with conv_workspace("ws"):
-        check_conv_f32(case, seed=1)
+        check_conv_f32(case, seed=20, parts=("y", "dx"), routes=routes)
+    routes.verify()
+
+
+@pytest.mark.parametrize("case", F32_CASES)
+def test_conv2d_f32_exact(case, request, tmp_path):
+    _dev()
+    routes = Routes(case_id(request), tmp_path, "ws")
+    with conv_workspace("ws"):
+        check_conv_f32(case, seed=1, routes=routes)
+    routes.verify()
 
 
 @pytest.mark.parametrize("case", [F32_CASES[1], F32_CASES[6], F32_CASES[10], F32_CASES[13]])
-def test_conv2d_f32_exact_atomic_split(case):
+def test_conv2d_f32_exact_atomic_split(case, request, tmp_path):
     """No workspace registered: K splits combine with float atomics on the output."""
     _dev()
+    routes = Routes(case_id(request), tmp_path, "atomics")
     with conv_workspace("none"):
-        check_conv_f32(case, seed=2, parts=("y", "dx"))
-        check_conv_f32(case, seed=3, accumulate=True, parts=("y", "dx"))
+        check_conv_f32(case, seed=2, parts=("y", "dx"), routes=routes)
+        check_conv_f32(case, seed=3, accumulate=True, parts=("y", "dx"), routes=routes, tag="+= ")
+    routes.verify()
 
 
 @pytest.mark.parametrize("case,xpad,ypad", [(F32_CASES[3], 4, 8), (F32_CASES[7], 3, 5), (F32_CASES[10], 8, 1),
                                             ((2, 72, 12, 12, 40, 3, 1, 1, 1, True), 3, 0)])
-def test_conv2d_f32_exact_accumulate_padded_strides(case, xpad, ypad):
+def test_conv2d_f32_exact_accumulate_padded_strides(case, xpad, ypad, request, tmp_path):
     """accumulate into integer-prefilled outputs, batch strides larger than C*H*W (unaligned ones included)."""
     _dev()
+    routes = Routes(case_id(request), tmp_path, "ws", f"xpad{xpad} ypad{ypad}")
     with conv_workspace("ws"):
-        check_conv_f32(case, seed=4, accumulate=True, xpad=xpad, ypad=ypad)
+        check_conv_f32(case, seed=4, accumulate=True, xpad=xpad, ypad=ypad, routes=routes, tag="+= ")
+    routes.verify()
 
 
 @pytest.mark.parametrize("case", [(4, 48, 100, 100, 129, 1, 1, 0, 1, True),   # the dedicated 1x1 GEMM, ragged Cout
                                   (8, 480, 100, 100, 128, 1, 1, 0, 1, True),   # tower_a skip
                                   (8, 130, 50, 50, 200, 1, 1, 0, 1, False)])
-def test_conv2d_f32_exact_1x1_gemm(case):
+def test_conv2d_f32_exact_1x1_gemm(case, request, tmp_path):
     _dev()
+    routes = Routes(case_id(request), tmp_path, "ws")
     with conv_workspace("ws"):
-        check_conv_f32(case, seed=5, parts=("y", "dx"))
-        check_conv_f32(case, seed=6, accumulate=True, parts=("y",))
+        check_conv_f32(case, seed=5, parts=("y", "dx"), routes=routes)
+        check_conv_f32(case, seed=6, accumulate=True, parts=("y",), routes=routes, tag="+= ")
+    routes.verify()
 
 
 @pytest.mark.parametrize("case", [(8, 480, 100, 100, 128, 3, 1, 1, 1, False)])
-def test_conv2d_f32_exact_production_100(case):
+def test_conv2d_f32_exact_production_100(case, request, tmp_path):
     """tower_a block 0: more blocks than one round over the CUs."""
     _dev()
+    routes = Routes(case_id(request), tmp_path, "ws")
     with conv_workspace("ws"):
-        check_conv_f32(case, seed=7)
+        check_conv_f32(case, seed=7, routes=routes)
+    routes.verify()
 
 
 @pytest.mark.parametrize("case", [
@@ -120,24 +189,32 @@ def test_conv2d_f32_exact_production_100(case):
     (3, 24, 100, 100, 32, 3, 1, 1, 1, False),  # the largest sum: 3 x 100 x 100 pixels
     (2, 40, 25, 25, 128, 1, 1, 0, 1, False),   # 1x1, odd plane
     (2, 32, 26, 26, 48, 3, 2, 1, 1, False),    # stride 2
+    (2, 32, 28, 28, 48, 1, 2, 0, 1, False),    # 1x1, stride 2: cn_wgrad_vec_kernel<1, 2> (route ledger)
 ])
 @pytest.mark.parametrize("ws", ["full", "none"])
-def test_conv2d_f32_weight_gradient_routes(case, ws):
+def test_conv2d_f32_weight_gradient_routes(case, ws, request, tmp_path):
     _dev()
-    check_conv_f32(case, seed=8, wgrad_ws=ws, parts=("dw",))
+    routes = Routes(case_id(request), tmp_path)
+    check_conv_f32(case, seed=8, wgrad_ws=ws, parts=("dw",), routes=routes)
+    routes.verify()
 
 
-def test_conv2d_f32_weight_gradient_padded_batch_stride():
+def test_conv2d_f32_weight_gradient_padded_batch_stride(request, tmp_path):
     """A batch stride that breaks 16-byte alignment forces the aligned copies (with ws) or the dword kernel."""
     _dev()
+    routes = Routes(case_id(request), tmp_path, "xpad1 ypad3")
     for ws in ("full", "none"):
-        check_conv_f32((2, 16, 12, 12, 24, 3, 1, 1, 1, False), seed=9, xpad=1, ypad=3, wgrad_ws=ws, parts=("dw",))
+        check_conv_f32((2, 16, 12, 12, 24, 3, 1, 1, 1, False), seed=9, xpad=1, ypad=3, wgrad_ws=ws, parts=("dw",),
+                       routes=routes, tag=f"ws {ws}: ")
+    routes.verify()
 
 
-def test_conv2d_f32_exact_largest_weight_gradient():
+def test_conv2d_f32_exact_largest_weight_gradient(request, tmp_path):
     """8 x 100 x 100 pixels per weight: the premise holds with margin (8e4 x 12 < 2^24)."""
     _dev()
-    check_conv_f32((8, 24, 100, 100, 32, 3, 1, 1, 1, False), seed=10, parts=("dw",))
+    routes = Routes(case_id(request), tmp_path)
+    check_conv_f32((8, 24, 100, 100, 32, 3, 1, 1, 1, False), seed=10, parts=("dw",), routes=routes)
+    routes.verify()
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -153,10 +230,24 @@ def test_conv2d_f32_exact_largest_weight_gradient():
     (1, 9, 7, 5, 33, 2, 1, True, True),
     (2, 16, 7, 7, 16, 4, 0, True, False),      # stride 4 as a plain transposed conv (some outputs: bias only)
     (1, 128, 25, 25, 128, 2, 1, True, False),
+    # the parity-class scatters of the training step and the predict forward (route ledger)
+    (8, 128, 25, 25, 128, 2, 1, True, False),
+    (8, 128, 50, 50, 128, 2, 1, True, False),
+    (8, 128, 25, 25, 64, 2, 1, True, False),
+    (4, 128, 14, 14, 128, 2, 1, True, False),
+    (4, 128, 28, 28, 128, 2, 0, True, False),
+    (4, 64, 55, 55, 64, 2, 1, True, False),
+    (4, 128, 55, 55, 128, 2, 1, True, False),
+    # the remaining production scatters, at the smallest batch that selects their tile (route ledger)
+    (4, 8, 50, 50, 128, 2, 1, True, False),  # production _vec<4, 1, 3, 1, 2> G1 cls4 is1 os2 taps4 whole il1 ws
+    (4, 8, 28, 28, 128, 2, 0, True, False),  # production _vec<2, 2, 2, 1, 1> cls4 os2 taps4 whole il0: unequal class tiles
+    (36, 8, 28, 28, 128, 2, 0, True, False),  # the same at the block count of the 36-window predict forward
 ])
-def test_conv_transpose2d_f32_exact(case):
+def test_conv_transpose2d_f32_exact(case, request, tmp_path):
     B, Cin, H, W, Cout, s, op, bias, acc = case
     dev = _dev()
+    routes = Routes(case_id(request), tmp_path)
+    facts = ("ws", "acc") if acc else ("ws",)  # of the forward / data-gradient parts; a weight gradient knows neither
     k, p, T = 3, 1, 9
     Ho, Wo = (H - 1) * s - 2 * p + k + op, (W - 1) * s - 2 * p + k + op
     x = ints((B, Cin, H, W), -4, 4, 11)
@@ -177,17 +268,20 @@ def test_conv_transpose2d_f32_exact(case):
         xc = Canvas(x.shape, F32, dev, fill=GARB, data=x)
         yc = Canvas(y64.shape, F32, dev, data=y0 if acc else None)
         wp, wpt = pack_f32(wd, T, Cin, Cout, Cout * T, T, 1), pack_f32(wd, T, Cout, Cin, T, Cout * T, 1)
-        L.call("cn_conv_transpose2d_fwd_f32", xc.ptr, xc.pitch, wp.data_ptr(), None if bd is None else bd.data_ptr(),
-               yc.ptr, yc.pitch, B, Cin, H, W, Cout, k, k, s, p, op, int(acc), st)
+        with routes.part("transposed y", *facts):
+            L.call("cn_conv_transpose2d_fwd_f32", xc.ptr, xc.pitch, wp.data_ptr(), None if bd is None else bd.data_ptr(),
+                   yc.ptr, yc.pitch, B, Cin, H, W, Cout, k, k, s, p, op, int(acc), st)
         dyc = Canvas(dy.shape, F32, dev, fill=GARB, data=dy)
         dxc = Canvas(x.shape, F32, dev, data=x0 if acc else None)
-        L.call("cn_conv_transpose2d_bwd_data_f32", dyc.ptr, dyc.pitch, wpt.data_ptr(), dxc.ptr, dxc.pitch, B, Cin, H, W,
-               Cout, k, k, s, p, op, int(acc), st)
+        with routes.part("transposed dx", *facts):
+            L.call("cn_conv_transpose2d_bwd_data_f32", dyc.ptr, dyc.pitch, wpt.data_ptr(), dxc.ptr, dxc.pitch, B, Cin, H,
+                   W, Cout, k, k, s, p, op, int(acc), st)
         for ws in ("full", "none"):
             dwc = Canvas(w.shape, F32, dev, data=w0)
             wsp, wsn, _keep = wgrad_ws_f32(B, Cin, H, W, Cout, Ho, Wo, ws)
-            L.call("cn_conv_transpose2d_bwd_weight_f32", xc.ptr, xc.pitch, dyc.ptr, dyc.pitch, dwc.ptr, B, Cin, H, W,
-                   Cout, k, k, s, p, op, wsp, wsn, st)
+            with routes.part(f"transposed dw ws {ws}"):
+                L.call("cn_conv_transpose2d_bwd_weight_f32", xc.ptr, xc.pitch, dyc.ptr, dyc.pitch, dwc.ptr, B, Cin, H, W,
+                       Cout, k, k, s, p, op, wsp, wsn, st)
             torch.cuda.synchronize()
             assert_exact(dwc.t, dw64 + w0, f"dw ws={ws}")
             dwc.assert_canary("dw")
@@ -195,9 +289,60 @@ def test_conv_transpose2d_f32_exact(case):
     yc.assert_canary("y")
     assert_exact(dxc.t, dx64 + x0, "dx")
     dxc.assert_canary("dx")
+    routes.verify()
+
+# Wide planes: the 2048- and 4096-float staging images (NV 2 | 4) of the 128-cout tiles under every row-padding variant
+# and tile config. With 128 couts the 4096-float image leaves LDS room for at most 7 taps, so only the 4-tap parity
+# classes of a strided scatter reach it (a 3x3 gather that needs it answers CN_ERR_LDS, as do the data and weight
+# gradients of these shapes): the forward alone, on the output_padding 1 grid (H -> 2 H). Shapes from a probe of the
+# dispatcher; batch 32 / 64 is what selects the 160-pixel tile.
+CONVT_WIDE_F32 = [
+    # B, Cin, H, W, Cout
+    (1, 8, 4, 511, 128),  # _vec<2, 2, 2, 2, 0>
+    (1, 8, 4, 256, 128),  # _vec<2, 2, 2, 2, 1>
+    (1, 8, 5, 409, 128),  # _vec<2, 2, 2, 2, 3>
+    (1, 8, 4, 1022, 128),  # _vec<2, 2, 2, 4, 0>
+    (1, 8, 4, 512, 128),  # _vec<2, 2, 2, 4, 1>
+    (1, 8, 4, 510, 128),  # _vec<2, 2, 2, 4, 2>
+    (1, 8, 3, 683, 128),  # _vec<2, 2, 2, 4, 3>
+    (1, 72, 4, 1022, 128),  # _vec<4, 1, 3, 4, 0>
+    (2, 72, 4, 512, 128),  # _vec<4, 1, 3, 4, 1>
+    (2, 72, 4, 510, 128),  # _vec<4, 1, 3, 4, 2>
+    (4, 8, 3, 683, 128),  # _vec<4, 1, 3, 4, 3>
+    (64, 8, 8, 256, 72),  # _vec<4, 1, 5, 2, 1>
+    (32, 8, 4, 1022, 72),  # _vec<4, 1, 5, 4, 0>
+    (64, 8, 4, 512, 72),  # _vec<4, 1, 5, 4, 1>
+    (64, 8, 4, 510, 72),  # _vec<4, 1, 5, 4, 2>
+    (8, 8, 3, 683, 128),  # _vec<4, 1, 5, 4, 3>
+    (16, 8, 5, 205, 128),  # production _vec<4, 1, 5, 1, 3> G1 cls4 is1 os2 taps4 whole il1 ws
+]
 
 
-def _engine_run(mod, fn, inputs, dy):
+@pytest.mark.parametrize("B,Cin,H,W,Cout", CONVT_WIDE_F32)
+def test_conv_transpose2d_f32_forward_wide_exact(B, Cin, H, W, Cout, request, tmp_path):
+    dev = _dev()
+    x = ints((B, Cin, H, W), -4, 4, 18)
+    w = ints((Cin, Cout, 3, 3), -3, 3, 19)
+    b = ints((Cout,), -8, 8, 20)
+    premise("convT wide", term_bound(x, w, Cin * 9), 8)
+    y64 = F.conv_transpose2d(x, w, b, 2, 1, output_padding=1)
+    L, st = lib(), stream()
+    wd, bd = w.float().to(dev), b.float().to(dev)
+    routes = Routes(case_id(request), tmp_path)
+    with conv_workspace("ws"):
+        xc = Canvas(x.shape, F32, dev, fill=GARB, data=x)
+        yc = Canvas(y64.shape, F32, dev)
+        wp = pack_f32(wd, 9, Cin, Cout, Cout * 9, 9, 1)
+        with routes.part("transposed y", "ws"):
+            L.call("cn_conv_transpose2d_fwd_f32", xc.ptr, xc.pitch, wp.data_ptr(), bd.data_ptr(), yc.ptr, yc.pitch, B, Cin,
+                   H, W, Cout, 3, 3, 2, 1, 1, 0, st)
+        torch.cuda.synchronize()
+    assert_exact(yc.t, y64, "y")
+    yc.assert_canary("y")
+    routes.verify()
+
+
+def _engine_run(mod, fn, inputs, dy, routes=None):
     from cultionet_amd import engine as E
 
     dev = _dev()
@@ -206,15 +351,17 @@ def _engine_run(mod, fn, inputs, dy):
     store.zero_grad()
     with E.using_store(store), E.recording(True) as tape:
         xs = [E.Var(t.to(dev).float().contiguous(), True) for t in inputs]
-        y = fn(*xs)
+        with part(routes, "engine forward"):
+            y = fn(*xs)
         y.grad = dy.to(dev).float().contiguous()
-        tape.backward()
+        with part(routes, "engine backward"):
+            tape.backward()
     torch.cuda.synchronize()
     return y.t.cpu(), [x.grad.cpu() for x in xs], {n: store.grad_of(p).cpu() for n, p in mod.named_parameters()}
 
 
 @pytest.mark.parametrize("B,C,H,W", [(2, 16, 7, 7), (1, 9, 25, 25), (2, 3, 5, 6)])
-def test_convt_taps_route_exact(B, C, H, W):
+def test_convt_taps_route_exact(B, C, H, W, request, tmp_path):
     """final_c's ConvTranspose2d(k 3, stride 4, padding 1) at its natural size: the 1x1 GEMM into taps-as-channels
     and cn_convt_taps_fwd_f32 / cn_convt_taps_bwd_f32 (no resize), through the engine."""
     from cultionet_amd import engine as E
@@ -229,11 +376,13 @@ def test_convt_taps_route_exact(B, C, H, W):
     y64, dx64, dw64 = ref_convT(x, mod.weight.detach(), mod.bias.detach(), dy, 4, 1)
     premise("taps", term_bound(x, mod.weight.detach(), C), 8)
     premise("taps dw", term_bound(x, dy, B * H * W), 0)
-    y, (dx,), pg = _engine_run(mod, lambda v: E.conv_transpose2d(v, mod, 4, 1), [x], dy)
+    routes = Routes(case_id(request), tmp_path)
+    y, (dx,), pg = _engine_run(mod, lambda v: E.conv_transpose2d(v, mod, 4, 1), [x], dy, routes)
     assert_exact(y, y64, "y")
     assert_exact(dx, dx64, "dx")
     assert_exact(pg["weight"], dw64, "dw")
     assert_exact(pg["bias"], dy.sum(dim=(0, 2, 3)), "db")
+    routes.verify()
 
 
 @pytest.mark.parametrize("B,C,H,W,size", [(1, 16, 25, 25, 100), (2, 8, 7, 7, 30)])
@@ -260,7 +409,7 @@ def test_convt_taps_route_resized_bound(B, C, H, W, size):
 
 
 @pytest.mark.parametrize("k", [3, 5])
-def test_time_conv_exact(k):
+def test_time_conv_exact(k, request, tmp_path):
     """nn.Conv3d(kernel (k,1,1)) of PreTimeReduction: cn_pack_timeconv_f32 (both orientations), the banded 1x1
     contraction and cn_fold_timeconv_grad_f32."""
     from cultionet_amd import engine as E
@@ -276,11 +425,13 @@ def test_time_conv_exact(k):
     dy = ints(y64.shape, -3, 3, 33)
     dx64, dw64 = torch.autograd.grad(y64, (xr, wr), dy)
     premise("time conv dw", term_bound(x, dy, B * H * W * (Tn - k + 1)), 0)
+    routes = Routes(case_id(request), tmp_path)
     y, (dx,), pg = _engine_run(conv, lambda v: E.time_conv(v, conv, Tn), [x.reshape(B, C * Tn, H, W)],
-                               dy.reshape(B, -1, H, W))
+                               dy.reshape(B, -1, H, W), routes)
     assert_exact(y.reshape(y64.shape), y64.detach(), "y")
     assert_exact(dx.reshape(x.shape), dx64, "dx")
     assert_exact(pg["weight"], dw64, "dw")
+    routes.verify()
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -294,8 +445,23 @@ def test_time_conv_exact(k):
     (4, 2, 32, 25, 25, 64, (1, 2, 3, 4), True, "ws"),
     (2, 8, 128, 25, 25, 128, (1, 2), True, "none"),
     (3, 2, 64, 7, 7, 128, (1, 1, 2), False, "none"),
+    # two convolutions of one input per launch, as the training step and the predict forward group them (route ledger)
+    (2, 8, 32, 100, 100, 32, (1, 1), True, "ws"),
+    (2, 8, 64, 50, 50, 64, (1, 1), True, "ws"),
+    (2, 8, 128, 50, 50, 128, (1, 1), True, "ws"),
+    (2, 8, 128, 25, 25, 128, (1, 1), True, "ws"),
+    (2, 4, 64, 55, 55, 64, (1, 1), True, "ws"),
+    (2, 4, 128, 28, 28, 128, (1, 1), True, "ws"),
+    (2, 4, 128, 55, 55, 128, (1, 1), True, "ws"),
+    # the unsplit two-group launches (few K chunks, or many blocks) of the predict forward and the eval forward
+    (2, 1, 8, 13, 13, 40, (1, 1), True, "ws"),  # production _vec<1, 2, 2, 1, 3> G>1 cls2 is1 os1 taps9 whole il0 ws
+    (2, 16, 8, 28, 28, 128, (1, 1), True, "ws"),  # production _vec<2, 2, 2, 1, 1> G>1 cls2 is1 os1 taps9 whole il0 ws
+    (2, 1, 8, 13, 13, 128, (1, 1), True, "ws"),  # production _vec<2, 2, 2, 1, 3> G>1 cls2 is1 os1 taps9 whole il0 ws
+    (2, 1, 8, 14, 14, 128, (1, 1), True, "ws"),  # production _vec<4, 1, 3, 1, 2> G>1 cls2 is1 os1 taps9 whole il0 ws
+    (2, 4, 8, 100, 100, 128, (1, 1), True, "ws"),  # production _vec<4, 1, 5, 1, 1> G>1 cls2 is1 os1 taps9 whole il0 ws
+    (2, 16, 8, 50, 50, 128, (1, 1), True, "ws"),  # production _vec<4, 1, 5, 1, 2> G>1 cls2 is1 os1 taps9 whole il0 ws
 ])
-def test_grouped_f32_exact(G, B, Cin, H, W, Cout, dils, shared_in, ws):
+def test_grouped_f32_exact(G, B, Cin, H, W, Cout, dils, shared_in, ws, request, tmp_path):
     """cn_conv2d_{fwd,bwd_data}_grouped_f32 with distinct and summed outputs (pad = dil per group), and
     cn_conv2d_bwd_weight_grouped_f32 (one pad / dilation for all groups)."""
     dev = _dev()
@@ -315,26 +481,32 @@ def test_grouped_f32_exact(G, B, Cin, H, W, Cout, dils, shared_in, ws):
     wps = [pack_f32(wd, T, Cin, Cout, T, Cin * T, 1) for wd in wds]
     wpts = [pack_f32(wd, T, Cout, Cin, Cin * T, T, 1) for wd in wds]
     pads = _ints_c(list(dils))
+    routes = Routes(case_id(request), tmp_path)
+    wsf = "ws" if ws == "ws" else "atomics"
     with conv_workspace(ws):
         ycs = [Canvas((B, Cout, H, W), F32, dev) for _ in range(G)]
-        L.call("cn_conv2d_fwd_grouped_f32", G, _tab(xptr), xcs[0].pitch, _tab([w.data_ptr() for w in wps]),
-               _tab([b.data_ptr() for b in bds]), _tab([y.ptr for y in ycs]), ycs[0].pitch, B, Cin, H, W, Cout, k, k, 1,
-               pads, pads, 0, st)
+        with routes.part("grouped y", wsf):
+            L.call("cn_conv2d_fwd_grouped_f32", G, _tab(xptr), xcs[0].pitch, _tab([w.data_ptr() for w in wps]),
+                   _tab([b.data_ptr() for b in bds]), _tab([y.ptr for y in ycs]), ycs[0].pitch, B, Cin, H, W, Cout, k, k,
+                   1, pads, pads, 0, st)
         ysum0 = ints((B, Cout, H, W), -8, 8, 80)
         ysum = Canvas((B, Cout, H, W), F32, dev, data=ysum0)
-        L.call("cn_conv2d_fwd_grouped_f32", G, _tab(xptr), xcs[0].pitch, _tab([w.data_ptr() for w in wps]),
-               _tab([b.data_ptr() for b in bds]), _tab([ysum.ptr] * G), ysum.pitch, B, Cin, H, W, Cout, k, k, 1, pads,
-               pads, 1, st)
+        with routes.part("grouped summed y", wsf, "acc"):
+            L.call("cn_conv2d_fwd_grouped_f32", G, _tab(xptr), xcs[0].pitch, _tab([w.data_ptr() for w in wps]),
+                   _tab([b.data_ptr() for b in bds]), _tab([ysum.ptr] * G), ysum.pitch, B, Cin, H, W, Cout, k, k, 1, pads,
+                   pads, 1, st)
         dycs = [Canvas((B, Cout, H, W), F32, dev, fill=GARB, data=d) for d in dys]
         dxcs = [Canvas((B, Cin, H, W), F32, dev) for _ in range(G)]
         k3 = _ints_c([3] * G)
-        L.call("cn_conv2d_bwd_data_grouped_f32", G, _tab([d.ptr for d in dycs]), dycs[0].pitch,
-               _tab([w.data_ptr() for w in wpts]), _tab([d.ptr for d in dxcs]), dxcs[0].pitch, B, Cin, H, W, Cout, k3,
-               k3, 1, pads, pads, 0, st)
+        with routes.part("grouped dx", wsf):
+            L.call("cn_conv2d_bwd_data_grouped_f32", G, _tab([d.ptr for d in dycs]), dycs[0].pitch,
+                   _tab([w.data_ptr() for w in wpts]), _tab([d.ptr for d in dxcs]), dxcs[0].pitch, B, Cin, H, W, Cout, k3,
+                   k3, 1, pads, pads, 0, st)
         dxsum = Canvas((B, Cin, H, W), F32, dev)
-        L.call("cn_conv2d_bwd_data_grouped_f32", G, _tab([d.ptr for d in dycs]), dycs[0].pitch,
-               _tab([w.data_ptr() for w in wpts]), _tab([dxsum.ptr] * G), dxsum.pitch, B, Cin, H, W, Cout, k3, k3, 1,
-               pads, pads, 0, st)
+        with routes.part("grouped summed dx", wsf):
+            L.call("cn_conv2d_bwd_data_grouped_f32", G, _tab([d.ptr for d in dycs]), dycs[0].pitch,
+                   _tab([w.data_ptr() for w in wpts]), _tab([dxsum.ptr] * G), dxsum.pitch, B, Cin, H, W, Cout, k3, k3, 1,
+                   pads, pads, 0, st)
         torch.cuda.synchronize()
     for i in range(G):
         assert_exact(ycs[i].t, refs[i][0], f"y{i}")
@@ -350,14 +522,16 @@ def test_grouped_f32_exact(G, B, Cin, H, W, Cout, dils, shared_in, ws):
     w0s = [ints((Cout, Cin, k, k), -8, 8, 90 + i) for i in range(G)]
     dws = [Canvas((Cout, Cin, k, k), F32, dev, data=w0) for w0 in w0s]
     wsp, wsn, _keep = wgrad_ws_f32(B, Cin, H, W, Cout, H, W, "full")
-    L.call("cn_conv2d_bwd_weight_grouped_f32", G, _tab(xptr), xcs[0].pitch, _tab([c.ptr for c in dycs]),
-           dycs[0].pitch, _tab([c.ptr for c in dws]), B, Cin, H, W, Cout, k, k, 1, d, d, wsp, wsn, st)
+    with routes.part("grouped dw", "ws full"):
+        L.call("cn_conv2d_bwd_weight_grouped_f32", G, _tab(xptr), xcs[0].pitch, _tab([c.ptr for c in dycs]),
+               dycs[0].pitch, _tab([c.ptr for c in dws]), B, Cin, H, W, Cout, k, k, 1, d, d, wsp, wsn, st)
     torch.cuda.synchronize()
     for i in range(G):
         premise("grouped dw", term_bound(xs[i], dys[i], B * H * W), 8)
         _, _, dw64 = ref_conv(xs[i], ws_[i], None, dys[i], 1, d, d)
         assert_exact(dws[i].t, dw64 + w0s[i], f"dw{i}")
         dws[i].assert_canary(f"dw{i}")
+    routes.verify()
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -452,27 +626,88 @@ BF16_CASES = [
 
 
 @pytest.mark.parametrize("case", BF16_CASES)
-def test_conv2d_bf16_exact(case):
+def test_conv2d_bf16_exact(case, request, tmp_path):
     _dev()
-    check_conv_bf16(case, seed=200)
+    routes = Routes(case_id(request), tmp_path)
+    check_conv_bf16(case, seed=200, routes=routes)
+    routes.verify()
 
 
 @pytest.mark.parametrize("case", [BF16_CASES[0], BF16_CASES[1], BF16_CASES[5], BF16_CASES[8], BF16_CASES[12]])
-def test_conv2d_bf16_exact_accumulate(case):
+def test_conv2d_bf16_exact_accumulate(case, request, tmp_path):
     _dev()
-    check_conv_bf16(case, seed=210, accumulate=True, xpad=16, ypad=8, parts=("y", "dx"))
+    routes = Routes(case_id(request), tmp_path, "acc")
+    check_conv_bf16(case, seed=210, accumulate=True, xpad=16, ypad=8, parts=("y", "dx"), routes=routes)
+    routes.verify()
 
 
 @pytest.mark.parametrize("case", [(2, 64, 25, 25, 64, 3, 1, 1, 1, False), (3, 24, 100, 100, 32, 3, 1, 1, 1, False),
                                   (2, 128, 13, 13, 136, 3, 2, 1, 1, False), (2, 40, 50, 50, 24, 1, 1, 0, 1, False)])
 @pytest.mark.parametrize("ws", ["full", "mid", "one"])
-def test_conv2d_bf16_weight_gradient_workspaces(case, ws):
+def test_conv2d_bf16_weight_gradient_workspaces(case, ws, request, tmp_path):
     """The split shrinks to fit the workspace: the full size, exactly one split's slice, and one in between."""
     _dev()
-    check_conv_bf16(case, seed=220, wgrad_ws=ws, parts=("dw",))
+    routes = Routes(case_id(request), tmp_path)
+    check_conv_bf16(case, seed=220, wgrad_ws=ws, parts=("dw",), routes=routes)
+    routes.verify()
 
 
-def test_bf16_outputs_round_ties_to_even():
+# Cases the route ledger (tests/contraction_routes.py) asked for: the smallest shapes that select an instantiation of
+# cn_bconv_kernel<WN, NP, KSC, MPW> or cn_bwgrad_kernel<T, NQ, full> no other exact case reaches. WN follows the cout
+# blocks (Cout <= 32: 1, <= 96: 2, else 4, halved with MPW 2 while a launch has <= 224 blocks -- hence the batches
+# of 57 and 113 tiny planes for the full-tile WN 4 routes), KSC the input depth (Cin > 32, and > 64 for 1x1) and NP the
+# halo image of one pixel tile; NQ and `full` follow the halo image and the tile of the weight gradient. Strides 3 and
+# 4 are calls the model never makes; the C ABI accepts them and they are the only way to two 1x1 gradient kernels.
+BF16_LEDGER_CASES = [
+    # B, Cin, H, W, Cout, k, stride, pad, dil, bias
+    (2, 8, 5, 6, 8, 3, 1, 5, 5, False),        # <1,6,2,4>; gradient <9,16,false>
+    (2, 40, 5, 6, 8, 1, 1, 0, 1, True),        # <1,6,4,4>
+    (1, 8, 20, 25, 8, 1, 1, 0, 1, False),      # <1,10,2,4>
+    (2, 40, 10, 10, 8, 1, 2, 0, 1, True),      # <1,10,4,4>
+    (2, 72, 5, 6, 8, 1, 1, 0, 1, False),       # <1,10,8,4>
+    (2, 8, 5, 6, 128, 1, 1, 0, 1, True),       # <2,4,2,2>
+    (2, 8, 5, 6, 40, 1, 1, 0, 1, False),       # <2,4,2,4>
+    (1, 8, 5, 6, 128, 3, 1, 5, 5, True),       # <2,6,2,2>
+    (1, 8, 5, 6, 40, 3, 1, 5, 5, False),       # <2,6,2,4>
+    (2, 40, 5, 6, 128, 1, 1, 0, 1, False),     # <2,6,4,2>
+    (2, 40, 5, 6, 40, 1, 1, 0, 1, True),       # <2,6,4,4>
+    (1, 8, 10, 50, 128, 1, 2, 0, 1, False),    # <2,10,2,2>; gradient <1,0,true>
+    (1, 8, 10, 50, 40, 1, 2, 0, 1, True),      # <2,10,2,4>
+    (1, 40, 10, 10, 128, 1, 2, 0, 1, True),    # <2,10,4,2>
+    (1, 40, 10, 10, 40, 1, 2, 0, 1, False),    # <2,10,4,4>
+    (2, 72, 5, 6, 128, 1, 1, 0, 1, True),      # <2,10,8,2>
+    (2, 72, 5, 6, 40, 1, 1, 0, 1, False),      # <2,10,8,4>
+    (113, 8, 5, 6, 256, 1, 1, 0, 1, False),    # <4,4,2,4>: 226 blocks
+    (113, 8, 5, 6, 256, 3, 1, 5, 5, False),    # <4,6,2,4>
+    (113, 40, 5, 6, 256, 1, 1, 0, 1, True),    # <4,6,4,4>, one tap
+    (113, 40, 5, 6, 256, 3, 1, 1, 1, False),   # <4,6,4,4>, nine taps: the tower layers at batch 32
+    (113, 8, 9, 49, 256, 1, 2, 0, 1, False),   # <4,10,2,4>
+    (113, 40, 10, 10, 256, 1, 2, 0, 1, False), # <4,10,4,4>, one tap
+    (57, 40, 5, 25, 512, 3, 1, 2, 2, False),   # <4,10,4,4>, nine taps, dilation 2: 228 blocks
+    (113, 72, 5, 6, 256, 1, 1, 0, 1, False),   # <4,10,8,4>
+    (2, 16, 1, 255, 24, 1, 2, 0, 1, False),    # gradient <1,8,true>: the 1 x 128 tile of a one-row plane
+    (2, 16, 22, 22, 24, 1, 3, 0, 1, False),    # gradient <1,8,false>: stride 3
+    (2, 16, 29, 29, 24, 1, 4, 0, 1, False),    # gradient <1,0,false>: stride 4
+    (2, 16, 10, 25, 24, 3, 1, 4, 4, False),    # gradient <9,16,true>: dilation 4 on two 5 x 25 tiles
+    (2, 16, 10, 25, 24, 3, 1, 5, 5, False),    # gradient <9,0,true>: dilation 5
+    (2, 16, 15, 15, 24, 3, 2, 4, 4, False),    # gradient <9,0,false>: stride 2, dilation 4, one 8 x 8 tile
+    # routes of the training step at batch 32 that no case above takes
+    (2, 32, 26, 26, 64, 3, 2, 1, 1, False),    # strided gather, 64 couts
+    (113, 40, 25, 25, 128, 3, 2, 1, 1, False), # strided gather, full-tile WN 4 (226 blocks)
+    (57, 40, 17, 97, 128, 3, 4, 1, 1, False),  # stride 4 (final_c), full-tile WN 4 (228 blocks)
+    (113, 9, 5, 25, 256, 3, 1, 1, 1, False),   # the first layer's 9 input channels: <4,4,2,4>
+]
+
+
+@pytest.mark.parametrize("case", BF16_LEDGER_CASES, ids=lambda c: "-".join(str(int(v)) for v in c))
+def test_conv2d_bf16_exact_ledger_cases(case, request, tmp_path):
+    _dev()
+    routes = Routes(case_id(request), tmp_path)
+    check_conv_bf16(case, seed=230, routes=routes)
+    routes.verify()
+
+
+def test_bf16_outputs_round_ties_to_even(request, tmp_path):
     """Outputs in [256, 512) have bf16 spacing 2: odd integers are ties. The exact tests reach them (checked here),
     so a store that truncates or rounds half up fails them."""
     case = (2, 64, 25, 25, 64, 3, 1, 1, 1, False)
@@ -484,7 +719,9 @@ def test_bf16_outputs_round_ties_to_even():
     assert int(ties.sum()) > 100, int(ties.sum())
     assert {float(v) % 4 for v in a[ties][:200]} == {1.0, 3.0}  # both directions of the tie
     _dev()
-    check_conv_bf16(case, seed=200, parts=("y",))
+    routes = Routes(case_id(request), tmp_path)
+    check_conv_bf16(case, seed=200, parts=("y",), routes=routes)
+    routes.verify()
 
 
 @pytest.mark.parametrize("G,B,Cin,H,W,Cout,dils,shared_in", [
@@ -492,8 +729,13 @@ def test_bf16_outputs_round_ties_to_even():
     (2, 2, 32, 14, 14, 32, (1, 2), True),
     (3, 1, 24, 11, 9, 40, (1, 2, 3), False),
     (4, 2, 64, 25, 25, 64, (1, 2, 3, 4), True),
+    # two convolutions of one input per launch as the training step groups them (route ledger): 64 and 128 couts, and
+    # the full-tile WN 4 route (320 blocks)
+    (2, 2, 64, 50, 50, 64, (1, 1), True),
+    (2, 2, 40, 25, 25, 128, (1, 1), True),
+    (2, 8, 40, 50, 50, 128, (1, 1), True),
 ])
-def test_grouped_bf16_exact(G, B, Cin, H, W, Cout, dils, shared_in):
+def test_grouped_bf16_exact(G, B, Cin, H, W, Cout, dils, shared_in, request, tmp_path):
     """cn_conv2d_fwd_grouped_bf16 (+= too), cn_conv2d_fwd_grouped_bnstats_bf16 (outputs equal to the plain launch)
     and cn_conv2d_bwd_data_grouped_bf16, per group against float64."""
     dev = _dev()
@@ -515,19 +757,23 @@ def test_grouped_bf16_exact(G, B, Cin, H, W, Cout, dils, shared_in):
     wps = [pack_bf16(wd, T, Cin, Cout, T, Cin * T, 1) for wd in wds]
     wpts = [pack_bf16(wd, T, Cout, Cin, Cin * T, T, 1) for wd in wds]
     pads = _ints_c(list(dils))
+    routes = Routes(case_id(request), tmp_path)
     ycs = [Canvas((B, Cout, H, W), BF, dev, pitch=ld(Cout)) for _ in range(G)]
-    L.call("cn_conv2d_fwd_grouped_bf16", G, _tab(xptr), xcs[0].pitch, _tab([w.data_ptr() for w in wps]),
-           _tab([b.data_ptr() for b in bds]), _tab([y.ptr for y in ycs]), ycs[0].pitch, B, Cin, H, W, Cout, k, k, 1,
-           pads, pads, 0, None, st)
+    with routes.part("grouped y"):
+        L.call("cn_conv2d_fwd_grouped_bf16", G, _tab(xptr), xcs[0].pitch, _tab([w.data_ptr() for w in wps]),
+               _tab([b.data_ptr() for b in bds]), _tab([y.ptr for y in ycs]), ycs[0].pitch, B, Cin, H, W, Cout, k, k, 1,
+               pads, pads, 0, None, st)
     y0s = [ints((B, Cout, H, W), -8, 8, 340 + i) for i in range(G)]
     yas = [Canvas((B, Cout, H, W), BF, dev, pitch=ld(Cout), data=y0) for y0 in y0s]
-    L.call("cn_conv2d_fwd_grouped_bf16", G, _tab(xptr), xcs[0].pitch, _tab([w.data_ptr() for w in wps]),
-           _tab([b.data_ptr() for b in bds]), _tab([y.ptr for y in yas]), yas[0].pitch, B, Cin, H, W, Cout, k, k, 1,
-           pads, pads, 1, None, st)
+    with routes.part("grouped y +=", "acc"):
+        L.call("cn_conv2d_fwd_grouped_bf16", G, _tab(xptr), xcs[0].pitch, _tab([w.data_ptr() for w in wps]),
+               _tab([b.data_ptr() for b in bds]), _tab([y.ptr for y in yas]), yas[0].pitch, B, Cin, H, W, Cout, k, k, 1,
+               pads, pads, 1, None, st)
     # bnstats: bias-free; outputs must equal the plain launch
     yps = [Canvas((B, Cout, H, W), BF, dev, pitch=ld(Cout)) for _ in range(G)]
-    L.call("cn_conv2d_fwd_grouped_bf16", G, _tab(xptr), xcs[0].pitch, _tab([w.data_ptr() for w in wps]), None,
-           _tab([y.ptr for y in yps]), yps[0].pitch, B, Cin, H, W, Cout, k, k, 1, pads, pads, 0, None, st)
+    with routes.part("grouped y no bias"):
+        L.call("cn_conv2d_fwd_grouped_bf16", G, _tab(xptr), xcs[0].pitch, _tab([w.data_ptr() for w in wps]), None,
+               _tab([y.ptr for y in yps]), yps[0].pitch, B, Cin, H, W, Cout, k, k, 1, pads, pads, 0, None, st)
     rows = L.query("cn_conv2d_stats_rows_bf16", B, H, W, Cout, k, k, 1, 1, 1)
     stats = [torch.empty(rows * 2 * Cout, device=dev) for _ in range(G)]
     means = [torch.empty(Cout, device=dev) for _ in range(G)]
@@ -536,20 +782,23 @@ def test_grouped_bf16_exact(G, B, Cin, H, W, Cout, dils, shared_in):
     bn_ws = torch.zeros(nbn, device=dev)
     fin = ctypes.c_int(-1)
     ybs = [Canvas((B, Cout, H, W), BF, dev, pitch=ld(Cout)) for _ in range(G)]
-    L.call("cn_conv2d_fwd_grouped_bnstats_bf16", G, _tab(xptr), xcs[0].pitch, _tab([w.data_ptr() for w in wps]),
-           _tab([y.ptr for y in ybs]), ybs[0].pitch, B, Cin, H, W, Cout, k, k, 1, pads, pads,
-           _tab([s.data_ptr() for s in stats]), _tab([m.data_ptr() for m in means]), _tab([r.data_ptr() for r in rstds]),
-           None, None, 0.1, 1e-5, bn_ws.data_ptr(), nbn, ctypes.addressof(fin), st)
+    with routes.part("grouped y bnstats", "stats rows and finalize requested"):
+        L.call("cn_conv2d_fwd_grouped_bnstats_bf16", G, _tab(xptr), xcs[0].pitch, _tab([w.data_ptr() for w in wps]),
+               _tab([y.ptr for y in ybs]), ybs[0].pitch, B, Cin, H, W, Cout, k, k, 1, pads, pads,
+               _tab([s.data_ptr() for s in stats]), _tab([m.data_ptr() for m in means]),
+               _tab([r.data_ptr() for r in rstds]), None, None, 0.1, 1e-5, bn_ws.data_ptr(), nbn, ctypes.addressof(fin), st)
     dycs = [Canvas((B, Cout, H, W), BF, dev, pitch=ld(Cout), fill=GARB, data=d) for d in dys]
     dxcs = [Canvas((B, Cin, H, W), BF, dev, pitch=ld(Cin)) for _ in range(G)]
-    L.call("cn_conv2d_bwd_data_grouped_bf16", G, _tab([d.ptr for d in dycs]), dycs[0].pitch,
-           _tab([w.data_ptr() for w in wpts]), _tab([d.ptr for d in dxcs]), dxcs[0].pitch, B, Cin, H, W, Cout, k, k, 1,
-           pads, pads, 0, st)
+    with routes.part("grouped dx"):
+        L.call("cn_conv2d_bwd_data_grouped_bf16", G, _tab([d.ptr for d in dycs]), dycs[0].pitch,
+               _tab([w.data_ptr() for w in wpts]), _tab([d.ptr for d in dxcs]), dxcs[0].pitch, B, Cin, H, W, Cout, k, k,
+               1, pads, pads, 0, st)
     x0s = [ints((B, Cin, H, W), -8, 8, 350 + i) for i in range(G)]
     dxas = [Canvas((B, Cin, H, W), BF, dev, pitch=ld(Cin), data=x0) for x0 in x0s]
-    L.call("cn_conv2d_bwd_data_grouped_bf16", G, _tab([d.ptr for d in dycs]), dycs[0].pitch,
-           _tab([w.data_ptr() for w in wpts]), _tab([d.ptr for d in dxas]), dxas[0].pitch, B, Cin, H, W, Cout, k, k, 1,
-           pads, pads, 1, st)
+    with routes.part("grouped dx +=", "acc"):
+        L.call("cn_conv2d_bwd_data_grouped_bf16", G, _tab([d.ptr for d in dycs]), dycs[0].pitch,
+               _tab([w.data_ptr() for w in wpts]), _tab([d.ptr for d in dxas]), dxas[0].pitch, B, Cin, H, W, Cout, k, k,
+               1, pads, pads, 1, st)
     torch.cuda.synchronize()
     assert fin.value in (0, 1)
     for i in range(G):
@@ -563,6 +812,62 @@ def test_grouped_bf16_exact(G, B, Cin, H, W, Cout, dils, shared_in):
         assert_exact(dxcs[i].t, rb(refs[i][1]), f"dx{i}")
         dxcs[i].assert_canary(f"dx{i}")
         assert_exact(dxas[i].t, bf16_store(refs[i][1], x0s[i], Cin, True), f"dx{i} (+=)")
+    routes.verify()
+
+
+@pytest.mark.parametrize("G,B,Cin,H,W,Cout,k,s,ws_ok", [
+    (1, 2, 16, 26, 26, 128, 3, 2, True),    # strided, half-tile 128 couts: statistics finished inside the launch
+    (1, 2, 16, 26, 26, 64, 3, 2, True),     # strided, 64 couts
+    (1, 2, 72, 13, 13, 128, 1, 1, True),    # 1x1, deep chunks
+    (2, 113, 40, 5, 6, 128, 3, 1, False),   # two groups on the full-tile WN 4 route, finalize refused: rows only
+])
+def test_bnstats_bf16_strided_1x1_refused_exact(G, B, Cin, H, W, Cout, k, s, ws_ok, request, tmp_path):
+    """cn_conv2d_fwd_grouped_bnstats_bf16 at the routes of the training step that test_grouped_bf16_exact (3x3, stride
+    1) does not take: y equals float64 rounded to nearest even; with the finalize granted the means are the float64
+    means within 2^-20 (one fp32 division of an exact integer sum), and with the workspace withheld (ws_ok False) the
+    launch reports finalized = 0 and its per-tile rows sum to the exact per-channel sums."""
+    dev = _dev()
+    L, st = lib(), stream()
+    T, p = k * k, k // 2
+    Ho, Wo = out_size(H, W, k, s, p, 1)
+    xs = [ints((B, Cin, H, W), -4, 4, 360)] * G
+    wts = [ints((Cout, Cin, k, k), -3, 3, 361 + i) for i in range(G)]
+    premise("bnstats", term_bound(xs[0], wts[0], Cin * T), 16)
+    y64 = [F.conv2d(xs[i], wts[i], None, s, p, 1) for i in range(G)]
+    premise("bnstats channel sums", float(max(v.abs().max() for v in y64)) * B * Ho * Wo)
+    ld = lambda c: (c + 7) // 8 * 8 + 8
+    xc = Canvas(xs[0].shape, BF, dev, pitch=ld(Cin), fill=GARB, data=xs[0])
+    wps = [pack_bf16(w.float().to(dev), T, Cin, Cout, T, Cin * T, 1) for w in wts]
+    rows = L.query("cn_conv2d_stats_rows_bf16", B, H, W, Cout, k, k, s, p, 1)
+    stats = [torch.full((rows * 2 * Cout,), float("nan"), device=dev) for _ in range(G)]
+    means = [torch.full((Cout,), float("nan"), device=dev) for _ in range(G)]
+    rstds = [torch.full((Cout,), float("nan"), device=dev) for _ in range(G)]
+    nbn = L.query("cn_bn_group_workspace_floats_bf16", G, Cout)
+    bn_ws = torch.zeros(nbn, device=dev)
+    fin = ctypes.c_int(-1)
+    ycs = [Canvas((B, Cout, Ho, Wo), BF, dev, pitch=ld(Cout)) for _ in range(G)]
+    pads = _ints_c([p] * G)
+    dils = _ints_c([1] * G)
+    routes = Routes(case_id(request), tmp_path)
+    with routes.part("y bnstats", "finalize workspace given" if ws_ok else "finalize workspace withheld"):
+        L.call("cn_conv2d_fwd_grouped_bnstats_bf16", G, _tab([xc.ptr] * G), xc.pitch, _tab([w.data_ptr() for w in wps]),
+               _tab([y.ptr for y in ycs]), ycs[0].pitch, B, Cin, H, W, Cout, k, k, s, pads, dils,
+               _tab([t.data_ptr() for t in stats]), _tab([m.data_ptr() for m in means]),
+               _tab([r.data_ptr() for r in rstds]), None, None, 0.1, 1e-5, bn_ws.data_ptr(), nbn if ws_ok else 0,
+               ctypes.addressof(fin), st)
+    torch.cuda.synchronize()
+    assert fin.value == int(ws_ok), fin.value
+    for i in range(G):
+        assert_exact(ycs[i].t, rb(y64[i]), f"y{i}")
+        ycs[i].assert_canary(f"y{i}")
+        if ws_ok:
+            m64 = y64[i].mean(dim=(0, 2, 3))
+            err = (means[i].double().cpu() - m64).abs()
+            assert bool((err <= 2.0 ** -20 * m64.abs().clamp_min(1.0)).all()), f"mean{i}: worst {float(err.max())}"
+        else:
+            got = stats[i].double().cpu().view(rows, 2, Cout)[:, 0].sum(0)
+            assert_exact(got, y64[i].sum(dim=(0, 2, 3)), f"row sums {i}")
+    routes.verify()
 
 
 @pytest.mark.parametrize("B,Cin,H,W,Cout,k,s,p,d,res", [
@@ -571,7 +876,7 @@ def test_grouped_bf16_exact(G, B, Cin, H, W, Cout, dils, shared_in):
     (2, 64, 25, 25, 128, 3, 1, 2, 2, True),
     (2, 40, 10, 10, 64, 1, 1, 0, 1, True),
 ])
-def test_fused_bf16_exact(B, Cin, H, W, Cout, k, s, p, d, res):
+def test_fused_bf16_exact(B, Cin, H, W, Cout, k, s, p, d, res, request, tmp_path):
     """cn_conv2d_fwd_fused_bf16, act 0: y = bf16(bf16(conv(x, W * scale) + bias) + res), with the weights packed by
     cn_pack_weights_scaled_bf16 under power-of-two scales (exact)."""
     dev = _dev()
@@ -594,18 +899,22 @@ def test_fused_bf16_exact(B, Cin, H, W, Cout, k, s, p, d, res):
     yc = Canvas(y64.shape, BF, dev, pitch=ld(Cout))
     wp = pack_bf16(w.float().to(dev), T, Cin, Cout, T, Cin * T, 1, nscale=scale.float().to(dev))
     bd = b.float().to(dev)
-    L.call("cn_conv2d_fwd_fused_bf16", xc.ptr, xc.pitch, wp.data_ptr(), bd.data_ptr(), rc.ptr if res else None,
-           rc.pitch if res else 0, yc.ptr, yc.pitch, B, Cin, H, W, Cout, k, k, s, p, d, 0, st)
+    routes = Routes(case_id(request), tmp_path)
+    with routes.part("fused y", "res" if res else "no res"):
+        L.call("cn_conv2d_fwd_fused_bf16", xc.ptr, xc.pitch, wp.data_ptr(), bd.data_ptr(), rc.ptr if res else None,
+               rc.pitch if res else 0, yc.ptr, yc.pitch, B, Cin, H, W, Cout, k, k, s, p, d, 0, st)
     torch.cuda.synchronize()
     assert_exact(yc.t, ref, "fused y")
     yc.assert_canary("fused y")
     if res:  # in place: res aliases y
         ya = Canvas(y64.shape, BF, dev, pitch=ld(Cout), data=r)
-        L.call("cn_conv2d_fwd_fused_bf16", xc.ptr, xc.pitch, wp.data_ptr(), bd.data_ptr(), ya.ptr, ya.pitch, ya.ptr,
-               ya.pitch, B, Cin, H, W, Cout, k, k, s, p, d, 0, st)
+        with routes.part("fused y in place", "res"):
+            L.call("cn_conv2d_fwd_fused_bf16", xc.ptr, xc.pitch, wp.data_ptr(), bd.data_ptr(), ya.ptr, ya.pitch, ya.ptr,
+                   ya.pitch, B, Cin, H, W, Cout, k, k, s, p, d, 0, st)
         torch.cuda.synchronize()
         assert_exact(ya.t, ref, "fused y (res aliases y)")
         ya.assert_canary("fused y in place")
+    routes.verify()
 
 
 @pytest.mark.parametrize("B,Cin,H,W,Cout,s,acc", [
@@ -615,9 +924,15 @@ def test_fused_bf16_exact(B, Cin, H, W, Cout, k, s, p, d, res):
     (2, 32, 7, 7, 24, 4, False),       # stride 4
     (1, 24, 5, 6, 31, 2, True),        # ragged couts, tiny plane
     (1, 128, 25, 25, 128, 4, False),   # 25 -> 97
+    # interleaved parity classes at the block counts of the training step (route ledger): full-tile WN 4, 64 couts
+    (4, 128, 25, 25, 128, 4, False),
+    (32, 128, 13, 13, 128, 2, False),
+    (2, 64, 50, 50, 64, 2, False),
 ])
-def test_conv_transpose2d_bf16_exact(B, Cin, H, W, Cout, s, acc):
+def test_conv_transpose2d_bf16_exact(B, Cin, H, W, Cout, s, acc, request, tmp_path):
     dev = _dev()
+    routes = Routes(case_id(request), tmp_path)
+    facts = ("acc",) if acc else ()
     L, st = lib(), stream()
     k, p, T = 3, 1, 9
     Ho, Wo = (H - 1) * s - 2 * p + k, (W - 1) * s - 2 * p + k
@@ -639,12 +954,14 @@ def test_conv_transpose2d_bf16_exact(B, Cin, H, W, Cout, s, acc):
     # (every device argument stays referenced until the launches are done: a temporary freed at data_ptr() can be
     # handed to the next allocation before the kernel reads it)
     wp, wpt, bd = pack_bf16(wd, T, Cin, Cout, Cout * T, T, 1), pack_bf16(wd, T, Cout, Cin, T, Cout * T, 1), b.float().to(dev)
-    L.call("cn_conv_transpose2d_fwd_bf16", xc.ptr, xc.pitch, wp.data_ptr(), bd.data_ptr(), yc.ptr, yc.pitch, B, Cin, H,
-           W, Cout, k, k, s, p, int(acc), st)
+    with routes.part("transposed y", *facts):
+        L.call("cn_conv_transpose2d_fwd_bf16", xc.ptr, xc.pitch, wp.data_ptr(), bd.data_ptr(), yc.ptr, yc.pitch, B, Cin,
+               H, W, Cout, k, k, s, p, int(acc), st)
     dyc = Canvas(dy.shape, BF, dev, pitch=ld(Cout), fill=GARB, data=dy)
     dxc = Canvas(x.shape, BF, dev, pitch=ld(Cin), data=x0)
-    L.call("cn_conv_transpose2d_bwd_data_bf16", dyc.ptr, dyc.pitch, wpt.data_ptr(), dxc.ptr, dxc.pitch, B, Cin, H, W,
-           Cout, k, k, s, p, int(acc), st)
+    with routes.part("transposed dx", *facts):
+        L.call("cn_conv_transpose2d_bwd_data_bf16", dyc.ptr, dyc.pitch, wpt.data_ptr(), dxc.ptr, dxc.pitch, B, Cin, H, W,
+               Cout, k, k, s, p, int(acc), st)
     torch.cuda.synchronize()
     assert_exact(yc.t, bf16_store(y64, y0, Cout, acc), "y")
     yc.assert_canary("y")
@@ -654,11 +971,13 @@ def test_conv_transpose2d_bf16_exact(B, Cin, H, W, Cout, s, acc):
         n = bwgrad_ws_floats(B, Cin, H, W, Cout, k, s, p, 1, 1, mode)
         ws = torch.empty(n + 4, device=dev)
         dwc = Canvas(w.shape, F32, dev, data=w0)
-        L.call("cn_conv_transpose2d_bwd_weight_bf16", xc.ptr, xc.pitch, dyc.ptr, dyc.pitch, dwc.ptr, B, Cin, H, W, Cout,
-               k, k, s, p, ws.data_ptr(), n, st)
+        with routes.part(f"transposed dw ws {mode}"):
+            L.call("cn_conv_transpose2d_bwd_weight_bf16", xc.ptr, xc.pitch, dyc.ptr, dyc.pitch, dwc.ptr, B, Cin, H, W,
+                   Cout, k, k, s, p, ws.data_ptr(), n, st)
         torch.cuda.synchronize()
         assert_exact(dwc.t, dw64 + w0, f"dw ws={mode}")
         dwc.assert_canary("dw")
+    routes.verify()
 
 
 # ---------------------------------------------------------------------------------------------------------------------

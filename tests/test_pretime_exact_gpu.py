@@ -66,6 +66,8 @@ import pytest
 import torch
 
 import pretime_ref as R
+from conv_exact_worker import part
+from route_ledger import Routes, case_id
 
 pytestmark = pytest.mark.gpu
 
@@ -121,8 +123,11 @@ def _tab(bufs):
 class Run:
     """One configuration on the device: buffers, the two ABI calls, the read-back in the reference's names."""
 
-    def __init__(self, case, x, prm, dy, training=True, backward=True, g0=None, strided=False, xpad=0, xbuf=None):
+    def __init__(self, case, x, prm, dy, training=True, backward=True, g0=None, strided=False, xpad=0, xbuf=None,
+                 routes=None):
         from cultionet_amd import _lib
+
+        self.routes = routes  # tests/route_ledger.py Routes of the calling test, or None
 
         self.lib = _lib
         B, C, T, HW, Cout, kind = case
@@ -191,9 +196,10 @@ class Run:
     def forward(self):
         B, C, T, HW, Cout, kind = self.case
         s = torch.cuda.current_stream().cuda_stream
-        self.lib.call("cn_pretime_fwd_f32", self.xptr, self.xbs, _tab(self.params), _tab(self.stats), self.bufs["y"].ptr,
-                      self.stride, kind, B, C, T, HW, Cout, int(self.training), self.bn, R.LN_EPS, self.bufs["ws"].ptr,
-                      self.need, s)
+        with part(self.routes, "forward", "training" if self.training else "eval"):
+            self.lib.call("cn_pretime_fwd_f32", self.xptr, self.xbs, _tab(self.params), _tab(self.stats),
+                          self.bufs["y"].ptr, self.stride, kind, B, C, T, HW, Cout, int(self.training), self.bn, R.LN_EPS,
+                          self.bufs["ws"].ptr, self.need, s)
         self._after("forward")
         out = {"y": self._layout(self.bufs["y"].get())}
         for k in R.BR:
@@ -207,9 +213,10 @@ class Run:
     def backward_(self):
         B, C, T, HW, Cout, kind = self.case
         s = torch.cuda.current_stream().cuda_stream
-        self.lib.call("cn_pretime_bwd_f32", self.xptr, self.xbs, _tab(self.params), _tab(self.stats), self.bufs["dy"].ptr,
-                      self.stride, kind, _tab(self.grads), B, C, T, HW, Cout, int(self.training), self.bn, R.LN_EPS,
-                      self.bufs["ws"].ptr, self.need, s)
+        with part(self.routes, "backward", "training" if self.training else "eval"):
+            self.lib.call("cn_pretime_bwd_f32", self.xptr, self.xbs, _tab(self.params), _tab(self.stats),
+                          self.bufs["dy"].ptr, self.stride, kind, _tab(self.grads), B, C, T, HW, Cout, int(self.training),
+                          self.bn, R.LN_EPS, self.bufs["ws"].ptr, self.need, s)
         self._after("backward")
         return {n: self.bufs[n].get() for n in R.GRAD_NAMES}
 
@@ -223,12 +230,12 @@ def _check(tag, got, ref, kind):
         R.within(v, ref[n], f"{tag} {n}", RECORD, R.group_of(n, kind))
 
 
-def _full(tag, case, training=True, backward=True, accumulate=False, strided=False, xpad=0):
+def _full(tag, case, training=True, backward=True, accumulate=False, strided=False, xpad=0, routes=None):
     """Forward (+ backward) of one configuration checked against float64 -> (Run, outputs, problem)."""
     B, C, T, HW, Cout, kind = case
     prob = R.problem(B, C, T, HW, Cout, kind, training, backward, accumulate, _generic())
     x, prm, dy, g0, ref = prob
-    run = Run(case, x, prm, dy, training, backward, g0, strided, xpad)
+    run = Run(case, x, prm, dy, training, backward, g0, strided, xpad, routes=routes)
     got = run.forward()
     if backward:
         got.update(run.backward_())
@@ -245,13 +252,25 @@ def _report():
 # ---------------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("name", list(R.dispatch_cases()))
-def test_dispatch(name):
+def test_dispatch(name, request, tmp_path):
     from cultionet_amd import _lib
 
     case = R.dispatch_cases()[name]
     served = not name.startswith(R.NO_BACKWARD)
     assert (_lib.query("cn_pretime_workspace_floats", *case[:5], 1) > 0) == served
-    _full(f"dispatch {name}", case, backward=served)
+    # (the generic-kernel child forces its kernel through CN_PRETIME_REG: forcing is its purpose, no route is asserted)
+    routes = None if _generic() else Routes(case_id(request), tmp_path)
+    _full(f"dispatch {name}", case, backward=served, routes=routes)
+    if routes is not None:
+        routes.verify()
+
+
+def test_small_cube_one_entry_tile(request, tmp_path):
+    """C (T - 2) = 24 <= 32 outside the register variant's cube: the generic kernels with ONE entry tile in the gradient
+    pass (cn_pretime_kernel<4, 4, 1, 1>), which no cube of the dispatch cases selects without CN_PRETIME_REG=0."""
+    routes = Routes(case_id(request), tmp_path)
+    _full("small cube c4t8", (2, 4, 8, 173, 8, 0), routes=routes)
+    routes.verify()
 
 
 def test_ne3_gradient_pass_has_no_servable_shape():
@@ -283,19 +302,23 @@ def test_generic_kernel_child():
 
 
 @pytest.mark.parametrize("name", list(R.WIDE_CASES))
-def test_wide_outputs(name):
+def test_wide_outputs(name, request, tmp_path):
     from cultionet_amd import _lib
 
     case = R.WIDE_CASES[name]
     B, C, T, HW, Cout, kind = case
     assert _lib.query("cn_pretime_workspace_floats", B, C, T, HW, Cout, 1) == -1
-    _full(f"wide train {name}", case, backward=False)
-    _full(f"wide inference {name}", case, training=False, backward=False)
+    routes = Routes(case_id(request), tmp_path)
+    _full(f"wide train {name}", case, backward=False, routes=routes)
+    _full(f"wide inference {name}", case, training=False, backward=False, routes=routes)
+    routes.verify()
 
 
 @pytest.mark.parametrize("name", list(R.EVAL_CASES))
-def test_eval_backward(name):
-    run, got, (x, prm, dy, g0, ref) = _full(f"eval {name}", R.EVAL_CASES[name], training=False)
+def test_eval_backward(name, request, tmp_path):
+    routes = Routes(case_id(request), tmp_path)
+    run, got, (x, prm, dy, g0, ref) = _full(f"eval {name}", R.EVAL_CASES[name], training=False, routes=routes)
+    routes.verify()
     for k, p in zip(R.BR, prm["br"]):
         for n in ("rm3", "rv3", "rm2", "rv2"):
             assert torch.equal(run.bufs[f"p_{n}_{k}"].get(), p[n]), f"{n}_{k} changed with training = 0"
@@ -331,10 +354,12 @@ def test_pixel_edges(cube, P):
 
 
 @pytest.mark.parametrize("name", list(R.TILE_CASES))
-def test_more_tiles_than_blocks(name):
+def test_more_tiles_than_blocks(name, request, tmp_path):
     B, C, T, HW, Cout, kind, train = R.TILE_CASES[name]
     assert (B * HW) % 128 != 0
-    _full(f"tiles {name}", (B, C, T, HW, Cout, kind), training=train, backward=train)
+    routes = Routes(case_id(request), tmp_path)
+    _full(f"tiles {name}", (B, C, T, HW, Cout, kind), training=train, backward=train, routes=routes)
+    routes.verify()
 
 
 @pytest.mark.parametrize("which", ["register", "generic"])

@@ -24,7 +24,8 @@ import torch
 
 import slicesum_ref as R
 from conv_exact_worker import (BF, F32, GARB, SENT, SLACK, Canvas, assert_exact, bwgrad_ws_floats, ints, lib, out_size,
-                               premise, ref_conv, ref_convT, stream, term_bound, wgrad_ws_f32)
+                               part, premise, ref_conv, ref_convT, stream, term_bound, wgrad_ws_f32)
+from route_ledger import Routes, case_id
 
 pytestmark = pytest.mark.gpu
 
@@ -455,14 +456,16 @@ class Wgrad:
         return ns
 
 
-def _deferred_exact(calls, classes, what):
-    """Every call into one sink: the dWs keep their prefill until the run, then equal float64; records as expected."""
+def _deferred_exact(calls, classes, what, routes=None):
+    """Every call into one sink: the dWs keep their prefill until the run, then equal float64; records as expected.
+    routes (tests/route_ledger.py): learns the kernel of every call, launched under the active sink."""
     dev = _dev()
     grad = Grad(sum(c.floats() for c in calls) + 16, dev)
     dws = [c.place(grad) for c in calls]
     with _sink_over(grad) as sink:
-        for c, d in zip(calls, dws):
-            c.launch(d)
+        for i, (c, d) in enumerate(zip(calls, dws)):
+            with part(routes, f"dw {i} {c.kind}", "sink active", f"ws {c.wsmode}"):
+                c.launch(d)
         torch.cuda.synchronize()
         assert sink.count == sum(c.G for c in calls), (what, sink.count)
         recs = sink.records()
@@ -491,12 +494,15 @@ F32_CASES = [
     (F32_WAVES, "waves"),
     ((4, 8, 28, 28, 8, 1, 1, 1), "flat"),   # 1x1
     ((4, 8, 56, 56, 8, 3, 2, 1), "flat"),   # stride 2: the 28 x 28 gradient plane is chunked, 28 slices again
+    ((4, 8, 100, 100, 40, 3, 2, 1), "flat"),  # single-buffered staging (more than 32 couts, 100-wide stride-2 halo)
 ]
 
 
 @pytest.mark.parametrize("case,cls", F32_CASES)
-def test_f32_weight_gradient_deferred_exact(case, cls):
-    recs = _deferred_exact([Wgrad("f32", case, 300)], [cls], f"f32 {case}")
+def test_f32_weight_gradient_deferred_exact(case, cls, request, tmp_path):
+    routes = Routes(case_id(request), tmp_path)
+    recs = _deferred_exact([Wgrad("f32", case, 300)], [cls], f"f32 {case}", routes)
+    routes.verify()
     if case in (F32_FLAT, F32_WAVES):
         assert int(recs[0]["nslices"]) == (28 if case == F32_FLAT else 200)
 
@@ -515,10 +521,37 @@ def test_f32_few_slices_are_not_deferred():
     grad.assert_untouched_outside("few slices")
 
 
+@pytest.mark.parametrize("kind,case,G", [
+    ("f32", (2, 8, 12, 12, 8, 3, 1, 1), 1),
+    ("f32g", (2, 8, 12, 12, 8, 3, 1, 1), 2),     # two sets per launch
+    ("f32", (2, 8, 12, 12, 8, 1, 1, 1), 1),      # 1x1
+    ("f32", (4, 8, 25, 25, 40, 3, 2, 1), 1),     # single-buffered stride-2 staging from an odd plane, 8 splits
+])
+def test_f32_below_16_slices_under_a_sink_exact(kind, case, G, request, tmp_path):
+    """Fewer than 16 splits with a sink active, as most fp32 weight gradients of a training step run: float atomics
+    straight into every dW, nothing pushed, equal to float64 (integer inputs)."""
+    dev = _dev()
+    c = Wgrad(kind, case, 315, G=G)
+    grad = Grad(c.floats() + 16, dev)
+    dws = c.place(grad)
+    routes = Routes(case_id(request), tmp_path)
+    with _sink_over(grad) as sink:
+        with routes.part("dw", "sink active", "ws full"):
+            c.launch(dws)
+        torch.cuda.synchronize()
+        assert sink.count == 0
+        for g in range(G):
+            assert_exact(dws[g].t, c.want(g), f"dW {g} complete at once")
+    grad.assert_untouched_outside("few slices")
+    routes.verify()
+
+
 @pytest.mark.parametrize("G", [2, 4])
-def test_f32_grouped_weight_gradient_deferred_exact(G):
+def test_f32_grouped_weight_gradient_deferred_exact(G, request, tmp_path):
     """G records from one push, their slices G * 28 in a row."""
-    _deferred_exact([Wgrad("f32g", F32_FLAT, 320, G=G)], [28], f"f32 grouped G={G}")
+    routes = Routes(case_id(request), tmp_path)
+    _deferred_exact([Wgrad("f32g", F32_FLAT, 320, G=G)], [28], f"f32 grouped G={G}", routes)
+    routes.verify()
 
 
 BF16_CASES = [
@@ -530,7 +563,11 @@ BF16_CASES = [
     ((2, 64, 25, 25, 64, 3, 1, 1), "one"),
     ((2, 64, 25, 25, 64, 3, 1, 1), "mid"),
     ((4, 8, 28, 28, 8, 3, 1, 1), "full"),   # at least 7 tiles per image whatever the tile: 28 or more splits, so the
-]                                           # 16-step loop of the sum really runs
+                                            # 16-step loop of the sum really runs
+    ((2, 16, 13, 13, 24, 1, 1, 1), "full"),  # routes of the training step (route ledger): 1x1 on an odd plane,
+    ((2, 16, 20, 50, 24, 3, 2, 1), "full"),  # stride 2 on 5 x 25 tiles,
+    ((2, 16, 29, 29, 24, 3, 4, 1), "full"),  # stride 4
+]
 
 
 def _bf16_class(case, ws):
@@ -538,9 +575,11 @@ def _bf16_class(case, ws):
 
 
 @pytest.mark.parametrize("case,ws", BF16_CASES)
-def test_bf16_weight_gradient_deferred_exact(case, ws):
+def test_bf16_weight_gradient_deferred_exact(case, ws, request, tmp_path):
     """Every bf16 weight gradient defers, with one split too."""
-    recs = _deferred_exact([Wgrad("bf16", case, 400, ws=ws)], [_bf16_class(case, ws)], f"bf16 {case} ws={ws}")
+    routes = Routes(case_id(request), tmp_path)
+    recs = _deferred_exact([Wgrad("bf16", case, 400, ws=ws)], [_bf16_class(case, ws)], f"bf16 {case} ws={ws}", routes)
+    routes.verify()
     ns = int(recs[0]["nslices"])
     if ws == "mid":
         assert ns > 1, "the in-between workspace was meant to leave more than one split"
@@ -548,16 +587,20 @@ def test_bf16_weight_gradient_deferred_exact(case, ws):
         assert ns >= 13, "chosen so that the 16-step loop runs"
 
 
-def test_bf16_transposed_weight_gradient_deferred_exact():
-    _deferred_exact([Wgrad("bf16t", (2, 16, 13, 13, 16, 3, 2, 1), 410)], ["relayout"], "bf16 ConvTranspose2d")
+def test_bf16_transposed_weight_gradient_deferred_exact(request, tmp_path):
+    routes = Routes(case_id(request), tmp_path)
+    _deferred_exact([Wgrad("bf16t", (2, 16, 13, 13, 16, 3, 2, 1), 410)], ["relayout"], "bf16 ConvTranspose2d", routes)
+    routes.verify()
 
 
-def test_mixed_flush_exact():
+def test_mixed_flush_exact(request, tmp_path):
     """Three fp32 and three bf16 launches into one sink, one run."""
     calls = [Wgrad("f32", F32_FLAT, 500), Wgrad("bf16", (2, 16, 13, 13, 31, 3, 1, 1), 510),
              Wgrad("f32", F32_WAVES, 520), Wgrad("bf16", (2, 24, 14, 14, 129, 3, 1, 2), 530),
              Wgrad("bf16", (2, 136, 9, 11, 256, 1, 1, 1), 540), Wgrad("f32", (4, 8, 28, 28, 8, 1, 1, 1), 550)]
-    _deferred_exact(calls, ["flat", "relayout", "waves", "relayout", "relayout", "flat"], "mixed flush")
+    routes = Routes(case_id(request), tmp_path)
+    _deferred_exact(calls, ["flat", "relayout", "waves", "relayout", "relayout", "flat"], "mixed flush", routes)
+    routes.verify()
 
 
 def _immediate_and_deferred(kind, case, ws, seed):
@@ -580,8 +623,11 @@ def _immediate_and_deferred(kind, case, ws, seed):
     return imm[0], dfr[0], rec, c
 
 
-@pytest.mark.parametrize("kind,case,ws", [("f32", c, "full") for c, cls in F32_CASES if cls == "flat"] +
-                         [("bf16", c, ws) for c, ws in BF16_CASES] + [("bf16t", (2, 16, 13, 13, 16, 3, 2, 1), "full")])
+# (the cases the route ledger added to F32_CASES / BF16_CASES follow the earlier ones, which keep their ids)
+@pytest.mark.parametrize("kind,case,ws", [("f32", c, "full") for c, cls in F32_CASES[:4] if cls == "flat"] +
+                         [("bf16", c, ws) for c, ws in BF16_CASES[:8]] + [("bf16t", (2, 16, 13, 13, 16, 3, 2, 1), "full")] +
+                         [("f32", c, "full") for c, cls in F32_CASES[4:] if cls == "flat"] +
+                         [("bf16", c, ws) for c, ws in BF16_CASES[8:]])
 def test_deferred_is_bitwise_the_immediate_sum(kind, case, ws):
     """Random inputs: the batched launch sums every output with the association of the immediate kernel, so wherever
     that kernel is deterministic (bf16 always; fp32 up to 128 slices) the two results are the same bits."""

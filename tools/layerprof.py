@@ -12,7 +12,7 @@ path = sys.argv[1]
 steps = float(sys.argv[2]) if len(sys.argv) > 2 else 1.0
 agg = defaultdict(lambda: [0.0, 0.0, 0])
 for line in open(path):
-    kind, desc, us, fl = line.rstrip("\n").split("\t")
+    kind, desc, us, fl = line.rstrip("\n").split("\t")[:4]  # (a fifth column names the kernel)
     a = agg[desc]
     a[0] += float(us); a[1] += float(fl); a[2] += 1
 rows = sorted(agg.items(), key=lambda kv: -kv[1][0])

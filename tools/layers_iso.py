@@ -51,7 +51,7 @@ with E.branch_streams(False):
     _lib.call("cn_profile_end", (ctypes.c_double * 24)())
 agg = defaultdict(lambda: [0.0, 0.0, 0])
 for line in open(dump):
-    kind, desc, us, fl = line.rstrip("\n").split("\t")
+    kind, desc, us, fl = line.rstrip("\n").split("\t")[:4]  # (a fifth column names the kernel)
     a = agg[desc]
     a[0] += float(us); a[1] += float(fl); a[2] += 1
 os.unlink(dump)
