@@ -1133,9 +1133,10 @@ extern "C" long cn_pretime_workspace_floats(int B, int C, int T, int HW, int Cou
   if (!pt_supported(C, T, Cout)) return -1;
   for (int ps = 0; ps < (with_backward ? 6 : 3); ++ps)  // every pass the caller may launch must fit the 160 KiB LDS
     if (pt_shmem(ps, C, T, Cout) > 160 * 1024) return -1;
-  // dWb accumulator registers of the gradient pass: up to three 32-entry tiles per branch at Cout <= 32; the two-tile
-  // Cout = 64 instantiation spills (1 KB per lane) and is left to the generic path for now
-  if (with_backward && (pt_ne(C, T) > 3 || Cout > 32)) return -1;
+  // The gradient passes are built for one cout tile (Cout <= 32: the two-tile Cout = 64 instantiation of the dWb
+  // accumulators spills, 1 KB per lane) and up to two 32-entry tiles per branch. (Three entry tiles, 65 <= C (T - 2)
+  // <= 96, never fitted anyway: the LDS image of pass 4 is beyond 160 KiB at every such cube.)
+  if (with_backward && (pt_ne(C, T) > 2 || Cout > 32)) return -1;
   const long E = (long)C * (T - 2) + (long)C * (T - 4);
   long n = pt_off_body() + pt_body_floats(C, T, Cout) + 4L * pt_ceil32(Cout) + 4L * C + 128 +
            ((pt_lds(4, C, T, Cout, pt_cmax(C)).xs + 63) / 64 * 64);
@@ -1189,6 +1190,8 @@ static int pt_launch(CnPtArgs a, float* ws, hipStream_t stream) {
   if (W > 0) a.tk = cn_t2_carve(reinterpret_cast<int*>(ws), ws + pt_off_body(), nblk, W);
   const int MT = a.Cout > 32 ? 2 : 1;
   const int NE = PASS == 4 ? pt_ne(a.C, a.T) : 1;
+  // the gradient passes have no instantiation for what cn_pretime_workspace_floats refuses with backward
+  if (PASS >= 3 && (MT == 2 || NE > 2)) return CN_ERR_ARG;
 #define PT_GO(CM, MT_, NE_)                                                                                    \
   do {                                                                                                         \
     if (shmem > 64 * 1024)                                                                                     \
@@ -1198,20 +1201,20 @@ static int pt_launch(CnPtArgs a, float* ws, hipStream_t stream) {
   } while (0)
 #define PT_GO_MT(CM)                                                                                           \
   do {                                                                                                         \
-    if constexpr (PASS == 4) {                                                                                 \
-      if (MT == 2) PT_GO(CM, 2, 1);                                                                            \
-      else if (NE == 1) PT_GO(CM, 1, 1); else if (NE == 2) PT_GO(CM, 1, 2); else PT_GO(CM, 1, 3);              \
-    } else {                                                                                                   \
+    if constexpr (PASS < 3) {                                                                                  \
       if (MT == 2) PT_GO(CM, 2, 1); else PT_GO(CM, 1, 1);                                                      \
+    } else if constexpr (PASS == 4) {                                                                          \
+      if (NE == 1) PT_GO(CM, 1, 1); else PT_GO(CM, 1, 2);                                                      \
+    } else {                                                                                                   \
+      PT_GO(CM, 1, 1);                                                                                         \
     }                                                                                                          \
   } while (0)
   const bool prof = cn_prof_on();  // per-pass times for tools/pretime_bench.py (kind 6: not a contraction kernel)
   if (prof) {
     cn_prof_name("cn_pretime_kernel<%d%s>", PASS, reg ? ", reg" : "");
     // the instantiation the branches below select (the name above is what bench.py aggregates by)
-    const int ne = (PASS == 4 && MT != 2) ? NE : 1;
     if (reg) cn_prof_desc("pretime<%d, 4, 1, 1, %s> B%d C%d T%d HW%d Cout%d", PASS, a.C == 3 ? "3, 12" : "4, 25", a.B, a.C, a.T, a.HW, a.Cout);
-    else cn_prof_desc("pretime<%d, %d, %d, %d, 0, 0> B%d C%d T%d HW%d Cout%d", PASS, pt_cmax(a.C), MT, ne, a.B, a.C, a.T, a.HW, a.Cout);
+    else cn_prof_desc("pretime<%d, %d, %d, %d, 0, 0> B%d C%d T%d HW%d Cout%d", PASS, pt_cmax(a.C), MT, NE, a.B, a.C, a.T, a.HW, a.Cout);
     cn_prof_before(stream);
   }
   if (reg && a.C == 3) {  // Cout <= 32, C T = 36: one cout tile, one entry tile per branch

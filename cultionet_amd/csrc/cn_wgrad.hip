@@ -21,9 +21,9 @@
 #define WG_BC 32   // b-channels per block
 #define WG_NS 4    // max S elements per lane per row of the chunk  (chunk pixels <= 256)
 #define WG_NB 13   // max Bg plane elements per lane               (plane_b <= 832)
-#define WG_KS 8    // 16-byte variant: DMA instructions per wave for the S image  (arows*npix <= 8192 floats)
-#define WG_U 4     // 16-byte variant: k-steps per unrolled group
-#define WG_KB 16   // 16-byte variant: DMA instructions per wave for the Bg image (32*plane_b <= 16384 floats)
+#define WG_DS 32   // 16-byte variant: DMA instructions (1 KiB each) for the S image of a chunk  (arows*npix <= 8192 floats)
+#define WG_DB 64   // 16-byte variant: DMA instructions for the Bg image of a chunk (32*plane_b <= 16384 floats)
+#define WG_U 4     // 16-byte variant, 1 x 1: k-steps per unrolled group
 
 struct CnWgradGeom {
   int N;
@@ -215,17 +215,6 @@ __global__ __launch_bounds__(256) void cn_wgrad_kernel(const float* __restrict__
 
 __device__ float cn_zero_line16[256];  // 1 KiB of zeros: per-lane 16-byte zero source
 
-// Diagnostic build (-DCNW_STAMP): s_memtime stamps of wave 0 of block 0 over its first chunks (tools/wgrad_stamps.py).
-#ifdef CNW_STAMP
-__device__ unsigned long long cnw_stamps[256];
-#define CNW_ST() do { if (do_stamp && stamp_i < 256) cnw_stamps[stamp_i++] = __builtin_amdgcn_s_memtime(); } while (0)
-extern "C" int cn_wgrad_read_stamps(unsigned long long* out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(cnw_stamps), sizeof(unsigned long long) * 256) == hipSuccess ? 0 : -2;
-}
-#else
-#define CNW_ST() do { } while (0)
-#endif
-
 __device__ __forceinline__ void cn_glds16(const float* src, float* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((cn_gbl_ptr)src, (cn_lds_ptr)lds_wave_base, 16, 0, 0);
 }
@@ -236,568 +225,29 @@ __device__ __forceinline__ void cn_glds16(const float* src, float* lds_wave_base
 // bound check and column overruns (which wrap into the neighbouring row) are masked per lane at operand read.
 // One DMA wave-instruction moves 1 KiB instead of 256 B: the per-CU DMA issue rate (~1 per 100 cycles)
 // is what bounded the dword version.
+// Two kernels, ONE body (cn_wgrad_vec_body.h, compiled into each): a block is a tile of 32 * a_tiles couts x 32
+// channels x all taps, and a wave owns one kernel row of the taps of one cout tile for a share of the pixel pairs.
+//
+// 1 x 1: four waves, one tap and one accumulator tile per wave.
 template <int T, int S_>
 __global__ __launch_bounds__(256) void cn_wgrad_vec_kernel(const float* __restrict__ S0, const float* __restrict__ Bg0,
                                                           float* __restrict__ dW0, const CnWgradGeom g) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int half = lane >> 5, l31 = lane & 31;
-  const int at = wid % g.a_tiles, kp = wid / g.a_tiles, kparts = 4 / g.a_tiles;
-  int bx, by, bz;
-  if (!cn_xcd_block(g.grid_x, g.grid_y, g.grid_x * g.grid_y * g.grid_z, bx, by, bz)) return;
-  const int grp = g.G > 1 ? bz / g.spg : 0;
-  const int split = bz - grp * g.spg;
-  const float* __restrict__ S = g.G > 1 ? g.gS[grp] : S0;
-  const float* __restrict__ Bg = g.G > 1 ? g.gB[grp] : Bg0;
-  float* __restrict__ dW = (g.G > 1 && g.slice_stride == 0) ? g.gdW[grp] : dW0;
-  const int a0 = by * g.a_tiles * 32;
-  const int b0 = bx * WG_BC;
-  const int npix = g.PR * g.Ws;   // unpadded, even, multiple of 4
-  const int n4s = npix >> 2;      // float4 pieces per S row (<= 64)
-  const int n4b = g.plane_b >> 2; // float4 pieces per Bg channel image
-  const float* zero = cn_zero_line16 + 4 * lane;
-  const int HWs = g.Hs * g.Ws, HWb = g.Hb * g.Wb;
-
-  int boff[T], ox[T];
-#pragma unroll
-  for (int j = 0; j < T; ++j) {
-    const int n = j * 32 + l31;
-    const int bl = n / T, t = n - bl * T;
-    boff[j] = bl * g.plane_b + (g.offy[t] - g.min_oy) * g.Wb + (g.offx[t] - g.min_ox) + half * g.s;
-    ox[j] = g.offx[t] + half * g.s;
-  }
-  const int aoff = (at * 32 + l31) * g.pitch_s + half;
-
-  f32x16 acc[T];
-#pragma unroll
-  for (int j = 0; j < T; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-
-  const int arows = g.a_tiles * 32;
-  int chunk = split * g.chunks_per_split;
-  int chunk_end = chunk + g.chunks_per_split;
-  if (chunk_end > g.total_chunks) chunk_end = g.total_chunks;
-
-  const int steps = npix >> 1;
-  const int q_begin = (steps * kp) / kparts, q_end = (steps * (kp + 1)) / kparts;
-  const int e_begin = q_begin * 2;
-  const int r_begin = e_begin / g.Ws, c_begin = e_begin - r_begin * g.Ws;
-
-  // dense LDS images: S [arows][npix], Bg [WG_BC][plane_b]; piece p of an image = its p-th 16 bytes, so one
-  // DMA wave-instruction (64 consecutive pieces = 1 KiB) may span several rows / channels.
-  // Per-lane BYTE offset of this lane's piece in DMA instruction k, relative to the chunk's base address (S: first
-  // pixel of the chunk in channel 0 of image n; Bg: the 16-byte aligned start of the halo in channel 0), or WG_IDLE
-  // for lanes past the image / past the channel count (their LDS rows only feed dW entries that are never stored).
-  // (Measured and not kept: issuing an interior chunk's DMA instructions singly between the MFMA groups instead of
-  // back to back -- each then stalls the wave ~330 instead of ~126 cycles: 252 -> 311 us at 128->128, 100^2.)
-  // Interior chunks -- all but the first / last rows of an image -- then stage with ONE instruction per KiB: scalar
-  // base + per-lane offset, no per-chunk address arithmetic or bound checks (those took ~3000 cycles per chunk with
-  // the matrix pipe idle: one wave per SIMD). Boundary chunks re-derive the piece index and zero-fill per piece.
-  constexpr unsigned WG_IDLE = 0xFFFFFFFFu;
-  unsigned so[WG_KS], bo[WG_KB];
-  {
-    const int nsp = arows * n4s, nbp = WG_BC * n4b;
-#pragma unroll
-    for (int k = 0; k < WG_KS; ++k) {
-      const int p = (wid + 4 * k) * 64 + lane;
-      const int a = p / n4s, pc = p - a * n4s;
-      so[k] = (p < nsp && (a0 + a) < g.A) ? (unsigned)(((long)(a0 + a) * g.scs + 4 * pc) * 4) : WG_IDLE;
-    }
-#pragma unroll
-    for (int k = 0; k < WG_KB; ++k) {
-      const int p = (wid + 4 * k) * 64 + lane;
-      const int bl = p / n4b, pi = p - bl * n4b;
-      bo[k] = (p < nbp && (b0 + bl) < g.Bc) ? (unsigned)(((long)(b0 + bl) * g.bcs + 4 * pi) * 4) : WG_IDLE;
-    }
-  }
-  auto stage = [&](int ck, int buf) {
-    float* s_lds = smem + buf * g.buf_stride;
-    float* b_lds = s_lds + g.b_lds_off;
-    const int n = ck / g.chunks_per_img;
-    const int gy0 = (ck - n * g.chunks_per_img) * g.PR;
-    const int nsp = arows * n4s, nbp = WG_BC * n4b;
-    {
-      const int fs0 = gy0 * g.Ws;
-      const char* sbase = reinterpret_cast<const char*>(S + (long)n * g.sbs + fs0);
-      if (fs0 + npix <= (int)g.scs) {  // wave-uniform: the whole chunk lies inside the plane
-#pragma unroll
-        for (int k = 0; k < WG_KS; ++k)
-          if ((wid + 4 * k) * 64 < nsp && so[k] != WG_IDLE)
-            cn_glds16(reinterpret_cast<const float*>(sbase + so[k]), s_lds + (wid + 4 * k) * 256);
-      } else {
-#pragma unroll
-        for (int k = 0; k < WG_KS; ++k) {
-          if ((wid + 4 * k) * 64 < nsp && so[k] != WG_IDLE) {
-            const int p = (wid + 4 * k) * 64 + lane;
-            const int pc = p % n4s;
-            const bool ok = (fs0 + 4 * pc + 3) < (int)g.scs;
-            const float* src = ok ? reinterpret_cast<const float*>(sbase + so[k]) : zero;
-            cn_glds16(src, s_lds + (wid + 4 * k) * 256);
-          }
-        }
-      }
-    }
-    {
-      const int start = (gy0 * g.s + g.min_oy) * g.Wb + g.min_ox;
-      const int f0 = (start >> 2) << 2;
-      const char* bbase = reinterpret_cast<const char*>(Bg + (long)n * g.bbs + f0);
-      if (f0 >= 0 && f0 + g.plane_b <= (int)g.bcs) {  // wave-uniform: the halo lies inside the plane
-#pragma unroll
-        for (int k = 0; k < WG_KB; ++k)
-          if ((wid + 4 * k) * 64 < nbp && bo[k] != WG_IDLE)
-            cn_glds16(reinterpret_cast<const float*>(bbase + bo[k]), b_lds + (wid + 4 * k) * 256);
-      } else {
-#pragma unroll
-        for (int k = 0; k < WG_KB; ++k) {
-          if ((wid + 4 * k) * 64 < nbp && bo[k] != WG_IDLE) {
-            const int p = (wid + 4 * k) * 64 + lane;
-            const int fq = f0 + 4 * (p % n4b);
-            const bool ok = fq >= 0 && (fq + 3) < (int)g.bcs;
-            const float* src = ok ? reinterpret_cast<const float*>(bbase + bo[k]) : zero;
-            cn_glds16(src, b_lds + (wid + 4 * k) * 256);
-          }
-        }
-      }
-    }
-  };
-
-  int cur = 0;
-#ifdef CNW_STAMP
-  const bool do_stamp = T == 9 && S_ == 1 && blockIdx.x == 8 && tid == 0;
-  int stamp_i = 0;
-#endif
-  CNW_ST();  // 0: prologue done
-  if (chunk < chunk_end && g.nbuf == 2) stage(chunk, 0);
-  for (; chunk < chunk_end; ++chunk) {
-    CNW_ST();  // chunk top
-    if (g.nbuf == 1) {
-      __syncthreads();
-      stage(chunk, 0);
-    }
-    __syncthreads();
-    CNW_ST();  // after barrier
-    if (g.nbuf == 2 && chunk + 1 < chunk_end) stage(chunk + 1, cur ^ 1);
-    CNW_ST();  // after DMA issue
-    const float* s_lds = smem + cur * g.buf_stride;
-    const float* b_lds = s_lds + g.b_lds_off;
-    const int gy0c = (chunk % g.chunks_per_img) * g.PR;
-    const int start = (gy0c * g.s + g.min_oy) * g.Wb + g.min_ox;
-    const int sh = start - ((start >> 2) << 2);
-    // One wave per SIMD issues everything in order, so instructions-per-MFMA bounds this loop: the pixel pairs
-    // of a row are walked in unrolled groups whose LDS offsets are compile-time immediates (stride S_), bases are
-    // bumped once per group, and the column masks are applied only on the first / last pair of an image row.
-    {
-      // the pixel pairs of every row are split over the k-part waves
-      const int nq_row = g.Ws >> 1;
-      const int q_lo = (nq_row * kp) / kparts, q_hi = (nq_row * (kp + 1)) / kparts;
-      // pairs [0, mq_lo) and [mq_hi, nq_row) of a row can reach outside [0, Wb) for some tap -> masked steps
-      const int seg0 = min(max(g.mq_lo, q_lo), q_hi), seg1 = max(min(g.mq_hi, q_hi), seg0);
-      for (int r = 0; r < g.PR; ++r) {
-        const float* ap = s_lds + aoff + r * g.Ws;          // indexed by absolute column
-        const float* bp[T];
-#pragma unroll
-        for (int j = 0; j < T; ++j) bp[j] = b_lds + boff[j] + sh + (r * S_) * g.Wb;
-        int q = q_lo;
-        // masked and left-over single pairs: all T + 1 operands are read before the first MFMA (read / wait / MFMA per
-        // tap exposed one LDS round trip in front of every MFMA of the pair)
-        for (; q < seg0; ++q) {  // leading masked pairs
-          const float av = ap[2 * q];
-          const int cs = 2 * q * S_;
-          float bv[T];
-#pragma unroll
-          for (int j = 0; j < T; ++j) bv[j] = bp[j][cs];
-#pragma unroll
-          for (int j = 0; j < T; ++j) {
-            const float b_ = ((unsigned)(cs + ox[j]) < (unsigned)g.Wb) ? bv[j] : 0.f;
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b_, acc[j], 0, 0, 0);
-          }
-        }
-        // Interior pairs (no masks, immediate offsets), in groups of two k-steps with the operands double-buffered
-        // in registers: the LDS reads of the NEXT group are issued before the 2*T MFMAs of the current one. One wave
-        // per SIMD issues in order, so without this every group waited out the full LDS latency with the MFMA pipe
-        // idle (the compiler emitted read-all / s_waitcnt 0 / MFMA-all). (Folding the edge pairs into this pipeline
-        // as well was measured slower: 252 -> 273 us at 128->128, 100^2 -- the extra live operands cost more moves
-        // than the two exposed LDS round trips per row.)
-        CNW_ST();  // after leading masked pairs
-        if constexpr (T == 1) {
-          // one MFMA per k-step: the register pipeline below was measured slower (172 vs 161 us at 480->128, 100^2)
-          for (; q + WG_U <= seg1; q += WG_U) {
-            const float* apq = ap + 2 * q;
-#pragma unroll
-            for (int u = 0; u < WG_U; ++u)
-              acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(apq[2 * u], (bp[0] + 2 * q * S_)[2 * u * S_], acc[0], 0, 0, 0);
-          }
-        } else {
-          constexpr int GS = 2;  // k-steps per group
-          const int ng = (seg1 - q) / GS;
-          if (ng > 0) {
-            float a0[GS], a1[GS], b0[GS][T], b1[GS][T];
-#define WG_LOADG(qq_, a_, b_)                                                    \
-  {                                                                              \
-    const float* apq_ = ap + 2 * (qq_);                                          \
-    _Pragma("unroll") for (int u = 0; u < GS; ++u) a_[u] = apq_[2 * u];          \
-    _Pragma("unroll") for (int j = 0; j < T; ++j) {                              \
-      const float* bq_ = bp[j] + 2 * (qq_) * S_;                                 \
-      _Pragma("unroll") for (int u = 0; u < GS; ++u) b_[u][j] = bq_[2 * u * S_]; \
-    }                                                                            \
-  }
-#define WG_MFMAG(a_, b_)                                                                                   \
-  {                                                                                                        \
-    _Pragma("unroll") for (int u = 0; u < GS; ++u)                                                         \
-        _Pragma("unroll") for (int j = 0; j < T; ++j)                                                      \
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_[u], b_[u][j], acc[j], 0, 0, 0);               \
-  }
-            WG_LOADG(q, a0, b0);
-            int i = 0;
-            for (; i + 2 <= ng; i += 2) {
-              WG_LOADG(q + GS * (i + 1), a1, b1);
-              WG_MFMAG(a0, b0);
-              if (i + 2 < ng) WG_LOADG(q + GS * (i + 2), a0, b0);
-              WG_MFMAG(a1, b1);
-            }
-            if (i < ng) WG_MFMAG(a0, b0);
-#undef WG_LOADG
-#undef WG_MFMAG
-            q += GS * ng;
-          }
-        }
-        CNW_ST();  // after pipelined groups
-        for (; q < seg1; ++q) {
-          const float av = ap[2 * q];
-          float bv[T];
-#pragma unroll
-          for (int j = 0; j < T; ++j) bv[j] = bp[j][2 * q * S_];
-#pragma unroll
-          for (int j = 0; j < T; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv[j], acc[j], 0, 0, 0);
-        }
-        for (; q < q_hi; ++q) {  // trailing masked pairs
-          const float av = ap[2 * q];
-          const int cs = 2 * q * S_;
-          float bv[T];
-#pragma unroll
-          for (int j = 0; j < T; ++j) bv[j] = bp[j][cs];
-#pragma unroll
-          for (int j = 0; j < T; ++j) {
-            const float b_ = ((unsigned)(cs + ox[j]) < (unsigned)g.Wb) ? bv[j] : 0.f;
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b_, acc[j], 0, 0, 0);
-          }
-        }
-      }
-    }
-    CNW_ST();  // chunk end
-    if (g.nbuf == 2) cur ^= 1;
-  }
-  CNW_ST();
-
-  // the k-part waves of a block hold partial sums of the SAME dW tile: add them up through LDS (free after the
-  // main loop) so the block writes its tile once
-  if (kparts > 1) {
-    __syncthreads();
-    float* red = smem;
-    if (kp > 0) {
-      float* rp = red + (long)((kp - 1) * g.a_tiles + at) * (T * 16 * 64) + lane;
-#pragma unroll
-      for (int j = 0; j < T; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) rp[(j * 16 + r) * 64] = acc[j][r];
-    }
-    __syncthreads();
-    if (kp > 0) return;
-    for (int k = 1; k < kparts; ++k) {
-      const float* rp = red + (long)((k - 1) * g.a_tiles + at) * (T * 16 * 64) + lane;
-#pragma unroll
-      for (int j = 0; j < T; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][r] += rp[(j * 16 + r) * 64];
-    }
-  }
-  // many splits on a small dW: same-address float atomics serialise (~200 ns each), so each split stores its
-  // partial into a private workspace slice instead and cn_wgrad_reduce_kernel sums the slices
-  float* dWs = dW + (long)bz * g.slice_stride;
-#pragma unroll
-  for (int j = 0; j < T; ++j) {
-    const int n = j * 32 + l31;
-    const int bl = n / T;
-    const bool bok = (b0 + bl) < g.Bc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int a = a0 + at * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-      if (bok && a < g.A) {
-        if (g.slice_stride != 0) dWs[(long)a * g.sa + (long)b0 * T + n] = acc[j][r];
-        else atomicAdd(dW + (long)a * g.sa + (long)b0 * T + n, acc[j][r]);
-      }
-    }
-  }
+  static_assert(T == 1, "3 x 3 kernels run on cn_wgrad_vec3_kernel");
+  constexpr int KR = 1;
+#include "cn_wgrad_vec_body.h"
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// 3 x 3 weight gradient, TWELVE waves per block (round 5): the same tile, LDS images and LDS-DMA staging as
-// cn_wgrad_vec_kernel<9, S_>, but a wave owns ONE KERNEL ROW of the taps -- 32 couts x (32 channels x 3 taps) = three
-// accumulator tiles, 48 registers instead of 144 -- so three waves share a SIMD (wave = cout tile x kernel row x k-part).
-// cn_wgrad_vec_kernel<9, *> runs one wave per SIMD (393 registers) and issues everything in order: while it issues a
-// chunk's ~17 LDS-DMA instructions (~126 cycles each at the CU's issue rate), waits at the chunk barrier or for the first
-// operands, the matrix pipe idles -- 14.4k of a chunk's ~20k cycles are MFMAs (0.58 of the f32 peak alone, four rounds
-// running). Here a wave's DMA issue, barrier skew and LDS latency run under the other two waves' MFMAs.
-// Columns of a wave's tile: n = j * 32 + lane % 32 (j < 3), channel n / 3, tap ky * 3 + n % 3 -- dW runs of three floats.
-#define WG3_WAVES 12
-#define WG3_KS 3   // DMA instructions per wave for the S image  (arows * npix <= 8192 floats = 32 KiB = 32 instructions)
-#define WG3_KB 6   // DMA instructions per wave for the Bg image (32 * plane_b <= 16384 floats = 64 instructions)
+// 3 x 3: TWELVE waves (cout tile x kernel row x k-part), 32 couts x (32 channels x 3 taps) = three accumulator tiles per
+// wave, 48 of its 167 registers -- so three waves share a SIMD (168 registers is the limit for three), and a wave's
+// LDS-DMA issue (a chunk's ~17 instructions at ~126 cycles each, the CU's issue rate), its wait at the chunk barrier
+// and its LDS latency run under the other two waves' MFMAs. (With all nine taps in one wave -- 144 accumulator
+// registers, one wave per SIMD, everything issued in order -- the matrix pipe idled through all three: 14.4k of a
+// chunk's ~20k cycles were MFMAs, 0.58 of the f32 peak.)
 template <int S_>
-__global__ __launch_bounds__(WG3_WAVES * 64) void cn_wgrad_vec3_kernel(const float* __restrict__ S0,
-                                                                       const float* __restrict__ Bg0,
-                                                                       float* __restrict__ dW0, const CnWgradGeom g) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr int T = 3;  // taps per wave
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int half = lane >> 5, l31 = lane & 31;
-  // wave = (k-part, kernel row, cout tile): the waves of one (cout tile, kernel row) are a_tiles * 3 apart
-  const int at = wid % g.a_tiles;
-  const int ky = (wid / g.a_tiles) % 3;
-  const int kp = wid / (g.a_tiles * 3), kparts = WG3_WAVES / (g.a_tiles * 3);
-  int bx, by, bz;
-  if (!cn_xcd_block(g.grid_x, g.grid_y, g.grid_x * g.grid_y * g.grid_z, bx, by, bz)) return;
-  const int grp = g.G > 1 ? bz / g.spg : 0;
-  const int split = bz - grp * g.spg;
-  const float* __restrict__ S = g.G > 1 ? g.gS[grp] : S0;
-  const float* __restrict__ Bg = g.G > 1 ? g.gB[grp] : Bg0;
-  float* __restrict__ dW = (g.G > 1 && g.slice_stride == 0) ? g.gdW[grp] : dW0;
-  const int a0 = by * g.a_tiles * 32;
-  const int b0 = bx * WG_BC;
-  const int npix = g.PR * g.Ws;
-  const int n4s = npix >> 2;
-  const int n4b = g.plane_b >> 2;
-  const float* zero = cn_zero_line16 + 4 * lane;
-
-  int boff[T], ox[T];
-#pragma unroll
-  for (int j = 0; j < T; ++j) {
-    const int n = j * 32 + l31;
-    const int bl = n / 3, t = ky * 3 + (n - bl * 3);
-    boff[j] = bl * g.plane_b + (g.offy[t] - g.min_oy) * g.Wb + (g.offx[t] - g.min_ox) + half * g.s;
-    ox[j] = g.offx[t] + half * g.s;
-  }
-  const int aoff = (at * 32 + l31) * g.pitch_s + half;
-
-  f32x16 acc[T];
-#pragma unroll
-  for (int j = 0; j < T; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-
-  const int arows = g.a_tiles * 32;
-  int chunk = split * g.chunks_per_split;
-  int chunk_end = chunk + g.chunks_per_split;
-  if (chunk_end > g.total_chunks) chunk_end = g.total_chunks;
-
-  constexpr unsigned WG_IDLE = 0xFFFFFFFFu;
-  unsigned so[WG3_KS], bo[WG3_KB];
-  {
-    const int nsp = arows * n4s, nbp = WG_BC * n4b;
-#pragma unroll
-    for (int k = 0; k < WG3_KS; ++k) {
-      const int p = (wid + WG3_WAVES * k) * 64 + lane;
-      const int a = p / n4s, pc = p - a * n4s;
-      so[k] = (p < nsp && (a0 + a) < g.A) ? (unsigned)(((long)(a0 + a) * g.scs + 4 * pc) * 4) : WG_IDLE;
-    }
-#pragma unroll
-    for (int k = 0; k < WG3_KB; ++k) {
-      const int p = (wid + WG3_WAVES * k) * 64 + lane;
-      const int bl = p / n4b, pi = p - bl * n4b;
-      bo[k] = (p < nbp && (b0 + bl) < g.Bc) ? (unsigned)(((long)(b0 + bl) * g.bcs + 4 * pi) * 4) : WG_IDLE;
-    }
-  }
-  auto stage = [&](int ck, int buf) {
-    float* s_lds = smem + buf * g.buf_stride;
-    float* b_lds = s_lds + g.b_lds_off;
-    const int n = ck / g.chunks_per_img;
-    const int gy0 = (ck - n * g.chunks_per_img) * g.PR;
-    const int nsp = arows * n4s, nbp = WG_BC * n4b;
-    {
-      const int fs0 = gy0 * g.Ws;
-      const char* sbase = reinterpret_cast<const char*>(S + (long)n * g.sbs + fs0);
-      const bool inside = fs0 + npix <= (int)g.scs;  // wave-uniform: the whole chunk lies inside the plane
-#pragma unroll
-      for (int k = 0; k < WG3_KS; ++k) {
-        if ((wid + WG3_WAVES * k) * 64 < nsp && so[k] != WG_IDLE) {
-          const float* src = reinterpret_cast<const float*>(sbase + so[k]);
-          if (!inside) {
-            const int p = (wid + WG3_WAVES * k) * 64 + lane;
-            if (!((fs0 + 4 * (p % n4s) + 3) < (int)g.scs)) src = zero;
-          }
-          cn_glds16(src, s_lds + (wid + WG3_WAVES * k) * 256);
-        }
-      }
-    }
-    {
-      const int start = (gy0 * g.s + g.min_oy) * g.Wb + g.min_ox;
-      const int f0 = (start >> 2) << 2;
-      const char* bbase = reinterpret_cast<const char*>(Bg + (long)n * g.bbs + f0);
-      const bool inside = f0 >= 0 && f0 + g.plane_b <= (int)g.bcs;  // wave-uniform: the halo lies inside the plane
-#pragma unroll
-      for (int k = 0; k < WG3_KB; ++k) {
-        if ((wid + WG3_WAVES * k) * 64 < nbp && bo[k] != WG_IDLE) {
-          const float* src = reinterpret_cast<const float*>(bbase + bo[k]);
-          if (!inside) {
-            const int p = (wid + WG3_WAVES * k) * 64 + lane;
-            const int fq = f0 + 4 * (p % n4b);
-            if (!(fq >= 0 && (fq + 3) < (int)g.bcs)) src = zero;
-          }
-          cn_glds16(src, b_lds + (wid + WG3_WAVES * k) * 256);
-        }
-      }
-    }
-  };
-
-  int cur = 0;
-  if (chunk < chunk_end && g.nbuf == 2) stage(chunk, 0);
-  for (; chunk < chunk_end; ++chunk) {
-    if (g.nbuf == 1) {
-      __syncthreads();
-      stage(chunk, 0);
-    }
-    __syncthreads();
-    // (The barrier puts the three waves of a SIMD in the same phase. Skewing them -- the waves of kernel row ky start
-    // ky * 512 / 1024 / 2048 / 4096 cycles late -- was measured: 239 -> 245 / 245 / 249 / 260 us at 128 -> 128, 8 x 100^2;
-    // moving a wave's DMA issue into its group pipeline costs registers the three-waves budget does not have.)
-    // (Round 5, measured with tools/wgrad_bench.py at 8 x 100^2, same box: (a) the next chunk's nine DMA instructions
-    // spread through this chunk's MFMA loop, three per iteration, 168 registers without scratch once the source pointers
-    // were kept from being hoisted: 128 -> 128 240 -> 280 us, 160 -> 128 270-292 -> 346 us -- a DMA issue inside the
-    // loop stalls the wave's in-order MFMA stream; (b) progress-based issue priority, s_setprio 3..0 by quarter of the
-    // row so that the wave that is behind is served first: the three waves of a SIMD then finish their row together and
-    // the chunk takes exactly as long: 243.0 -> 242.2 us, 160 -> 128 268.5 -> 297.4 us. Neither kept. Under this kernel the
-    // shader clock reads ~1.97 GHz (s_memtime against the event time of the launch), not 2.4: its 0.62 of the nominal
-    // f32 peak is ~0.75 of what the matrix pipes can deliver at that clock.)
-    if (g.nbuf == 2 && chunk + 1 < chunk_end) stage(chunk + 1, cur ^ 1);
-    const float* s_lds = smem + cur * g.buf_stride;
-    const float* b_lds = s_lds + g.b_lds_off;
-    const int gy0c = (chunk % g.chunks_per_img) * g.PR;
-    const int start = (gy0c * g.s + g.min_oy) * g.Wb + g.min_ox;
-    const int sh = start - ((start >> 2) << 2);
-    const int nq_row = g.Ws >> 1;
-    const int q_lo = (nq_row * kp) / kparts, q_hi = (nq_row * (kp + 1)) / kparts;
-    const int seg0 = min(max(g.mq_lo, q_lo), q_hi), seg1 = max(min(g.mq_hi, q_hi), seg0);
-    for (int r = 0; r < g.PR; ++r) {
-      const float* ap = s_lds + aoff + r * g.Ws;
-      const float* bp[T];
-#pragma unroll
-      for (int j = 0; j < T; ++j) bp[j] = b_lds + boff[j] + sh + (r * S_) * g.Wb;
-      int q = q_lo;
-      for (; q < seg0; ++q) {  // leading masked pairs
-        const float av = ap[2 * q];
-        const int cs = 2 * q * S_;
-        float bv[T];
-#pragma unroll
-        for (int j = 0; j < T; ++j) bv[j] = bp[j][cs];
-#pragma unroll
-        for (int j = 0; j < T; ++j) {
-          const float b_ = ((unsigned)(cs + ox[j]) < (unsigned)g.Wb) ? bv[j] : 0.f;
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b_, acc[j], 0, 0, 0);
-        }
-      }
-      {  // interior pairs: groups of GS k-steps with the operands double-buffered in registers.
-         // (A conflict-free A operand -- one ds_read_b128 per lane for four k-steps + two v_permlane32_swap, instead of
-         // four dwords at a row pitch that puts 32 couts on 8 banks -- was built and measured: 239 -> 251 us at 128 -> 128,
-         // 855 -> 899 at 480 -> 128, step 388 -> 383 chips/s: the bank conflicts are not what idles the pipe. Note for the
-         // next attempt: __builtin_bit_cast(unsigned, v[i]) of an ext_vector ELEMENT expression yields element 0 / undef
-         // with this compiler; copy the element to a scalar first.)
-        constexpr int GS = 3;
-        const int ng = (seg1 - q) / GS;
-        if (ng > 0) {
-          float a0[GS], a1[GS], b0[GS][T], b1[GS][T];
-#define WG3_LOADG(qq_, a_, b_)                                                   \
-  {                                                                              \
-    const float* apq_ = ap + 2 * (qq_);                                          \
-    _Pragma("unroll") for (int u = 0; u < GS; ++u) a_[u] = apq_[2 * u];          \
-    _Pragma("unroll") for (int j = 0; j < T; ++j) {                              \
-      const float* bq_ = bp[j] + 2 * (qq_) * S_;                                 \
-      _Pragma("unroll") for (int u = 0; u < GS; ++u) b_[u][j] = bq_[2 * u * S_]; \
-    }                                                                            \
-  }
-#define WG3_MFMAG(a_, b_)                                                                                  \
-  {                                                                                                        \
-    _Pragma("unroll") for (int u = 0; u < GS; ++u)                                                         \
-        _Pragma("unroll") for (int j = 0; j < T; ++j)                                                      \
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_[u], b_[u][j], acc[j], 0, 0, 0);               \
-  }
-          WG3_LOADG(q, a0, b0);
-          int i = 0;
-          for (; i + 2 <= ng; i += 2) {
-            WG3_LOADG(q + GS * (i + 1), a1, b1);
-            WG3_MFMAG(a0, b0);
-            if (i + 2 < ng) WG3_LOADG(q + GS * (i + 2), a0, b0);
-            WG3_MFMAG(a1, b1);
-          }
-          if (i < ng) WG3_MFMAG(a0, b0);
-#undef WG3_LOADG
-#undef WG3_MFMAG
-          q += GS * ng;
-        }
-      }
-      for (; q < seg1; ++q) {
-        const float av = ap[2 * q];
-        float bv[T];
-#pragma unroll
-        for (int j = 0; j < T; ++j) bv[j] = bp[j][2 * q * S_];
-#pragma unroll
-        for (int j = 0; j < T; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv[j], acc[j], 0, 0, 0);
-      }
-      for (; q < q_hi; ++q) {  // trailing masked pairs
-        const float av = ap[2 * q];
-        const int cs = 2 * q * S_;
-        float bv[T];
-#pragma unroll
-        for (int j = 0; j < T; ++j) bv[j] = bp[j][cs];
-#pragma unroll
-        for (int j = 0; j < T; ++j) {
-          const float b_ = ((unsigned)(cs + ox[j]) < (unsigned)g.Wb) ? bv[j] : 0.f;
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b_, acc[j], 0, 0, 0);
-        }
-      }
-    }
-    if (g.nbuf == 2) cur ^= 1;
-  }
-
-  // the k-part waves of a (cout tile, kernel row) hold partial sums of the SAME dW tile: add them up through LDS
-  if (kparts > 1) {
-    __syncthreads();
-    float* red = smem;
-    const int slot = ky * g.a_tiles + at;  // (cout tile, kernel row) within the block
-    if (kp > 0) {
-      float* rp = red + (long)((kp - 1) * g.a_tiles * 3 + slot) * (T * 16 * 64) + lane;
-#pragma unroll
-      for (int j = 0; j < T; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) rp[(j * 16 + r) * 64] = acc[j][r];
-    }
-    __syncthreads();
-    if (kp > 0) return;
-    for (int k = 1; k < kparts; ++k) {
-      const float* rp = red + (long)((k - 1) * g.a_tiles * 3 + slot) * (T * 16 * 64) + lane;
-#pragma unroll
-      for (int j = 0; j < T; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][r] += rp[(j * 16 + r) * 64];
-    }
-  }
-  float* dWs = dW + (long)bz * g.slice_stride;
-#pragma unroll
-  for (int j = 0; j < T; ++j) {
-    const int n = j * 32 + l31;
-    const int bl = n / 3, t = ky * 3 + (n - bl * 3);
-    const bool bok = (b0 + bl) < g.Bc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int a = a0 + at * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-      if (bok && a < g.A) {
-        float* d = (g.slice_stride != 0 ? dWs : dW) + (long)a * g.sa + (long)(b0 + bl) * 9 + t;
-        if (g.slice_stride != 0) *d = acc[j][r];
-        else atomicAdd(d, acc[j][r]);
-      }
-    }
-  }
+__global__ __launch_bounds__(768) void cn_wgrad_vec3_kernel(const float* __restrict__ S0, const float* __restrict__ Bg0,
+                                                           float* __restrict__ dW0, const CnWgradGeom g) {
+  constexpr int KR = 3;
+#include "cn_wgrad_vec_body.h"
 }
 
 // dW_g[i] += sum_s part[g * nslices + s][i]; grid = (ceil(n / 256), 1 or 16, groups): with 16 slice groups,
@@ -844,7 +294,7 @@ static int cn_wgrad_launch_vec(const float* S, const float* Bg, float* dW, CnWgr
   g.pitch_b = g.Wb;
   // last read: (rows_b-1)*Wb + (Ws-1)*s + (max_ox-min_ox) + sh(<=3)
   g.plane_b = ((g.rows_b - 1) * g.Wb + (g.Ws - 1) * g.s + (max_ox - g.min_ox) + 4 + 3) / 4 * 4;
-  if (WG_BC * g.plane_b > WG_KB * 4 * 256) return CN_ERR_ARG;
+  if (WG_BC * g.plane_b > WG_DB * 256) return CN_ERR_ARG;
   g.pitch_s = g.PR * g.Ws;  // dense image (DMA pieces run across rows)
   g.a_tiles = g.A > 32 ? 2 : 1;
   size_t lds;
@@ -852,10 +302,10 @@ static int cn_wgrad_launch_vec(const float* S, const float* Bg, float* dW, CnWgr
     g.b_lds_off = (g.a_tiles * 32 * g.pitch_s + 255) / 256 * 256;  // whole DMA instructions
     g.buf_stride = g.b_lds_off + (WG_BC * g.plane_b + 255) / 256 * 256;
     lds = (size_t)g.buf_stride * sizeof(float);
-    if ((lds <= 160 * 1024 && g.a_tiles * 32 * g.pitch_s <= WG_KS * 4 * 256) || g.a_tiles == 1) break;
+    if ((lds <= 160 * 1024 && g.a_tiles * 32 * g.pitch_s <= WG_DS * 256) || g.a_tiles == 1) break;
     g.a_tiles >>= 1;
   }
-  if (lds > 160 * 1024 || g.a_tiles * 32 * g.pitch_s > WG_KS * 4 * 256) return CN_ERR_ARG;
+  if (lds > 160 * 1024 || g.a_tiles * 32 * g.pitch_s > WG_DS * 256) return CN_ERR_ARG;
   g.nbuf = (2 * lds <= 160 * 1024) ? 2 : 1;
   lds *= g.nbuf;
   {  // room for the in-block reduction over the k-part waves: [kparts-1][a_tiles][T*16][64] floats
@@ -885,15 +335,17 @@ static int cn_wgrad_launch_vec(const float* S, const float* Bg, float* dW, CnWgr
   if (splits < 1) splits = 1;
   g.chunks_per_split = (g.total_chunks + splits - 1) / splits;
   splits = (g.total_chunks + g.chunks_per_split - 1) / g.chunks_per_split;
+  if (g.s != 1 && g.s != 2) return CN_ERR_ARG;
+  // the instantiations of this T by stride. 3 x 3: twelve waves per block; 1 x 1: four
+  using Kern = void (*)(const float*, const float*, float*, CnWgradGeom);
+  static const Kern kern[2] = {T == 9 ? cn_wgrad_vec3_kernel<1> : cn_wgrad_vec_kernel<1, 1>,
+                               T == 9 ? cn_wgrad_vec3_kernel<2> : cn_wgrad_vec_kernel<1, 2>};
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)cn_wgrad_vec_kernel<T, 1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-    (void)hipFuncSetAttribute((const void*)cn_wgrad_vec_kernel<T, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
+    for (const Kern k : kern)
+      (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_set = true;
   }
-  if (g.s != 1 && g.s != 2) return CN_ERR_ARG;
   {
     // pair q covers columns 2q, 2q+1: masked iff 2q*s + min_ox < 0 or (2q+1)*s + max_ox >= Wb
     const int nq_row = g.Ws / 2;
@@ -907,7 +359,8 @@ static int cn_wgrad_launch_vec(const float* S, const float* Bg, float* dW, CnWgr
     g.mq_lo = lo;
     g.mq_hi = hi;
   }
-  cn_prof_name("cn_wgrad_vec_kernel<%d, %d>", T, g.s == 1 ? 1 : 2);
+  if (T == 9) cn_prof_name("cn_wgrad_vec3_kernel<%d>", g.s);
+  else cn_prof_name("cn_wgrad_vec_kernel<1, %d>", g.s);
   g.spg = splits;
   g.grid_x = gx; g.grid_y = gy; g.grid_z = splits * g.G;
   const dim3 grid(cn_xcd_grid((long)gx * gy * splits * g.G));
@@ -921,26 +374,11 @@ static int cn_wgrad_launch_vec(const float* S, const float* Bg, float* dW, CnWgr
     g.slice_stride = dw_floats;
     out = ws;
   }
-  if (T == 9) cn_prof_name("cn_wgrad_vec3_kernel<%d>", g.s == 1 ? 1 : 2);
   cn_prof_desc("wgrad_vec<%d> G%d N%d A%d %dx%d Bc%d %dx%d s%d grid%dx%dx%d nbuf%d sl%d", T, g.G, g.N, g.A, g.Hs, g.Ws,
                g.Bc, g.Hb, g.Wb, g.s, gx, gy, splits, g.nbuf, g.slice_stride != 0 ? 1 : 0);
   cn_prof_bytes(4.0 * g.G * ((double)g.N * g.A * g.Hs * g.Ws + (double)g.N * g.Bc * g.Hb * g.Wb + (double)dw_floats));
   cn_prof_before(stream);
-  if (T == 9) {  // 3 x 3: twelve waves per block, one kernel row of taps per wave (cn_wgrad_vec3_kernel)
-    static bool attr3 = false;
-    if (!attr3) {
-      (void)hipFuncSetAttribute((const void*)cn_wgrad_vec3_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute((const void*)cn_wgrad_vec3_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr3 = true;
-    }
-    if (g.s == 1)
-      CN_LAUNCH((cn_wgrad_vec3_kernel<1>), grid, dim3(WG3_WAVES * 64), lds, stream, g.gS[0], g.gB[0], out, g);
-    else
-      CN_LAUNCH((cn_wgrad_vec3_kernel<2>), grid, dim3(WG3_WAVES * 64), lds, stream, g.gS[0], g.gB[0], out, g);
-  } else if (g.s == 1)
-    CN_LAUNCH((cn_wgrad_vec_kernel<T, 1>), grid, dim3(256), lds, stream, g.gS[0], g.gB[0], out, g);
-  else
-    CN_LAUNCH((cn_wgrad_vec_kernel<T, 2>), grid, dim3(256), lds, stream, g.gS[0], g.gB[0], out, g);
+  CN_LAUNCH(kern[g.s - 1], grid, dim3(T == 9 ? 768 : 256), lds, stream, g.gS[0], g.gB[0], out, g);
   cn_prof_after(stream, T == 9 ? 2 : 3, g.flops * g.G);  // the contraction kernel alone
   if (g.slice_stride != 0) {
     // deferred: a sink on this thread takes the G sums (one record per group) and runs them later in one batched launch

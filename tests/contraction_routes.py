@@ -163,31 +163,21 @@ COMPILED = [
     'cn_pretime_kernel<2, 8, 2, 1, 0, 0>',
     'cn_pretime_kernel<3, 4, 1, 1, 0, 0>',
     'cn_pretime_kernel<3, 4, 1, 1, 3, 12>',
-    'cn_pretime_kernel<3, 4, 2, 1, 0, 0>',
     'cn_pretime_kernel<3, 8, 1, 1, 0, 0>',
-    'cn_pretime_kernel<3, 8, 2, 1, 0, 0>',
     'cn_pretime_kernel<4, 4, 1, 1, 0, 0>',
     'cn_pretime_kernel<4, 4, 1, 1, 3, 12>',
     'cn_pretime_kernel<4, 4, 1, 2, 0, 0>',
-    'cn_pretime_kernel<4, 4, 1, 3, 0, 0>',
-    'cn_pretime_kernel<4, 4, 2, 1, 0, 0>',
     'cn_pretime_kernel<4, 8, 1, 1, 0, 0>',
     'cn_pretime_kernel<4, 8, 1, 2, 0, 0>',
-    'cn_pretime_kernel<4, 8, 1, 3, 0, 0>',
-    'cn_pretime_kernel<4, 8, 2, 1, 0, 0>',
     'cn_pretime_kernel<5, 4, 1, 1, 0, 0>',
     'cn_pretime_kernel<5, 4, 1, 1, 3, 12>',
-    'cn_pretime_kernel<5, 4, 2, 1, 0, 0>',
     'cn_pretime_kernel<5, 8, 1, 1, 0, 0>',
-    'cn_pretime_kernel<5, 8, 2, 1, 0, 0>',
     'cn_wgrad_kernel<1>',
     'cn_wgrad_kernel<9>',
     'cn_wgrad_vec3_kernel<1>',
     'cn_wgrad_vec3_kernel<2>',
     'cn_wgrad_vec_kernel<1, 1>',
     'cn_wgrad_vec_kernel<1, 2>',
-    'cn_wgrad_vec_kernel<9, 1>',
-    'cn_wgrad_vec_kernel<9, 2>',
 ]
 
 CASES = {
@@ -1073,6 +1063,12 @@ CASES = {
     'test_conv_exact_gpu.py::test_conv2d_f32_weight_gradient_routes[full-case6]': {
         'dw': [('cn_wgrad_vec_kernel<1, 2>', 'G1', 's2', 'nbuf1', 'split', 'atomics', 'ws full')],
     },
+    'test_conv_exact_gpu.py::test_conv2d_f32_weight_gradient_routes[full-case7]': {
+        'dw': [('cn_wgrad_vec_kernel<1, 1>', 'G1', 's1', 'nbuf2', 'split', 'atomics', 'ws full')],
+    },
+    'test_conv_exact_gpu.py::test_conv2d_f32_weight_gradient_routes[full-case8]': {
+        'dw': [('cn_wgrad_vec_kernel<1, 1>', 'G1', 's1', 'nbuf2', 'whole', 'atomics', 'ws full')],
+    },
     'test_conv_exact_gpu.py::test_conv2d_f32_weight_gradient_routes[none-case0]': {
         'dw': [('cn_wgrad_vec3_kernel<1>', 'G1', 's1', 'nbuf2', 'split', 'atomics', 'ws none')],
     },
@@ -1093,6 +1089,12 @@ CASES = {
     },
     'test_conv_exact_gpu.py::test_conv2d_f32_weight_gradient_routes[none-case6]': {
         'dw': [('cn_wgrad_vec_kernel<1, 2>', 'G1', 's2', 'nbuf1', 'split', 'atomics', 'ws none')],
+    },
+    'test_conv_exact_gpu.py::test_conv2d_f32_weight_gradient_routes[none-case7]': {
+        'dw': [('cn_wgrad_vec_kernel<1, 1>', 'G1', 's1', 'nbuf2', 'split', 'atomics', 'ws none')],
+    },
+    'test_conv_exact_gpu.py::test_conv2d_f32_weight_gradient_routes[none-case8]': {
+        'dw': [('cn_wgrad_vec_kernel<1, 1>', 'G1', 's1', 'nbuf2', 'whole', 'atomics', 'ws none')],
     },
     'test_conv_exact_gpu.py::test_conv2d_f32_weight_gradient_padded_batch_stride': {
         'ws full: dw': [
@@ -2994,25 +2996,4 @@ PRODUCTION = {
     },
 }
 
-UNREACHABLE = {
-    'cn_wgrad_vec_kernel<9, 1>':
-        'cn_wgrad.hip, cn_wgrad_launch_vec: `if (T == 9) {  // 3 x 3: twelve waves per block, one kernel row of taps per wave (cn_wgrad_vec3_kernel)` -- every 3x3 launch of the 16-byte variant goes to cn_wgrad_vec3_kernel<S>; cn_wgrad_vec_kernel<T, S> is launched in the else branches, that is for T == 1 only (the entry refuses other T)',
-    'cn_wgrad_vec_kernel<9, 2>':
-        'cn_wgrad.hip, cn_wgrad_launch_vec: `if (T == 9) {  // 3 x 3: twelve waves per block, one kernel row of taps per wave (cn_wgrad_vec3_kernel)` -- as for <9, 1>, at stride 2',
-    'cn_pretime_kernel<3, 4, 2, 1, 0, 0>':
-        'cn_pretime.hip, cn_pretime_workspace_floats: `if (with_backward && (pt_ne(C, T) > 3 || Cout > 32)) return -1;` -- MT = 2 is Cout > 32, and passes 3 to 5 are launched by cn_pretime_bwd_f32 alone, whose pt_fill refuses every shape this query refuses (need < 0)',
-    'cn_pretime_kernel<3, 8, 2, 1, 0, 0>':
-        'cn_pretime.hip, cn_pretime_workspace_floats: `if (with_backward && (pt_ne(C, T) > 3 || Cout > 32)) return -1;` -- MT = 2 is Cout > 32, and passes 3 to 5 are launched by cn_pretime_bwd_f32 alone, whose pt_fill refuses every shape this query refuses (need < 0)',
-    'cn_pretime_kernel<4, 4, 2, 1, 0, 0>':
-        'cn_pretime.hip, cn_pretime_workspace_floats: `if (with_backward && (pt_ne(C, T) > 3 || Cout > 32)) return -1;` -- MT = 2 is Cout > 32, and passes 3 to 5 are launched by cn_pretime_bwd_f32 alone, whose pt_fill refuses every shape this query refuses (need < 0)',
-    'cn_pretime_kernel<4, 8, 2, 1, 0, 0>':
-        'cn_pretime.hip, cn_pretime_workspace_floats: `if (with_backward && (pt_ne(C, T) > 3 || Cout > 32)) return -1;` -- MT = 2 is Cout > 32, and passes 3 to 5 are launched by cn_pretime_bwd_f32 alone, whose pt_fill refuses every shape this query refuses (need < 0)',
-    'cn_pretime_kernel<5, 4, 2, 1, 0, 0>':
-        'cn_pretime.hip, cn_pretime_workspace_floats: `if (with_backward && (pt_ne(C, T) > 3 || Cout > 32)) return -1;` -- MT = 2 is Cout > 32, and passes 3 to 5 are launched by cn_pretime_bwd_f32 alone, whose pt_fill refuses every shape this query refuses (need < 0)',
-    'cn_pretime_kernel<5, 8, 2, 1, 0, 0>':
-        'cn_pretime.hip, cn_pretime_workspace_floats: `if (with_backward && (pt_ne(C, T) > 3 || Cout > 32)) return -1;` -- MT = 2 is Cout > 32, and passes 3 to 5 are launched by cn_pretime_bwd_f32 alone, whose pt_fill refuses every shape this query refuses (need < 0)',
-    'cn_pretime_kernel<4, 4, 1, 3, 0, 0>':
-        'cn_pretime.hip, cn_pretime_workspace_floats: `if (pt_shmem(ps, C, T, Cout) > 160 * 1024) return -1;` -- NE = 3 is 65 <= C (T - 2) <= 96, where the LDS image of pass 4 is beyond 160 KiB at every cube (test_ne3_gradient_pass_has_no_servable_shape asserts the refusal for all of them)',
-    'cn_pretime_kernel<4, 8, 1, 3, 0, 0>':
-        'cn_pretime.hip, cn_pretime_workspace_floats: `if (pt_shmem(ps, C, T, Cout) > 160 * 1024) return -1;` -- NE = 3 is 65 <= C (T - 2) <= 96, where the LDS image of pass 4 is beyond 160 KiB at every cube (test_ne3_gradient_pass_has_no_servable_shape asserts the refusal for all of them)',
-}
+UNREACHABLE = {}

@@ -190,6 +190,11 @@ def test_conv2d_f32_exact_production_100(case, request, tmp_path):
     (2, 40, 25, 25, 128, 1, 1, 0, 1, False),   # 1x1, odd plane
     (2, 32, 26, 26, 48, 3, 2, 1, 1, False),    # stride 2
     (2, 32, 28, 28, 48, 1, 2, 0, 1, False),    # 1x1, stride 2: cn_wgrad_vec_kernel<1, 2> (route ledger)
+    # the staging branches of cn_wgrad_vec_kernel<1, 1>. PR = 10 on 14 rows: the second chunk of an image runs past the
+    # plane, both operands zero-fill per 16-byte piece; a ragged second cout tile and Cin < 32: idle DMA lanes; two k-parts
+    (2, 24, 14, 12, 40, 1, 1, 0, 1, False),
+    # one cout tile, four k-part waves on two pixel pairs per row: two waves own no pair and add zeros in the LDS reduction
+    (1, 8, 4, 4, 8, 1, 1, 0, 1, False),
 ])
 @pytest.mark.parametrize("ws", ["full", "none"])
 def test_conv2d_f32_weight_gradient_routes(case, ws, request, tmp_path):
