@@ -83,11 +83,15 @@ SIGNATURES = {
     "cn_pack_timeconv_f32": [P, P, I, I, I, I, I, P],
     "cn_fold_timeconv_grad_f32": [P, P, I, I, I, I, P],
     "cn_prepare_chips_f32": [P, I, P, P, P, I, I, L, F, F, F, P],
+    "cn_prepare_chips_log_f32": [P, I, P, P, P, I, I, L, F, F, F, F, F, P],
     "cn_predictions_to_u16": [P, P, P, P, I, I, I, I, I, I, I, F, P],
     "cn_augment_chips_f32": [P, I, P, I, P, I, P, P, P, P, P, P, P, P, I, I, I, I, I, F, F, F, P],
     "cn_label_parcels_i32": [P, I, L, P, P, I, I, I, P],  # crop_value: long long, as wide as long here
     "cn_augment_parcels_f32": [P, I, P, I, P, I, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, F, F, P],
     "cn_augment_series_f32": [P, I, P, I, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, P, P, I, I, I, I, I, F, F, F, P],
+    "cn_augment_chips_log_f32": [P, I, P, I, P, I, P, P, P, P, P, P, P, P, I, I, I, I, I, F, F, F, F, F, P],
+    "cn_augment_parcels_log_f32": [P, I, P, I, P, I, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, F, F, F, F, P],
+    "cn_augment_series_log_f32": [P, I, P, I, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, P, P, I, I, I, I, I, F, F, F, F, F, P],
     "cn_chip_hist_u32": [P, I, P, I, I, L, I, P],
     "cn_hist_batch_reduce": [P, P, P, P, I, I, I, I, P],
     "cn_label_counts_i64": [P, I, L, P, I, P],
@@ -145,6 +149,7 @@ SIGNATURES = {
     "cn_pretime_fwd_f32": [P, L, P, P, P, L, I, I, I, I, I, I, I, P, F, P, L, P],
     "cn_pretime_bwd_f32": [P, L, P, P, P, L, I, P, I, I, I, I, I, I, P, F, P, L, P],
     "cn_window_chips_f32": [P, I, P, P, I, I, I, I, I, I, I, P, P, F, F, F, P],
+    "cn_window_chips_log_f32": [P, I, P, P, I, I, I, I, I, I, I, P, P, F, F, F, F, F, P],
     "cn_stitch_predictions_u16": [P, P, P, P, P, I, I, I, I, I, I, F, P],
     "cn_profile_begin": [],
     "cn_profile_end": [P],

@@ -44,7 +44,7 @@ import torch
 from . import _lib
 from .curves import cubic_spline, pchip
 from .data import Data
-from .edges import _DTYPES, SCALE_FACTOR, prepare_chips
+from .edges import _DTYPES, LOG_FLOOR, LOG_GAIN, SCALE_FACTOR, prepare_chips
 from .engine import _stream
 
 OPS = ("none", "rot90", "rot180", "rot270", "fliplr", "flipud", "gaussian", "saltpepper", "cropresize", "perlin")
@@ -330,10 +330,12 @@ class DeviceAugmenter:
 
     def apply(self, batch: Data, mean: T.Optional[torch.Tensor] = None, std: T.Optional[torch.Tensor] = None,
               plan: T.Optional[AugmentPlan] = None, scale: float = 1.0 / SCALE_FACTOR, lo: float = 1e-9,
-              hi: float = 1.0) -> Data:
+              hi: float = 1.0, log_transform: bool = False) -> Data:
         """Raw device batch -> prepared Data (x fp32 z-scored, bdist fp32, y int64) with ``plan`` (default: a fresh
         ``draw``) applied, on the current stream. A batch without labels passes through the plain prologue: the
-        reference only augments labelled samples (datasets.py:448)."""
+        reference only augments labelled samples (datasets.py:448). ``log_transform``: the reference's
+        ``--log-transform`` (datasets.py:481-484) on x, after the augmentation's last clip and before the z-score, in the
+        same launches (the ``_log_f32`` entry points); bdist and y are not transformed, the draw is the same."""
         x = batch.x
         if not x.is_cuda:
             raise RuntimeError("DeviceAugmenter.apply needs a device batch")
@@ -343,7 +345,7 @@ class DeviceAugmenter:
         bd = kw.get("bdist")
         y = kw.get("y")
         if y is None:
-            kw["x"] = prepare_chips(x, mean, std, scale, lo, hi)
+            kw["x"] = prepare_chips(x, mean, std, scale, lo, hi, log_transform)
             if bd is not None and bd.dtype != torch.float32:
                 kw["bdist"] = prepare_chips(bd.reshape(bd.shape[0], 1, 1, *bd.shape[1:]), None, None, scale, lo,
                                             hi).reshape(bd.shape)
@@ -385,7 +387,8 @@ class DeviceAugmenter:
                 bd_out.data_ptr() if bd is not None else None, y_out.data_ptr(), table_h.data_ptr(),
                 table_d.data_ptr(), perlin_d.data_ptr() if perlin_d is not None else None)
         tail = (m.data_ptr() if m is not None else None, s.data_ptr() if s is not None else None, B, C, Tn, H, W,
-                float(scale), float(lo), float(hi), _stream())
+                float(scale), float(lo), float(hi)) + ((LOG_GAIN, LOG_FLOOR) if log_transform else ()) + (_stream(),)
+        entry = "cn_augment_{}_log_f32" if log_transform else "cn_augment_{}_f32"
         parcel_h = parcel_d = None
         has_parcel = plan.has_parcel
         if has_parcel:
@@ -402,15 +405,15 @@ class DeviceAugmenter:
             packed[size:].view(np.int32)[:] = rows
             series_d = series_h.to(dev, non_blocking=True)
             labels, _ = label_parcels(y, self.crop_value)
-            _lib.call("cn_augment_series_f32", *head, labels.data_ptr(),
+            _lib.call(entry.format("series"), *head, labels.data_ptr(),
                       parcel_h.data_ptr() if parcel_h is not None else None,
                       parcel_d.data_ptr() if parcel_d is not None else None, series_h.data_ptr(), series_d.data_ptr(),
                       series_h.data_ptr() + 4 * size, series_d.data_ptr() + 4 * size, len(rows), *tail)
         elif has_parcel:  # three launches: label, x, targets
             labels, _ = label_parcels(y, self.crop_value)
-            _lib.call("cn_augment_parcels_f32", *head, labels.data_ptr(), parcel_h.data_ptr(), parcel_d.data_ptr(), *tail)
+            _lib.call(entry.format("parcels"), *head, labels.data_ptr(), parcel_h.data_ptr(), parcel_d.data_ptr(), *tail)
         else:
-            _lib.call("cn_augment_chips_f32", *head, *tail)
+            _lib.call(entry.format("chips"), *head, *tail)
         kw["x"], kw["y"] = x_out, y_out
         if bd is not None:
             kw["bdist"] = bd_out

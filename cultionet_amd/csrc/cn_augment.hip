@@ -11,6 +11,8 @@
 // The four time-series ops (tswarp, tsnoise, tsdrift, tspeaks; augment_time, augment/augmenter_utils.py:111-165) work on
 // whole pixel series and have a kernel of their own, cn_augment_series_kernel, reached through cn_augment_series_f32 only:
 // the plane kernel leaves a series sample alone, the target kernel treats it as `none`.
+// The `_log_f32` entry points run the same kernels with EdgeDataset.get's log transform (data/datasets.py:481-484) in the
+// final store of x (CnChipStore<true>, cn_chip_store.h); bdist and y are never transformed.
 //
 // Plan table: CN_AUG_PLAN_WORDS int32 words per sample
 //   [0] op   [1] div   [2] top   [3] left   [4] r   [5] sigma (float bits)   [6] noise seed, low word   [7] high word
@@ -23,6 +25,7 @@
 // (torchvision is not available to the test suite; this equivalence is argued here, the permutation itself is tested.)
 // On a non-square plane the reference fills the uncovered corners with zeros; that case is refused (CN_ERR_ARG).
 #include "cn_common.h"
+#include "cn_chip_store.h"
 
 #include <type_traits>
 
@@ -95,15 +98,13 @@ struct CnAugLoadLabel {
   }
 };
 
-// final clip + z-score (x), final clip (bdist: m = 0, inv = 1), or a plain store (labels)
-struct CnAugStore {
-  float* p;
-  float lo, hi, m, inv;
-  __device__ __forceinline__ void operator()(long i, float v) const { p[i] = (fminf(fmaxf(v, lo), hi) - m) * inv; }
-};
+// final clip (+ log transform) + z-score (x), final clip (bdist: m = 0, inv = 1): CnChipStore (cn_chip_store.h), shared
+// with cn_edges.hip; or a plain store (labels)
 struct CnAugStoreLabel {
   long long* p;
   __device__ __forceinline__ void operator()(long i, long long v) const { p[i] = v; }
+  __device__ __forceinline__ const CnAugStoreLabel& values() const { return *this; }
+  __device__ __forceinline__ void finish(long) const {}
 };
 
 struct CnAugCrop {
@@ -154,7 +155,7 @@ __device__ __forceinline__ void cn_aug_geometry(int op, const Ld& ld, const St& 
         const float hy = 1.f - ly, hx = 1.f - lx;
         const float v00 = ld(cbase + (long)y0 * W + x0), v01 = ld(cbase + (long)y0 * W + x1);
         const float v10 = ld(cbase + (long)y1 * W + x0), v11 = ld(cbase + (long)y1 * W + x1);
-        st(base + (long)h * W + w, hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11));
+        st.values()(base + (long)h * W + w, hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11));
       } else {
         // nearest: source = min(floor(d * s), size - 1) with the float32 product
         const int y0 = min((int)floorf(__fmul_rn((float)h, sh)), ch - 1);
@@ -162,6 +163,8 @@ __device__ __forceinline__ void cn_aug_geometry(int op, const Ld& ld, const St& 
         st(base + (long)h * W + w, ld(cbase + (long)y0 * W + x0));
       }
     }
+    if constexpr (std::is_same<V, float>::value)
+      for (int idx = tid; idx < n; idx += 256) st.finish(base + (long)(r0 + idx / W) * W + idx % W);
     return;
   }
   const bool fh = op == CN_AUG_FLIPUD || op == CN_AUG_ROT180, fw = op == CN_AUG_FLIPLR || op == CN_AUG_ROT180;
@@ -199,12 +202,13 @@ __device__ __forceinline__ int cn_aug_checked_op(const int* __restrict__ row, in
 }
 
 // grid (bands, C * T, B); dynamic LDS: max(rotation tile, blur band, perlin gradients, parcel shifts)
-template <typename TIn>
+template <typename TIn, bool LOG>
 __global__ __launch_bounds__(256) void cn_augment_x_kernel(const TIn* __restrict__ x, float* __restrict__ out,
                                                           const int* __restrict__ plan, const float* __restrict__ perlin,
                                                           const int* __restrict__ labels, const int* __restrict__ parcel,
                                                           const float* __restrict__ mean, const float* __restrict__ stdv,
-                                                          int T, int H, int W, float scale, float lo, float hi) {
+                                                          int T, int H, int W, float scale, float lo, float hi,
+                                                          CnChipLog<LOG> lg) {
   extern __shared__ float smem[];
   const int tid = threadIdx.x, plane = blockIdx.y, b = blockIdx.z;
   const int c = plane / T, t = plane - c * T;
@@ -216,7 +220,8 @@ __global__ __launch_bounds__(256) void cn_augment_x_kernel(const TIn* __restrict
   const long HW = (long)H * W;
   const long base = ((long)b * gridDim.y + plane) * HW;
   const CnAugLoad<TIn> ld{x, scale, lo, hi};
-  const CnAugStore st{out, lo, hi, mean ? mean[c] : 0.f, stdv ? 1.0f / stdv[c] : 1.f};
+  const CnChipStore<LOG> st{out, lo, hi, mean ? mean[c] : 0.f, stdv ? 1.0f / stdv[c] : 1.f, lg};
+  const auto sv = st.values();  // the ops that compute in front of the store: see CnChipStore::values
   const int n = (r1 - r0) * W;
 
   if (op == CN_AUG_GAUSSIAN) {
@@ -239,8 +244,9 @@ __global__ __launch_bounds__(256) void cn_augment_x_kernel(const TIn* __restrict
       const float a = k0 * p[0] + k1 * p[1] + k0 * p[2];
       const float m = k0 * p[SW] + k1 * p[SW + 1] + k0 * p[SW + 2];
       const float z = k0 * p[2 * SW] + k1 * p[2 * SW + 1] + k0 * p[2 * SW + 2];
-      st(base + (long)(r0 + hl) * W + w, k0 * a + k1 * m + k0 * z);
+      sv(base + (long)(r0 + hl) * W + w, k0 * a + k1 * m + k0 * z);
     }
+    for (int idx = tid; idx < n; idx += 256) st.finish(base + (long)r0 * W + idx);
     return;
   }
   if (op == CN_AUG_SALTPEPPER) {
@@ -253,8 +259,9 @@ __global__ __launch_bounds__(256) void cn_augment_x_kernel(const TIn* __restrict
       const float u1 = (float)((cn_splitmix64(seed + 2ull * i) >> 40) + 1ull) * 0x1p-24f;
       const float u2 = (float)(cn_splitmix64(seed + 2ull * i + 1ull) >> 40) * 0x1p-24f;
       const float nrm = sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
-      st(base + off, ld(base + off) + 0.01f * nrm);
+      sv(base + off, ld(base + off) + 0.01f * nrm);
     }
+    for (int idx = tid; idx < n; idx += 256) st.finish(base + (long)r0 * W + idx);
     return;
   }
   if (op == CN_AUG_PERLIN) {
@@ -296,8 +303,9 @@ __global__ __launch_bounds__(256) void cn_augment_x_kernel(const TIn* __restrict
       const float n0 = (1.f - qh) * n00 + qh * n10;
       const float n1 = (1.f - qh) * n01 + qh * n11;
       const long off = (long)h * W + w;
-      st(base + off, ld(base + off) + 0.06f * ((1.f - qw) * n0 + qw * n1));
+      sv(base + off, ld(base + off) + 0.06f * ((1.f - qw) * n0 + qw * n1));
     }
+    for (int idx = tid; idx < n; idx += 256) st.finish(base + (long)r0 * W + idx);
     return;
   }
   if (op == CN_AUG_ROLL) {
@@ -339,7 +347,7 @@ __global__ __launch_bounds__(256) void cn_augment_target_kernel(const void* __re
   if (blockIdx.y == 0) {
     if (bdist == nullptr) return;
     const CnAugLoadAny ld{bdist, bdtype, scale, lo, hi};
-    const CnAugStore st{bdist_out, 0.f, hi, 0.f, 1.f};
+    const CnChipStore<false> st{bdist_out, 0.f, hi, 0.f, 1.f, {}};  // bdist is never log-transformed
     cn_aug_geometry<float>(op, ld, st, base, H, W, r0, r1, crop, (float*)tile);
   } else {
     const CnAugLoadLabel ld{y, ydtype};
@@ -363,11 +371,11 @@ __global__ __launch_bounds__(256) void cn_augment_target_kernel(const void* __re
 //   out[t] = store(clip(e[t], 0, 1))
 // With identity tables every step returns its input bit for bit (p - j = 0, drift = 0), so such a pixel equals
 // cn_prepare_chips_f32. A thread touches its own columns only: there is no barrier. grid (pixel tiles, C, series rows).
-template <typename TIn>
+template <typename TIn, bool LOG>
 __global__ __launch_bounds__(CN_AUG_SERIES_NT) void cn_augment_series_kernel(
     const TIn* __restrict__ x, float* __restrict__ out, const int* __restrict__ plan, const int* __restrict__ labels,
     const float* __restrict__ tables, const int* __restrict__ rows, const float* __restrict__ mean,
-    const float* __restrict__ stdv, int B, int T, int H, int W, float scale, float lo, float hi) {
+    const float* __restrict__ stdv, int B, int T, int H, int W, float scale, float lo, float hi, CnChipLog<LOG> lg) {
   extern __shared__ float smem[];
   const int tile = blockDim.x, tid = threadIdx.x, C = gridDim.y, c = blockIdx.y;
   const int b = rows[blockIdx.z];
@@ -376,7 +384,7 @@ __global__ __launch_bounds__(CN_AUG_SERIES_NT) void cn_augment_series_kernel(
   const int* row = plan + (long)b * CN_AUG_PLAN_WORDS;
   const int op = row[0];
   const CnAugLoad<TIn> ld{x, scale, lo, hi};
-  const CnAugStore st{out, lo, hi, mean ? mean[c] : 0.f, stdv ? 1.0f / stdv[c] : 1.f};
+  const CnChipStore<LOG> st{out, lo, hi, mean ? mean[c] : 0.f, stdv ? 1.0f / stdv[c] : 1.f, lg};
   const long base = ((long)b * C + c) * T * HW + pix;
   float* v = smem + tid;
   float* e = smem + T * tile + tid;
@@ -453,14 +461,17 @@ __global__ __launch_bounds__(CN_AUG_SERIES_NT) void cn_augment_series_kernel(
 // series_host / series_dev: the SAME [nrows][256 * (T + C * T + 1)] packed tables of the series samples (pos, drift,
 // nscale; see cn_augment_series_kernel) in host and in device memory; rows_host / rows_dev: the SAME [nrows] sample
 // indices, increasing, one per series sample; all nullable with nrows = 0, and a series op is then an unknown op.
+// logt: EdgeDataset.get's log transform (data/datasets.py:481-484) in the final store of x, w = max(log(v * gain + 1), floor)
+// between the last clip and the z-score (CnChipStore<true>); bdist and y are never transformed.
 // Two launches, three with a series sample; no allocation, no synchronisation.
 static int cn_augment_run(const void* x, int xdtype, const void* bdist, int bdtype, const void* y, int ydtype,
                           float* x_out, float* bdist_out, long long* y_out, const int* plan_host, const int* plan_dev,
                           const float* perlin_dev, const int* labels_dev, const int* parcel_host, const int* parcel_dev,
                           const float* series_host, const float* series_dev, const int* rows_host, const int* rows_dev,
                           int nrows, const float* mean, const float* stdv, int B, int C, int T, int H, int W,
-                          float scale, float lo, float hi, void* stream_) {
+                          float scale, float lo, float hi, bool logt, float gain, float floor, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
+  if (logt && !(gain > 0.f)) return CN_ERR_ARG;
   if (B <= 0 || C <= 0 || T <= 0 || H <= 0 || W <= 0) return CN_OK;
   if (x == nullptr || x_out == nullptr || y == nullptr || y_out == nullptr || plan_host == nullptr || plan_dev == nullptr) return CN_ERR_ARG;
   if ((bdist == nullptr) != (bdist_out == nullptr)) return CN_ERR_ARG;
@@ -543,12 +554,18 @@ static int cn_augment_run(const void* x, int xdtype, const void* bdist, int bdty
   }
   const int bands = cn_cdiv(H, CN_AUG_BR);
   const dim3 grid(bands, C * T, B), block(256);
+  const CnChipLog<true> lg{gain, floor};
+#define CN_AUG_X(TY, LOG, LG) CN_LAUNCH((cn_augment_x_kernel<TY, LOG>), grid, block, lds, stream, (const TY*)x, x_out, plan_dev, \
+                                   perlin_dev, labels_dev, parcel_dev, mean, stdv, T, H, W, scale, lo, hi, LG)
+#define CN_AUG_X2(TY) do { if (logt) CN_AUG_X(TY, true, lg); else CN_AUG_X(TY, false, CnChipLog<false>{}); } while (0)
   switch (xdtype) {
-    case 0: CN_LAUNCH(cn_augment_x_kernel<float>, grid, block, lds, stream, (const float*)x, x_out, plan_dev, perlin_dev, labels_dev, parcel_dev, mean, stdv, T, H, W, scale, lo, hi); break;
-    case 1: CN_LAUNCH(cn_augment_x_kernel<int>, grid, block, lds, stream, (const int*)x, x_out, plan_dev, perlin_dev, labels_dev, parcel_dev, mean, stdv, T, H, W, scale, lo, hi); break;
-    case 2: CN_LAUNCH(cn_augment_x_kernel<short>, grid, block, lds, stream, (const short*)x, x_out, plan_dev, perlin_dev, labels_dev, parcel_dev, mean, stdv, T, H, W, scale, lo, hi); break;
-    default: CN_LAUNCH(cn_augment_x_kernel<unsigned short>, grid, block, lds, stream, (const unsigned short*)x, x_out, plan_dev, perlin_dev, labels_dev, parcel_dev, mean, stdv, T, H, W, scale, lo, hi); break;
+    case 0: CN_AUG_X2(float); break;
+    case 1: CN_AUG_X2(int); break;
+    case 2: CN_AUG_X2(short); break;
+    default: CN_AUG_X2(unsigned short); break;
   }
+#undef CN_AUG_X2
+#undef CN_AUG_X
   int rc = cn_check_launch();
   if (rc != CN_OK) return rc;
   if (nrows > 0) {
@@ -556,12 +573,17 @@ static int cn_augment_run(const void* x, int xdtype, const void* bdist, int bdty
     const int nt = 2 * T * CN_AUG_SERIES_NT * (int)sizeof(float) <= CN_AUG_MAX_LDS ? CN_AUG_SERIES_NT : CN_AUG_SERIES_NT / 2;
     const size_t slds = (size_t)2 * T * nt * sizeof(float);
     const dim3 sgrid(cn_cdiv((long)H * W, nt), C, nrows), sblock(nt);
+#define CN_AUG_S(TY, LOG, LG) CN_LAUNCH((cn_augment_series_kernel<TY, LOG>), sgrid, sblock, slds, stream, (const TY*)x, x_out, \
+                                   plan_dev, labels_dev, series_dev, rows_dev, mean, stdv, B, T, H, W, scale, lo, hi, LG)
+#define CN_AUG_S2(TY) do { if (logt) CN_AUG_S(TY, true, lg); else CN_AUG_S(TY, false, CnChipLog<false>{}); } while (0)
     switch (xdtype) {
-      case 0: CN_LAUNCH(cn_augment_series_kernel<float>, sgrid, sblock, slds, stream, (const float*)x, x_out, plan_dev, labels_dev, series_dev, rows_dev, mean, stdv, B, T, H, W, scale, lo, hi); break;
-      case 1: CN_LAUNCH(cn_augment_series_kernel<int>, sgrid, sblock, slds, stream, (const int*)x, x_out, plan_dev, labels_dev, series_dev, rows_dev, mean, stdv, B, T, H, W, scale, lo, hi); break;
-      case 2: CN_LAUNCH(cn_augment_series_kernel<short>, sgrid, sblock, slds, stream, (const short*)x, x_out, plan_dev, labels_dev, series_dev, rows_dev, mean, stdv, B, T, H, W, scale, lo, hi); break;
-      default: CN_LAUNCH(cn_augment_series_kernel<unsigned short>, sgrid, sblock, slds, stream, (const unsigned short*)x, x_out, plan_dev, labels_dev, series_dev, rows_dev, mean, stdv, B, T, H, W, scale, lo, hi); break;
+      case 0: CN_AUG_S2(float); break;
+      case 1: CN_AUG_S2(int); break;
+      case 2: CN_AUG_S2(short); break;
+      default: CN_AUG_S2(unsigned short); break;
     }
+#undef CN_AUG_S2
+#undef CN_AUG_S
     rc = cn_check_launch();
     if (rc != CN_OK) return rc;
   }
@@ -578,7 +600,7 @@ extern "C" int cn_augment_parcels_f32(const void* x, int xdtype, const void* bdi
                                       int B, int C, int T, int H, int W, float scale, float lo, float hi, void* stream_) {
   return cn_augment_run(x, xdtype, bdist, bdtype, y, ydtype, x_out, bdist_out, y_out, plan_host, plan_dev, perlin_dev,
                         labels_dev, parcel_host, parcel_dev, nullptr, nullptr, nullptr, nullptr, 0, mean, stdv, B, C, T, H, W,
-                        scale, lo, hi, stream_);
+                        scale, lo, hi, false, 0.f, 0.f, stream_);
 }
 
 // cn_augment_parcels_f32 plus the four series ops (11 tswarp, 12 tsnoise, 13 tsdrift, 14 tspeaks). CN_ERR_ARG with
@@ -593,7 +615,7 @@ extern "C" int cn_augment_series_f32(const void* x, int xdtype, const void* bdis
                                      float lo, float hi, void* stream_) {
   return cn_augment_run(x, xdtype, bdist, bdtype, y, ydtype, x_out, bdist_out, y_out, plan_host, plan_dev, perlin_dev,
                         labels_dev, parcel_host, parcel_dev, series_host, series_dev, rows_host, rows_dev, nrows, mean, stdv,
-                        B, C, T, H, W, scale, lo, hi, stream_);
+                        B, C, T, H, W, scale, lo, hi, false, 0.f, 0.f, stream_);
 }
 
 // The nine ops that need no parcel labelling: a `roll` row is CN_ERR_ARG here, as every unknown op.
@@ -603,4 +625,39 @@ extern "C" int cn_augment_chips_f32(const void* x, int xdtype, const void* bdist
                                     int B, int C, int T, int H, int W, float scale, float lo, float hi, void* stream_) {
   return cn_augment_parcels_f32(x, xdtype, bdist, bdtype, y, ydtype, x_out, bdist_out, y_out, plan_host, plan_dev, perlin_dev,
                                 nullptr, nullptr, nullptr, mean, stdv, B, C, T, H, W, scale, lo, hi, stream_);
+}
+
+// The three entry points above with EdgeDataset.get's log transform (data/datasets.py:481-484) in the final store of x,
+// between the last clip and the z-score; bdist and y come out as from the plain entries. log_gain <= 0 is CN_ERR_ARG.
+extern "C" int cn_augment_series_log_f32(const void* x, int xdtype, const void* bdist, int bdtype, const void* y, int ydtype,
+                                         float* x_out, float* bdist_out, long long* y_out, const int* plan_host,
+                                         const int* plan_dev, const float* perlin_dev, const int* labels_dev,
+                                         const int* parcel_host, const int* parcel_dev, const float* series_host,
+                                         const float* series_dev, const int* rows_host, const int* rows_dev, int nrows,
+                                         const float* mean, const float* stdv, int B, int C, int T, int H, int W,
+                                         float scale, float lo, float hi, float log_gain, float log_floor, void* stream_) {
+  return cn_augment_run(x, xdtype, bdist, bdtype, y, ydtype, x_out, bdist_out, y_out, plan_host, plan_dev, perlin_dev,
+                        labels_dev, parcel_host, parcel_dev, series_host, series_dev, rows_host, rows_dev, nrows, mean, stdv,
+                        B, C, T, H, W, scale, lo, hi, true, log_gain, log_floor, stream_);
+}
+
+extern "C" int cn_augment_parcels_log_f32(const void* x, int xdtype, const void* bdist, int bdtype, const void* y, int ydtype,
+                                          float* x_out, float* bdist_out, long long* y_out, const int* plan_host,
+                                          const int* plan_dev, const float* perlin_dev, const int* labels_dev,
+                                          const int* parcel_host, const int* parcel_dev, const float* mean,
+                                          const float* stdv, int B, int C, int T, int H, int W, float scale, float lo,
+                                          float hi, float log_gain, float log_floor, void* stream_) {
+  return cn_augment_series_log_f32(x, xdtype, bdist, bdtype, y, ydtype, x_out, bdist_out, y_out, plan_host, plan_dev,
+                                   perlin_dev, labels_dev, parcel_host, parcel_dev, nullptr, nullptr, nullptr, nullptr, 0,
+                                   mean, stdv, B, C, T, H, W, scale, lo, hi, log_gain, log_floor, stream_);
+}
+
+extern "C" int cn_augment_chips_log_f32(const void* x, int xdtype, const void* bdist, int bdtype, const void* y, int ydtype,
+                                        float* x_out, float* bdist_out, long long* y_out, const int* plan_host,
+                                        const int* plan_dev, const float* perlin_dev, const float* mean, const float* stdv,
+                                        int B, int C, int T, int H, int W, float scale, float lo, float hi, float log_gain,
+                                        float log_floor, void* stream_) {
+  return cn_augment_parcels_log_f32(x, xdtype, bdist, bdtype, y, ydtype, x_out, bdist_out, y_out, plan_host, plan_dev,
+                                    perlin_dev, nullptr, nullptr, nullptr, mean, stdv, B, C, T, H, W, scale, lo, hi,
+                                    log_gain, log_floor, stream_);
 }

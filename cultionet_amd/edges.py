@@ -16,13 +16,19 @@ from . import _lib
 from .engine import _stream
 
 SCALE_FACTOR = 10_000.0
+# ``--log-transform`` of the reference (scripts/args.yml:281-286; EdgeDataset.get, data/datasets.py:481-484):
+# x = torch.log(x * 50.0 + 1.0).clamp_min(1e-9) after scale / clip / augmentation and before the z-score
+LOG_GAIN, LOG_FLOOR = 50.0, 1e-9
 _DTYPES = {torch.float32: 0, torch.int32: 1, torch.int16: 2, torch.uint16: 3}
 
 
 def prepare_chips(x_raw: torch.Tensor, mean: T.Optional[torch.Tensor] = None, std: T.Optional[torch.Tensor] = None,
-                  scale: float = 1.0 / SCALE_FACTOR, lo: float = 1e-9, hi: float = 1.0) -> torch.Tensor:
+                  scale: float = 1.0 / SCALE_FACTOR, lo: float = 1e-9, hi: float = 1.0,
+                  log_transform: bool = False) -> torch.Tensor:
     """x_raw: [B, C, T, H, W] on the GPU (f32 / i32 / i16 / u16); mean / std: exactly C values each (any shape), each
-    optional on its own: the kernel indexes both by channel."""
+    optional on its own: the kernel indexes both by channel. ``log_transform``: the reference's ``--log-transform``,
+    log(v * 50 + 1) floored at 1e-9 between the clip and the z-score, in the same pass (cn_prepare_chips_log_f32); mean and
+    std must then be statistics of the transformed values."""
     if not x_raw.is_cuda:
         raise RuntimeError("prepare_chips needs a device tensor")
     if x_raw.dtype not in _DTYPES:
@@ -37,9 +43,12 @@ def prepare_chips(x_raw: torch.Tensor, mean: T.Optional[torch.Tensor] = None, st
         raise ValueError("mean must hold one value per channel")
     if s is not None and s.numel() != C:
         raise ValueError("std must hold one value per channel")
-    _lib.call("cn_prepare_chips_f32", x_raw.data_ptr(), _DTYPES[x_raw.dtype], out.data_ptr(),
-              m.data_ptr() if m is not None else None, s.data_ptr() if s is not None else None, B, C, L, float(scale),
-              float(lo), float(hi), _stream())
+    args = (x_raw.data_ptr(), _DTYPES[x_raw.dtype], out.data_ptr(), m.data_ptr() if m is not None else None,
+            s.data_ptr() if s is not None else None, B, C, L, float(scale), float(lo), float(hi))
+    if log_transform:
+        _lib.call("cn_prepare_chips_log_f32", *args, LOG_GAIN, LOG_FLOOR, _stream())
+    else:
+        _lib.call("cn_prepare_chips_f32", *args, _stream())
     return out
 
 

@@ -13,6 +13,9 @@ host arithmetic and a synchronous copy would be what limits data-parallel scalin
 
 Float batches (already prepared upstream) are copied and passed through untouched.
 
+``DeviceFeeder(..., log_transform=True)`` applies the reference's ``--log-transform`` (data/datasets.py:481-484) to ``x``
+in that same pass, between the clip (or the augmentation) and the z-score.
+
 ``DeviceFeeder(..., augmenter=DeviceAugmenter(...))`` augments the labelled raw batches in the same place: the plan of
 each batch is drawn on the host, and ``cn_augment_chips_f32`` takes the place of the plain prologue on the copy stream
 (cultionet_amd.augment).
@@ -42,13 +45,17 @@ class DeviceFeeder:
     """``for batch in feeder.iterate(host_batches): step(batch)`` -- double-buffered host -> HBM feeding."""
 
     def __init__(self, device: T.Union[str, torch.device], mean: T.Optional[torch.Tensor] = None,
-                 std: T.Optional[torch.Tensor] = None, augmenter: T.Optional["DeviceAugmenter"] = None):
+                 std: T.Optional[torch.Tensor] = None, augmenter: T.Optional["DeviceAugmenter"] = None,
+                 log_transform: bool = False):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("DeviceFeeder feeds a GPU (there is no CPU training path)")
         self.copy_stream = torch.cuda.Stream(device=self.device)
         self.mean, self.std = mean, std
         self.augmenter = augmenter  # cultionet_amd.augment.DeviceAugmenter for TRAINING batches; None: no augmentation
+        # the reference's --log-transform (data/datasets.py:481-484), fused into the prologue of x, with or without an
+        # augmenter; mean / std are then statistics of the transformed values (NormValues.from_batches(log_transform=True))
+        self.log_transform = bool(log_transform)
 
     def _stage(self, host: Data) -> T.Tuple[Data, "torch.cuda.Event"]:
         """Enqueue copy + prologue of one batch on the copy stream; returns (device batch, ready event)."""
@@ -60,11 +67,11 @@ class DeviceFeeder:
             x = kw["x"]
             if self.augmenter is not None and x.dtype != torch.float32 and kw.get("y") is not None:
                 ev = torch.cuda.Event()  # scale -> clip -> one augmentation per chosen sample -> clip -> z-score
-                out = self.augmenter.apply(Data(**kw), self.mean, self.std)
+                out = self.augmenter.apply(Data(**kw), self.mean, self.std, log_transform=self.log_transform)
                 ev.record(self.copy_stream)
                 return out, ev
             if x.dtype != torch.float32:  # raw reflectances: x/10000 -> clip -> z-score, one pass on the device
-                kw["x"] = prepare_chips(x, self.mean, self.std)
+                kw["x"] = prepare_chips(x, self.mean, self.std, log_transform=self.log_transform)
             bd = kw.get("bdist")
             if bd is not None and bd.dtype != torch.float32:
                 B = bd.shape[0]

@@ -120,9 +120,14 @@ class LightningModuleMixin(_Base):
         self.cultionet_model.mask_model.precision = value
 
     # ---- device-side input prologue ----------------------------------------------------------
-    def set_norm_values(self, mean: T.Optional[torch.Tensor], std: T.Optional[torch.Tensor]) -> None:
-        """Per-channel z-score statistics (NormValues, utils/normalize.py:63-82) applied by the device prologue."""
+    def set_norm_values(self, mean: T.Optional[torch.Tensor], std: T.Optional[torch.Tensor],
+                        log_transform: bool = False) -> None:
+        """Per-channel z-score statistics (NormValues, utils/normalize.py:63-82) applied by the device prologue.
+        ``log_transform``: the datasets' ``log_transform`` switch (data/datasets.py:481-484), passed where the statistics
+        are, as upstream passes both to EdgeDataset: the prologue then takes log(x * 50 + 1) floored at 1e-9 before the
+        z-score, and mean / std are statistics of the transformed values."""
         self._norm_mean, self._norm_std = mean, std
+        self._log_transform = bool(log_transform)
 
     def set_augmenter(self, augmenter) -> None:
         """A cultionet_amd.augment.DeviceAugmenter (or None): raw labelled batches are augmented by the device prologue
@@ -142,9 +147,10 @@ class LightningModuleMixin(_Base):
         from .edges import SCALE_FACTOR, prepare_chips
 
         aug = getattr(self, "_augmenter", None)
+        log = getattr(self, "_log_transform", False)
         if aug is not None and self.training and getattr(batch, "y", None) is not None:
-            return aug.apply(batch, getattr(self, "_norm_mean", None), getattr(self, "_norm_std", None))
-        batch.x = prepare_chips(x, getattr(self, "_norm_mean", None), getattr(self, "_norm_std", None))
+            return aug.apply(batch, getattr(self, "_norm_mean", None), getattr(self, "_norm_std", None), log_transform=log)
+        batch.x = prepare_chips(x, getattr(self, "_norm_mean", None), getattr(self, "_norm_std", None), log_transform=log)
         bd = getattr(batch, "bdist", None)
         if bd is not None and bd.dtype != torch.float32:
             B = bd.shape[0]

@@ -17,6 +17,13 @@ Quantiles follow the sketch's definition at the point where the sketch still hol
 cumulative weights (i - 0.5) / n between the minimum at 0 and the maximum at 1); above 12288 rows the reference's own
 quantiles are a randomized approximation of these. The value of bin k is ``float32(clip(k / 10000, 1e-9, 1))``, the
 reference's own fp32 value, widened to float64.
+
+``log_transform=True`` (the reference's ``--log-transform``: the statistics dataset is built with it too,
+scripts/cultionet.py:630-721) changes the VALUE of a bin and nothing on the device: EdgeDataset.get feeds
+``log(x * 50 + 1).clamp_min(1e-9)`` of the clipped value (data/datasets.py:481-484), a strictly increasing map of the bins
+above 0, so the histograms, the per-batch lower-median bins and the quantile bins are the same, and
+``cn_hist_batch_reduce`` takes its weights as a table. The caller says so where the counts are made (``DatasetStats``,
+``from_batches``) and where they are read (``stats_from_counts``, ``from_counts``); a ``.norm`` file gains no key.
 """
 from __future__ import annotations
 
@@ -31,23 +38,33 @@ from .data import Data
 NBINS = 10_001           # bins 0..10000 of clamp(v, 0, 10000)
 REC_WORDS = 7            # int64 words of one (batch, channel) record of cn_hist_batch_reduce
 WEIGHT_SHIFT = 37        # every fp32 value in [1e-4, 1] is a multiple of 2^-37
+LOG_WEIGHT_SHIFT = 31    # every log-domain value of a bin k >= 1, in [0.004987, 3.931826], is a multiple of 2^-31
 RECORD_CHUNK = 256       # batches per device record table
 _XDTYPES = {torch.int32: 1, torch.int16: 2, torch.uint16: 3}
 _YDTYPES = {torch.int32: 1, torch.int16: 2, torch.uint16: 3, torch.int64: 4}
 
 
-def bin_values() -> np.ndarray:
-    """float64 [NBINS]: what EdgeDataset.get makes of a stored k, in fp32 as the reference holds it (datasets.py:443)."""
+def weight_shift(log_transform: bool = False) -> int:
+    return LOG_WEIGHT_SHIFT if log_transform else WEIGHT_SHIFT
+
+
+def bin_values(log_transform: bool = False) -> np.ndarray:
+    """float64 [NBINS]: what EdgeDataset.get makes of a stored k, in fp32 as the reference holds it (datasets.py:443);
+    with ``log_transform`` its torch.log(x * 50.0 + 1.0).clamp_min(1e-9) of that (datasets.py:481-484), computed by torch
+    itself in fp32. Bin 0 is 1e-9 in both domains."""
     k = np.arange(NBINS, dtype=np.float32)
-    return np.clip(k / np.float32(10000.0), np.float32(1e-9), np.float32(1.0)).astype(np.float64)
+    v = np.clip(k / np.float32(10000.0), np.float32(1e-9), np.float32(1.0))
+    if log_transform:
+        v = torch.log(torch.from_numpy(v) * 50.0 + 1.0).clamp_min(1e-9).numpy()
+    return v.astype(np.float64)
 
 
-def bin_weights() -> np.ndarray:
-    """int64 [NBINS]: bin_values() * 2^37, exact for k >= 1; bin 0 (1e-9, no multiple of 2^-37) has weight 0 and is
-    carried by its own count in the record."""
-    v = bin_values()
-    w = np.round(v * 2.0 ** WEIGHT_SHIFT).astype(np.int64)
-    assert np.array_equal(w[1:].astype(np.float64) * 2.0 ** -WEIGHT_SHIFT, v[1:])
+def bin_weights(log_transform: bool = False) -> np.ndarray:
+    """int64 [NBINS]: bin_values() * 2^37 (2^31 in the log domain), exact for k >= 1; bin 0 (1e-9, no such multiple) has
+    weight 0 and is carried by its own count in the record."""
+    v, shift = bin_values(log_transform), weight_shift(log_transform)
+    w = np.round(v * 2.0 ** shift).astype(np.int64)
+    assert np.array_equal(w[1:].astype(np.float64) * 2.0 ** -shift, v[1:]) and w.max() < 2 ** 40
     w[0] = 0
     return w
 
@@ -61,7 +78,7 @@ def _check_classes(class_info: T.Dict[str, int]) -> T.Tuple[int, int]:
     return max_crop, edge
 
 
-def _replay_variance(records: np.ndarray, values: np.ndarray) -> float:
+def _replay_variance(records: np.ndarray, values: np.ndarray, shift: int = WEIGHT_SHIFT) -> float:
     """Variance(method='median').add over one channel's records in order, then .std() (stats.py:642-683)."""
     v0 = Fraction(float(values[0]))
     count, mean, cmom2 = 0, None, 0.0
@@ -72,7 +89,7 @@ def _replay_variance(records: np.ndarray, values: np.ndarray) -> float:
         s2 = (s2hi << 64) | (s2lo & 0xFFFFFFFFFFFFFFFF)
         m = Fraction(float(values[mbin]))
         # sum_{k>=1} h_k (val_k - m)^2 + h_0 (1e-9 - m)^2, exactly, rounded once
-        centred = (Fraction(s2, 1 << (2 * WEIGHT_SHIFT)) - 2 * m * Fraction(s1, 1 << WEIGHT_SHIFT) + (n - h0) * m * m
+        centred = (Fraction(s2, 1 << (2 * shift)) - 2 * m * Fraction(s1, 1 << shift) + (n - h0) * m * m
                    + h0 * (v0 - m) ** 2)
         centred, m = float(centred), float(values[mbin])
         if mean is None:
@@ -111,22 +128,23 @@ def _hist_quantile(hist: np.ndarray, cum: np.ndarray, values: np.ndarray, q: flo
 
 
 def stats_from_counts(records: np.ndarray, hist: np.ndarray, label_counts: np.ndarray, class_info: T.Dict[str, int],
-                      centering: str = "median", lower_quantile: float = 0.05,
-                      upper_quantile: float = 0.95) -> T.Dict[str, np.ndarray]:
+                      centering: str = "median", lower_quantile: float = 0.05, upper_quantile: float = 0.95,
+                      log_transform: bool = False) -> T.Dict[str, np.ndarray]:
     """The host half of DatasetStats.finish, float64 throughout; runs without a GPU.
 
-    records: int64 [batches, C, 7] as cn_hist_batch_reduce writes them with bin_weights(); hist: [C, NBINS] counts of the
-    whole dataset; label_counts: int64 [edge_class + 3] = {y < 0, y == 0, ..., y == edge_class, y > edge_class}.
+    records: int64 [batches, C, 7] as cn_hist_batch_reduce writes them with bin_weights(log_transform), the same flag as
+    here; hist: [C, NBINS] counts of the whole dataset; label_counts: int64 [edge_class + 3] = {y < 0, y == 0, ...,
+    y == edge_class, y > edge_class}.
     """
     max_crop, edge = _check_classes(class_info)
     records = np.asarray(records, dtype=np.int64).reshape(-1, hist.shape[0], REC_WORDS)
     hist = np.asarray(hist).astype(np.int64)
-    values = bin_values()
+    values, shift = bin_values(log_transform), weight_shift(log_transform)
     C = hist.shape[0]
     out = {k: np.zeros(C) for k in ("std", "mean", "lower_bound", "upper_bound")}
     for c in range(C):
         cum = np.cumsum(hist[c])
-        out["std"][c] = _replay_variance(records[:, c], values)
+        out["std"][c] = _replay_variance(records[:, c], values, shift)
         if centering == "mean":  # Quantile.mean(), stats.py:455-456
             out["mean"][c] = float(np.dot(hist[c].astype(np.float64), values) / cum[-1]) if cum[-1] else float("nan")
         else:                    # Quantile.median()
@@ -207,8 +225,10 @@ class NormValues:
 
     @classmethod
     def from_counts(cls, records, hist, label_counts, class_info, centering: str = "median",
-                    lower_quantile: float = 0.05, upper_quantile: float = 0.95) -> "NormValues":
-        s = stats_from_counts(records, hist, label_counts, class_info, centering, lower_quantile, upper_quantile)
+                    lower_quantile: float = 0.05, upper_quantile: float = 0.95,
+                    log_transform: bool = False) -> "NormValues":
+        s = stats_from_counts(records, hist, label_counts, class_info, centering, lower_quantile, upper_quantile,
+                              log_transform)
         return cls(dataset_mean=_c5(s["mean"]), dataset_std=_c5(s["std"]), lower_bound=_c5(s["lower_bound"]),
                    upper_bound=_c5(s["upper_bound"]), dataset_crop_counts=torch.from_numpy(s["crop_counts"]),
                    dataset_edge_counts=torch.from_numpy(s["edge_counts"]), num_channels=len(s["mean"]))
@@ -216,9 +236,10 @@ class NormValues:
     @classmethod
     def from_batches(cls, host_batches: T.Iterable[Data], device: T.Union[str, torch.device],
                      class_info: T.Dict[str, int], centering: str = "median", lower_quantile: float = 0.05,
-                     upper_quantile: float = 0.95) -> "NormValues":
+                     upper_quantile: float = 0.95, log_transform: bool = False) -> "NormValues":
         """from_dataset over raw host batches: batch i+1 is pinned and copied on a copy stream while batch i is counted on
-        the current stream (the double buffering of DeviceFeeder.iterate)."""
+        the current stream (the double buffering of DeviceFeeder.iterate). ``log_transform``: statistics of the values a
+        dataset built with ``log_transform=True`` feeds (datasets.py:481-484), for ``DeviceFeeder(log_transform=True)``."""
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("NormValues.from_batches counts on a GPU; use stats_from_counts for host-side counts")
@@ -255,7 +276,7 @@ class NormValues:
                     if v is not None:
                         v.record_stream(cur)
                 if stats is None:
-                    stats = DatasetStats(batch.x.shape[1], class_info, device)
+                    stats = DatasetStats(batch.x.shape[1], class_info, device, log_transform=log_transform)
                 stats.add(batch)
             return stats.finish(centering, lower_quantile, upper_quantile)
 
@@ -264,11 +285,12 @@ class DatasetStats:
     """Streaming counts of raw device batches; ``add`` and ``finish`` work on the current stream."""
 
     def __init__(self, num_channels: int, class_info: T.Dict[str, int], device: T.Union[str, torch.device],
-                 record_chunk: int = RECORD_CHUNK):
+                 record_chunk: int = RECORD_CHUNK, log_transform: bool = False):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("DatasetStats counts on a GPU (there is no CPU path; see stats_from_counts)")
         self.class_info = dict(class_info)
+        self.log_transform = bool(log_transform)  # decides the weights of the records, so it is fixed here
         _, edge = _check_classes(class_info)
         self.num_channels, self.nlab, self.chunk = int(num_channels), edge + 1, int(record_chunk)
         C = self.num_channels
@@ -277,7 +299,7 @@ class DatasetStats:
         self._buf = torch.zeros(sum(sizes), dtype=torch.int64, device=self.device)
         self._hist, self._labels, self._records = self._buf.split(sizes)
         self._batch_hist = torch.zeros(C * NBINS, dtype=torch.int32, device=self.device)  # uint32 words
-        self._weights = torch.from_numpy(bin_weights()).to(self.device)
+        self._weights = torch.from_numpy(bin_weights(self.log_transform)).to(self.device)
         self._filled = 0                             # records in the device table
         self._host_records: T.List[np.ndarray] = []  # full chunks, already on the host
 
@@ -317,7 +339,12 @@ class DatasetStats:
         records = np.concatenate(self._host_records + [rec.reshape(self._filled, C, REC_WORDS)])
         return records, hist.reshape(C, NBINS), labels
 
-    def finish(self, centering: str = "median", lower_quantile: float = 0.05,
-               upper_quantile: float = 0.95) -> NormValues:
+    def finish(self, centering: str = "median", lower_quantile: float = 0.05, upper_quantile: float = 0.95,
+               log_transform: T.Optional[bool] = None) -> NormValues:
+        """``log_transform`` defaults to the constructor's; another value is refused, since the records were summed with
+        that domain's weights."""
+        if log_transform is not None and bool(log_transform) != self.log_transform:
+            raise ValueError(f"these counts were made with log_transform={self.log_transform}")
         records, hist, labels = self.counts()
-        return NormValues.from_counts(records, hist, labels, self.class_info, centering, lower_quantile, upper_quantile)
+        return NormValues.from_counts(records, hist, labels, self.class_info, centering, lower_quantile, upper_quantile,
+                                      self.log_transform)

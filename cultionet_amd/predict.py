@@ -19,7 +19,7 @@ import typing as T
 import torch
 
 from . import _lib
-from .edges import _DTYPES, SCALE_FACTOR
+from .edges import _DTYPES, LOG_FLOOR, LOG_GAIN, SCALE_FACTOR
 from .engine import _stream
 
 
@@ -35,7 +35,7 @@ class SlidingWindowPredictor:
     def __init__(self, lit, window_size: int = 100, padding: int = 5, batch_size: int = 8,
                  mean: T.Optional[torch.Tensor] = None, std: T.Optional[torch.Tensor] = None,
                  scale: float = 1.0 / SCALE_FACTOR, lo: float = 1e-9, hi: float = 1.0, precision: str = "32-true",
-                 replay: bool = True, pixels_per_launch: T.Optional[int] = 400_000):
+                 replay: bool = True, pixels_per_launch: T.Optional[int] = 400_000, log_transform: bool = False):
         if window_size <= 0 or padding < 0 or batch_size <= 0:
             raise ValueError("window_size, batch_size must be positive and padding non-negative")
         if pixels_per_launch is not None and pixels_per_launch < 0:
@@ -49,6 +49,9 @@ class SlidingWindowPredictor:
         self.ws, self.pad, self.bs = int(window_size), int(padding), int(batch_size)
         self.mean, self.std = mean, std
         self.scale, self.lo, self.hi = float(scale), float(lo), float(hi)
+        # the predict dataset's log_transform (scripts/cultionet.py:171; data/datasets.py:481-484): log(v * 50 + 1) floored at
+        # 1e-9 before the z-score, in the window kernel (cn_window_chips_log_f32). For a model trained with --log-transform.
+        self.log_transform = bool(log_transform)
         # every full window batch has the same shape: its ~120 launches are recorded once and replayed
         # (cultionet_amd/replay.py) -- at the reference CLI's default batch of 4 the eager forward is host-bound
         self.replay = bool(replay)
@@ -95,10 +98,13 @@ class SlidingWindowPredictor:
                     x = plan_input(model, (n, C, Tn, S, S), self.bf16, dev)
                 if x is None:
                     x = torch.empty((n, C, Tn, S, S), dtype=torch.float32, device=dev)
-                _lib.call("cn_window_chips_f32", scene.data_ptr(), _DTYPES[scene.dtype], x.data_ptr(),
-                          rc[i:i + n].data_ptr(), n, C, Tn, H, W, S, self.pad,
-                          mean.data_ptr() if mean is not None else None, std.data_ptr() if std is not None else None,
-                          self.scale, self.lo, self.hi, _stream())
+                args = (scene.data_ptr(), _DTYPES[scene.dtype], x.data_ptr(), rc[i:i + n].data_ptr(), n, C, Tn, H, W, S,
+                        self.pad, mean.data_ptr() if mean is not None else None,
+                        std.data_ptr() if std is not None else None, self.scale, self.lo, self.hi)
+                if self.log_transform:
+                    _lib.call("cn_window_chips_log_f32", *args, LOG_GAIN, LOG_FLOOR, _stream())
+                else:
+                    _lib.call("cn_window_chips_f32", *args, _stream())
                 with torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.bf16):
                     pred = model(x)
                 d, e, c = (pred[k].float().contiguous() for k in ("distance", "edge", "crop"))

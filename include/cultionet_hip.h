@@ -363,6 +363,14 @@ int cn_amp_count_skip(const float* found_inf, int* skipped, void* stream);
  * predictions: LightningGTiffWriter (callbacks.py:176-227): drop padding, x scale, clip, cast to uint16. */
 int cn_prepare_chips_f32(const void* x, int dtype, float* y, const float* mean, const float* stdv, int B, int C, long L,
                          float scale, float lo, float hi, void* stream);
+/* cn_prepare_chips_f32 with EdgeDataset.get's log transform (data/datasets.py:481-484: torch.log(x * 50.0 + 1.0)
+ * .clamp_min(1e-9), after scale / clip / augmentation and before the z-score) fused into the same pass, in fp32 step by
+ * step as torch does it, with v = clip(x*scale, lo, hi):
+ *   t = v * log_gain;  u = t + 1 (two roundings, no fma);  w = max(log u, log_floor);  y = (w - mean[c]) / std[c]
+ * log u is the double logarithm rounded once. A stored 0 or negative value gives v = lo = 1e-9, u = 1, w = log_floor.
+ * Same launch as the plain entry, whose results do not change. CN_ERR_ARG: log_gain <= 0 (checked first). */
+int cn_prepare_chips_log_f32(const void* x, int dtype, float* y, const float* mean, const float* stdv, int B, int C, long L,
+                             float scale, float lo, float hi, float log_gain, float log_floor, void* stream);
 int cn_predictions_to_u16(const float* dist, const float* edge, const float* crop, unsigned short* out, int B, int H,
                           int W, int pad_top, int pad_left, int h, int w, float scale, void* stream);
 /* Training augmentation fused into the prologue: replaces the per-sample CPU augmentation of EdgeDataset.get
@@ -424,6 +432,27 @@ int cn_augment_series_f32(const void* x, int xdtype, const void* bdist, int bdty
                           const float* series_host, const float* series_dev, const int* rows_host, const int* rows_dev,
                           int nrows, const float* mean, const float* stdv, int B, int C, int T, int H, int W, float scale,
                           float lo, float hi, void* stream);
+/* cn_augment_chips_f32 / cn_augment_parcels_f32 / cn_augment_series_f32 with EdgeDataset.get's log transform
+ * (data/datasets.py:481-484) in the final store of x: after the last clip of the augmentation and before the z-score,
+ * w = max(log(v * log_gain + 1), log_floor) with the arithmetic of cn_prepare_chips_log_f32. bdist_out and y_out are
+ * those of the plain entries (the reference transforms batch.x only); a sample with op none comes out bit-identical to
+ * cn_prepare_chips_log_f32. Same launches and same errors as the plain entries, plus CN_ERR_ARG for log_gain <= 0. */
+int cn_augment_chips_log_f32(const void* x, int xdtype, const void* bdist, int bdtype, const void* y, int ydtype,
+                             float* x_out, float* bdist_out, long long* y_out, const int* plan_host, const int* plan_dev,
+                             const float* perlin_dev, const float* mean, const float* stdv, int B, int C, int T, int H,
+                             int W, float scale, float lo, float hi, float log_gain, float log_floor, void* stream);
+int cn_augment_parcels_log_f32(const void* x, int xdtype, const void* bdist, int bdtype, const void* y, int ydtype,
+                               float* x_out, float* bdist_out, long long* y_out, const int* plan_host, const int* plan_dev,
+                               const float* perlin_dev, const int* labels_dev, const int* parcel_host,
+                               const int* parcel_dev, const float* mean, const float* stdv, int B, int C, int T, int H,
+                               int W, float scale, float lo, float hi, float log_gain, float log_floor, void* stream);
+int cn_augment_series_log_f32(const void* x, int xdtype, const void* bdist, int bdtype, const void* y, int ydtype,
+                              float* x_out, float* bdist_out, long long* y_out, const int* plan_host, const int* plan_dev,
+                              const float* perlin_dev, const int* labels_dev, const int* parcel_host,
+                              const int* parcel_dev, const float* series_host, const float* series_dev,
+                              const int* rows_host, const int* rows_dev, int nrows, const float* mean, const float* stdv,
+                              int B, int C, int T, int H, int W, float scale, float lo, float hi, float log_gain,
+                              float log_floor, void* stream);
 /* sliding-window predict (BASELINE configs[4]; data/create.py:176-212, data/store.py:69-100, callbacks.py:176-227):
  * window_chips: window n = crop [r0-pad, r0-pad+S) x [c0-pad, c0-pad+S) of the zero-extended scene [C*T][H][W]
  *   (stored dtype as prepare), scaled / clipped / z-scored into fp32 [nwin][C*T][S][S]; win_rc: DEVICE int [nwin][2].
@@ -431,6 +460,12 @@ int cn_augment_series_f32(const void* x, int xdtype, const void* bdist, int bdty
 int cn_window_chips_f32(const void* scene, int dtype, float* out, const int* win_rc, int nwin, int C, int T, int H, int W,
                         int S, int pad, const float* mean, const float* stdv, float scale, float lo, float hi,
                         void* stream);
+/* cn_window_chips_f32 with EdgeDataset.get's log transform (data/datasets.py:481-484, which the predict dataset applies
+ * too) between the clip and the z-score, arithmetic of cn_prepare_chips_log_f32. A zero-filled border pixel is
+ * v = lo = 1e-9 and comes out as (log_floor - mean[c]) / std[c]. CN_ERR_ARG: log_gain <= 0 (checked first). */
+int cn_window_chips_log_f32(const void* scene, int dtype, float* out, const int* win_rc, int nwin, int C, int T, int H,
+                            int W, int S, int pad, const float* mean, const float* stdv, float scale, float lo, float hi,
+                            float log_gain, float log_floor, void* stream);
 int cn_stitch_predictions_u16(const float* dist, const float* edge, const float* crop, unsigned short* out,
                               const int* win_rc, int nwin, int S, int pad, int ws, int H, int W, float scale,
                               void* stream);
